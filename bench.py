@@ -65,7 +65,34 @@ def parse():
     ap.add_argument("--grad-sync", default="flat", choices=["flat", "ddp"],
                     help="N > 1: zero-copy slice-wise all-reduce of the flat gradient buffer (self-checked, falls back "
                          "to ddp) or torch DistributedDataParallel")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as float32 DIR/<name>.npy (rank 0): loss, logits, "
+                         "the parameters after its optimizer step and its gradients (see dump_outputs)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+# elements written per output by --dump-outputs: a larger one is replaced by a fixed, seeded sample of its elements, so the dump
+# stays under 64 MB (JPEG-Ti's 5.6 M parameters and their gradients are written whole)
+DUMP_ELEMS = {"loss": 1, "logits": 2_000_000, "params": 6_000_000, "grads": 6_000_000}
+
+
+def dump_outputs(d, outs):
+    """outs: name -> tensor.  Writes each one in its own shape as float32 d/<name>.npy; one with more than DUMP_ELEMS[name] elements
+    is written as the 1-D array of its elements at sorted flat indices drawn without replacement by numpy's default_rng(0): the
+    same indices in every run with the same arguments."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    for name, t in outs.items():
+        x = t.detach().float()
+        n, cap = x.numel(), DUMP_ELEMS[name]
+        if n > cap:
+            idx = np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+            x = x.reshape(-1)[torch.from_numpy(idx).to(x.device)]
+        np.save(os.path.join(d, f"{name}.npy"), x.cpu().numpy())
 
 
 def _flat_sync_selfcheck(model, fsync, cdt, dev, B, dist, S=28):
@@ -478,10 +505,13 @@ def main():
             return mix((y, c), lab, lam=lam, out=None if out is None else (out[0], out[1], None))
         return mix((y, c), lab, out=None if out is None else out[:3])
 
+    last_logits = [None]         # the logits of the latest step (--dump-outputs); a graph replay writes the captured pass's tensor
+
     def model_part(my, mc, mt):
         logits = net(my, mc)
         loss = rg.cls_transforms.cross_entropy(logits, mt, grad_dtype=cdt)
         loss.backward()
+        last_logits[0] = logits
         return loss
 
     # One GPU: mixup output -> model forward -> loss -> backward (~110 of the step's ~150 launches, ~2.5 ms of host time next to
@@ -562,7 +592,7 @@ def main():
                     raise RuntimeError("graph replay does not resemble the eager pass")
             elif model.flat_grad_base() is None or not torch.equal(gloss.detach(), ref_loss) or not torch.equal(got_grad, ref_grad):
                 raise RuntimeError("graph replay does not reproduce the eager pass")
-            graph = (g, gloss, static)
+            graph = (g, gloss, static, last_logits[0])
             graph_inputs = (sy, sc, smt)
         except Exception as e:          # noqa: BLE001
             print(f"[bench] HIP graph capture unavailable ({type(e).__name__}: {e}); running eagerly", file=sys.stderr)
@@ -596,7 +626,7 @@ def main():
                 data_part(out=graph[2])
                 deferred.finish(opt.step)
                 graph[0].replay()
-                loss = graph[1]
+                loss, last_logits[0] = graph[1], graph[3]
             else:
                 (my, mc), mt = data_part()
                 deferred.finish(opt.step)
@@ -611,6 +641,7 @@ def main():
         if graph is not None and use_graph and not eager:
             data_part(out=graph[2])
             graph[0].replay()
+            last_logits[0] = graph[3]
             if world > 1:
                 exchange_after_replay()
             opt.step()
@@ -637,6 +668,13 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    # The prewarm loop runs for a time, not a number of steps, and at N > 1 the schedule calibration picks its candidate by measurement:
+    # their steps only bring the clocks up and choose how to run.  Parameters, optimizer state and random streams are put back after
+    # them, so that with the same arguments every run times the same steps on the same inputs (--dump-outputs).
+    import copy
+    opt_state0 = copy.deepcopy(opt.state_dict())
+    model_state0 = {k: v.clone() for k, v in model.state_dict().items()}
+    rng_state0 = (None if a.no_augment else sampler.rng.bit_generator.state, torch.get_rng_state(), torch.cuda.get_rng_state(dev))
     t_pre = time.perf_counter()
     while True:                                            # DVFS ramp: cold clocks cost up to 40 % on the first runs
         go = time.perf_counter() - t_pre < a.prewarm_sec
@@ -709,6 +747,13 @@ def main():
             if pick:
                 sync_schedule, fs.bucket_elems, use_graph = pick[0][0], pick[0][1], pick[0][2]
                 use_deferred = "next step's data stage" in sync_schedule
+    model.load_state_dict(model_state0)              # in place: the flat buffer the captured graph reads stays where it is
+    opt.load_state_dict(opt_state0)
+    if rng_state0[0] is not None:
+        sampler.rng.bit_generator.state = rng_state0[0]
+    torch.set_rng_state(rng_state0[1])
+    torch.cuda.set_rng_state(rng_state0[2], dev)
+    del model_state0, opt_state0
     # every traced kernel class: (tag, key in profiles/pmc_traffic*.json / pmc_mfma*.json, the roof SURVEY 8d names for it, description)
     TRACED = ((6, "chain_bwd", "mfma", "vit_chain_bwd_kernel: the data path of the whole encoder backward, one launch, one workgroup per image"),
               (5, "chain_fwd", "mfma", "vit_chain_fwd_kernel: the whole encoder forward, one launch, one workgroup per image"),
@@ -781,6 +826,12 @@ def main():
         dt = t.item()
     ms = dt / a.steps * 1e3
     value = world * B * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed step receives from its last run: the loss, the logits of the forward, the parameters after the
+        # optimizer step and the gradients it applied (N > 1: averaged over the ranks)
+        dump_outputs(a.dump_outputs, {"loss": loss, "logits": last_logits[0],
+                                      "params": torch.cat([p.detach().reshape(-1) for p in model.parameters()]),
+                                      "grads": torch.cat([p.grad.reshape(-1) for p in model.parameters()])})
     if rank == 0 and step_times:
         worst = sorted(step_times, reverse=True)[:6]
         print("[bench] slowest steps on the host (ms, index, traced): " + ", ".join(f"({1e3 * t:.2f}, {i}, {int(tr)})" for t, i, tr in worst)

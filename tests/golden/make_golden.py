@@ -253,11 +253,7 @@ def main():
     feat = torch.cat([pe.collapser(yy), pe.collapser(pe.rearrange_C(tc))], dim=3)
     np.savez_compressed(os.path.join(HERE, "g9_subblock.npz"), feat=feat.numpy(), convY=pe.conv_Y.numpy())
 
-    # ---------------- G10 sin-cos table -------------------------------------------------------
-    sc = pvit.SinCosEmbedding()
-    t192 = sc(torch.zeros((1, 14, 14, 192))).reshape(196, 192).numpy()
-    t384 = sc(torch.zeros((1, 14, 14, 384))).reshape(196, 384).numpy()
-    np.savez_compressed(os.path.join(HERE, "g10_sincos.npz"), t192=t192, t384_rows=t384[[0, 1, 13, 14, 97, 195]])
+    # ---------------- G10 sin-cos table: make_golden_sincos.py (MKL's reproducible mode, set before torch starts) -------------
 
     # ---------------- G11 model forward/backward ----------------------------------------------
     g11 = {}

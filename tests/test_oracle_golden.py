@@ -1,6 +1,9 @@
 """Pin the oracle (oracle/dct_np.py, oracle/vit_torch.py) against golden vectors captured from the
 reference itself (tests/golden/make_golden.py).  CPU only."""
 import math
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -9,6 +12,8 @@ import torch
 from oracle import dct_np as O
 from oracle import vit_torch as V
 from rgb_no_more_amd import detfill
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_g2_dequant(golden):
@@ -162,10 +167,17 @@ def test_g9_subblock_features(golden):
     assert np.array_equal(feat[..., 256:], g["feat"][..., 256:])
 
 
-def test_g10_sincos(golden):
+def test_g10_sincos(golden, tmp_path):
+    """G10 holds the reference's tables under MKL's reproducible mode COMPATIBLE (make_golden_sincos.py): torch's CPU exp / sin / cos
+    otherwise round by the CPU's MKL code path.  MKL reads the mode when it starts, so the oracle runs in a child process."""
     g = golden("g10_sincos.npz")
-    assert np.array_equal(V.sincos_table(14, 14, 192).numpy(), g["t192"])
-    assert np.array_equal(V.sincos_table(14, 14, 384).numpy()[[0, 1, 13, 14, 97, 195]], g["t384_rows"])
+    out = tmp_path / "t.npz"
+    code = ("import sys; import numpy as np; sys.path.insert(0, sys.argv[1]); from oracle import vit_torch as V; "
+            "np.savez(sys.argv[2], t192=V.sincos_table(14, 14, 192).numpy(), t384=V.sincos_table(14, 14, 384).numpy())")
+    subprocess.run([sys.executable, "-c", code, ROOT, str(out)], env=dict(os.environ, MKL_CBWR="COMPATIBLE"), check=True, timeout=300)
+    t = np.load(out)
+    assert np.array_equal(t["t192"], g["t192"])
+    assert np.array_equal(t["t384"][[0, 1, 13, 14, 97, 195]], g["t384_rows"])
 
 
 @pytest.mark.parametrize("tag,emb,heads,depth,B", [("ti_d2", 192, 3, 2, 2), ("ti_d12", 192, 3, 12, 4), ("s_d2", 384, 6, 2, 2)])
