@@ -9,8 +9,16 @@
  *   - plain pointers + sizes; device pointers unless the name says host; no C++/torch types.
  *   - returns 0 on success, negative RGBNM_E* otherwise; never throws; never allocates device memory;
  *     keeps no per-call state; all work is enqueued on `stream` (a hipStream_t passed as void*), no sync.
- *   - dtype: 0 = fp32 ("strict" mode, exact-fp32 MFMA), 1 = bf16 (fp32 accumulate).  Activations and
+ *   - dtype: 0 = fp32 ("strict" mode, exact-fp32 MFMA), 1 = bf16 (fp32 accumulate), 2 = fp16 (IEEE half, fp32
+ *     accumulate; conversions round to nearest even and overflow to +-inf, like torch's .half()).  Activations and
  *     MFMA operands use that type; parameters, gradients, statistics and optimizer state are fp32.
+ *     RGBNM_DT_F16 is accepted by: rgbnm_gemm_nt, rgbnm_gemm_tn, rgbnm_prep_weights[_chain] (without chain images),
+ *     rgbnm_layernorm_fwd / _bwd, rgbnm_head_pool_fwd / _bwd, rgbnm_attention_fwd / _bwd, rgbnm_subblock_embed[_mix]
+ *     (out_dtype; in_dtype fp32 / bf16 / fp16 with an fp16 output), rgbnm_softxent / _grad / _grad_mix (dl_dtype) and,
+ *     through rgbnm_vit_cfg.dtype, the ViT composites (patch embedding, blocks, head).  They run the generic kernels;
+ *     the bf16-tuned ones (one-launch chains, k-pipelined / weight-resident / small-M GEMMs, fused MLP, attention v2,
+ *     pipelined weight-gradient kernels, LayerNorm-chained epilogues) are bf16 only and are skipped for fp16.
+ *     Everything else (SwinV2, the augment stage, rgbnm_mixup) takes fp32 / bf16 only.
  *   - tensors are dense row-major; "ld*" are row strides in elements.
  */
 #ifndef RGBNM_H
@@ -25,7 +33,8 @@ extern "C" {
 #define RGBNM_ABI_VERSION 3
 #define RGBNM_DT_F32 0
 #define RGBNM_DT_BF16 1
-#define RGBNM_DT_I16 2   /* only as out_dtype of rgbnm_dct_augment[_ex] */
+#define RGBNM_DT_F16 2   /* see the list of entries above */
+#define RGBNM_DT_I16 2   /* only as out_dtype of rgbnm_dct_augment[_ex] (which has no fp16 output) */
 
 /* epilogues of rgbnm_gemm_nt */
 #define RGBNM_EPI_NONE 0   /* C = A.W^T (+bias)                                         */

@@ -216,8 +216,8 @@ class _SoftXent(torch.autograd.Function):
 def cross_entropy(logits: Tensor, target: Tensor, grad_dtype=torch.float32) -> Tensor:
     """torch.nn.CrossEntropyLoss()(logits, target) for class-index (int64 [B]) or probability ([B,C] fp32)
     targets, mean reduction: one HIP launch forward, one backward.  grad_dtype: the dtype the model's head wants its dlogits
-    in; honoured when `logits` come from a rgb-no-more_amd head that handed out a gradient edge of that dtype (fp32 logits keep an
-    fp32 gradient otherwise, as autograd demands)."""
+    in (torch.bfloat16 or torch.float16 for a head computing in that dtype); honoured when `logits` come from a rgb-no-more_amd head
+    that handed out a gradient edge of that dtype (fp32 logits keep an fp32 gradient otherwise, as autograd demands)."""
     mixlam = None
     if isinstance(target, LazyTarget):          # RandomMixup_DCT(lazy_target=True): labels + lambda
         if target.num_classes != logits.shape[1]:

@@ -64,9 +64,10 @@ __device__ __forceinline__ Frag<T> tfrag(const T* img, int d, int t, int fi, int
   if constexpr (sizeof(T) == 2) {
     // regs 8*fi .. 8*fi+7  <->  keys 32t + 16fi + 4g + {0..3}  and  + 8 + {0..3}
     const T* p = img + d * TP + 32 * t + 16 * fi + 4 * g;
-    const bf16x4 lo = *reinterpret_cast<const bf16x4*>(p);
-    const bf16x4 hi = *reinterpret_cast<const bf16x4*>(p + 8);
-    f.v = (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    using V4 = typename Vec4<T>::type;       // bf16 or fp16
+    const V4 lo = *reinterpret_cast<const V4*>(p);
+    const V4 hi = *reinterpret_cast<const V4*>(p + 8);
+    f.v = (typename Vec8<T>::type){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   } else {
     // regs 4*fi .. 4*fi+3  <->  keys 32t + 8fi + 4g + {0..3}
     f.v = *reinterpret_cast<const f32x4*>(img + d * TP + 32 * t + 8 * fi + 4 * g);
@@ -464,11 +465,13 @@ int rgbnm_attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B
   if (N > AN<7>::NPAD) {       // 225 .. 320 tokens (embed_type 3: 294): generic kernels with 10 tiles
     if (dtype == DT_BF16) return attn_fwd_t<bf16, 10>(qkv, out, lse, B, N, heads, scale, st);
     if (dtype == DT_F32) return attn_fwd_t<float, 10>(qkv, out, lse, B, N, heads, scale, st);
+    if (dtype == DT_F16) return attn_fwd_t<f16, 10>(qkv, out, lse, B, N, heads, scale, st);
     return RGBNM_EINVAL;
   }
   if (dtype == DT_BF16 && rgbnm_get_option("attn_v2")) return rgbnm_launch_attn2_fwd(qkv, out, lse, B, N, heads, scale, st);
   if (dtype == DT_BF16) return attn_fwd_t<bf16, 7>(qkv, out, lse, B, N, heads, scale, st);
   if (dtype == DT_F32) return attn_fwd_t<float, 7>(qkv, out, lse, B, N, heads, scale, st);
+  if (dtype == DT_F16) return attn_fwd_t<f16, 7>(qkv, out, lse, B, N, heads, scale, st);
   return RGBNM_EINVAL;
 }
 
@@ -479,12 +482,14 @@ int rgbnm_attention_bwd(int dtype, const void* qkv, const void* out, const void*
   if (N > AN<7>::NPAD) {
     if (dtype == DT_BF16) return attn_bwd_t<bf16, 10>(qkv, out, dout, lse, dqkv, B, N, heads, scale, st);
     if (dtype == DT_F32) return attn_bwd_t<float, 10>(qkv, out, dout, lse, dqkv, B, N, heads, scale, st);
+    if (dtype == DT_F16) return attn_bwd_t<f16, 10>(qkv, out, dout, lse, dqkv, B, N, heads, scale, st);
     return RGBNM_EINVAL;
   }
   if (dtype == DT_BF16 && rgbnm_get_option("attn_v2"))
     return rgbnm_launch_attn2_bwd(qkv, out, dout, lse, dqkv, B, N, heads, scale, st);
   if (dtype == DT_BF16) return attn_bwd_t<bf16, 7>(qkv, out, dout, lse, dqkv, B, N, heads, scale, st);
   if (dtype == DT_F32) return attn_bwd_t<float, 7>(qkv, out, dout, lse, dqkv, B, N, heads, scale, st);
+  if (dtype == DT_F16) return attn_bwd_t<f16, 7>(qkv, out, dout, lse, dqkv, B, N, heads, scale, st);
   return RGBNM_EINVAL;
 }
 

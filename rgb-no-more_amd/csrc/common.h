@@ -7,6 +7,12 @@
 typedef __bf16 bf16;
 typedef bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef bf16 bf16x4 __attribute__((ext_vector_type(4)));
+// fp16 (IEEE binary16): conversions from fp32 are the compiler's (v_cvt_f16_f32 / v_cvt_pk_f16_f32: round to nearest even,
+// overflow to +-inf, subnormals kept -- hipcc's default kernel mode keeps fp16 denormals, float_denorm_mode_16_64 = 3),
+// i.e. torch's `.half()`.  Never __builtin_amdgcn_cvt_pkrtz (round toward zero).
+typedef _Float16 f16;
+typedef f16 f16x8 __attribute__((ext_vector_type(8)));
+typedef f16 f16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -24,7 +30,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define RGBNM_ELAUNCH (-2)
 #define RGBNM_EWORKSPACE (-3)
 
-enum { DT_F32 = 0, DT_BF16 = 1 };
+enum { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2 };
 
 // "hipFuncSetAttribute already done for this kernel on this device": per function and per device, lock-free.  Racing
 // host threads may both set the (idempotent) attribute; nobody launches before it is set.  Keeps the launchers re-entrant.
@@ -55,6 +61,10 @@ template <> struct Frag<bf16> {
   bf16x8 v;
   static constexpr int EPL = 8;
 };
+template <> struct Frag<f16> {      // same lane / slot layout as bf16
+  f16x8 v;
+  static constexpr int EPL = 8;
+};
 template <> struct Frag<float> {
   f32x4 v;
   static constexpr int EPL = 4;
@@ -62,6 +72,9 @@ template <> struct Frag<float> {
 
 __device__ __forceinline__ void mma(f32x16& acc, const Frag<bf16>& a, const Frag<bf16>& b) {
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, b.v, acc, 0, 0, 0);
+}
+__device__ __forceinline__ void mma(f32x16& acc, const Frag<f16>& a, const Frag<f16>& b) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.v, b.v, acc, 0, 0, 0);
 }
 __device__ __forceinline__ void mma(f32x16& acc, const Frag<float>& a, const Frag<float>& b) {
 #pragma unroll
@@ -77,6 +90,11 @@ template <> __device__ __forceinline__ Frag<bf16> load_frag<bf16>(const bf16* p)
   f.v = *reinterpret_cast<const bf16x8*>(p);
   return f;
 }
+template <> __device__ __forceinline__ Frag<f16> load_frag<f16>(const f16* p) {
+  Frag<f16> f;
+  f.v = *reinterpret_cast<const f16x8*>(p);
+  return f;
+}
 template <> __device__ __forceinline__ Frag<float> load_frag<float>(const float* p) {
   Frag<float> f;
   f.v = *reinterpret_cast<const f32x4*>(p);
@@ -85,11 +103,22 @@ template <> __device__ __forceinline__ Frag<float> load_frag<float>(const float*
 
 template <typename T> __device__ __forceinline__ float to_f32(T x) { return (float)x; }
 template <typename T> __device__ __forceinline__ T from_f32(float x) { return (T)x; }
+// fp16: the fp32 value is formed first and then rounded, like torch's `.half()` of an fp32 result -- without the opaque step
+// the compiler folds a final multiply into the conversion (v_fma_mixlo_f16: one rounding instead of two, other bits)
+template <> __device__ __forceinline__ f16 from_f32<f16>(float x) {
+  asm volatile("" : "+v"(x));
+  return (f16)x;
+}
 
 // 4 consecutive elements <-> 4 floats (8-byte / 16-byte accesses)
 template <typename T> struct Vec4;
 template <> struct Vec4<bf16> { typedef bf16x4 type; };
+template <> struct Vec4<f16> { typedef f16x4 type; };
 template <> struct Vec4<float> { typedef f32x4 type; };
+// 8 consecutive 16-bit elements (one 16-byte vector)
+template <typename T> struct Vec8;
+template <> struct Vec8<bf16> { typedef bf16x8 type; };
+template <> struct Vec8<f16> { typedef f16x8 type; };
 
 template <typename T> __device__ __forceinline__ f32x4 load4(const T* p) {
   typename Vec4<T>::type v = *reinterpret_cast<const typename Vec4<T>::type*>(p);
@@ -109,7 +138,7 @@ __device__ __forceinline__ int lane_id_here() {
 
 template <typename T> __device__ __forceinline__ void store4(T* p, f32x4 v) {
   typename Vec4<T>::type o;
-  o[0] = (T)v[0]; o[1] = (T)v[1]; o[2] = (T)v[2]; o[3] = (T)v[3];
+  o[0] = from_f32<T>(v[0]); o[1] = from_f32<T>(v[1]); o[2] = from_f32<T>(v[2]); o[3] = from_f32<T>(v[3]);
   *reinterpret_cast<typename Vec4<T>::type*>(p) = o;
 }
 
@@ -178,6 +207,13 @@ __device__ __forceinline__ void store_c2(bf16* ptr, const bf16x8& v) {
   __builtin_nontemporal_store(v, reinterpret_cast<bf16x8*>(ptr));
 #else
   *reinterpret_cast<bf16x8*>(ptr) = v;
+#endif
+}
+__device__ __forceinline__ void store_c2(f16* ptr, const f16x8& v) {
+#if NT_C2
+  __builtin_nontemporal_store(v, reinterpret_cast<f16x8*>(ptr));
+#else
+  *reinterpret_cast<f16x8*>(ptr) = v;
 #endif
 }
 

@@ -361,6 +361,9 @@ int rgbnm_subblock_embed_mix(int in_dtype, int out_dtype, const void* y, const v
   else if (in_dtype == DT_F32 && out_dtype == DT_BF16) SB(float, bf16);
   else if (in_dtype == DT_BF16 && out_dtype == DT_BF16) SB(bf16, bf16);
   else if (in_dtype == DT_BF16 && out_dtype == DT_F32) SB(bf16, float);
+  else if (in_dtype == DT_F32 && out_dtype == DT_F16) SB(float, f16);
+  else if (in_dtype == DT_BF16 && out_dtype == DT_F16) SB(bf16, f16);
+  else if (in_dtype == DT_F16 && out_dtype == DT_F16) SB(f16, f16);
   else return RGBNM_EINVAL;
 #undef SB
   rgbnm_trace_end(tslot, st);
@@ -381,6 +384,8 @@ int rgbnm_softxent(int dl_dtype, const float* logits, const float* soft_target, 
     hipLaunchKernelGGL((softxent_kernel<bf16>), dim3(B), dim3(256), 0, st, logits, soft_target, hard_target, loss_rows, (bf16*)dlogits, C, grad_scale);
   else if (dl_dtype == DT_F32)
     hipLaunchKernelGGL((softxent_kernel<float>), dim3(B), dim3(256), 0, st, logits, soft_target, hard_target, loss_rows, (float*)dlogits, C, grad_scale);
+  else if (dl_dtype == DT_F16)
+    hipLaunchKernelGGL((softxent_kernel<f16>), dim3(B), dim3(256), 0, st, logits, soft_target, hard_target, loss_rows, (f16*)dlogits, C, grad_scale);
   else return RGBNM_EINVAL;
   LAUNCH_CHECK();
   hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, st, loss_rows, loss, B);
@@ -405,6 +410,8 @@ int rgbnm_softxent_grad(int dl_dtype, const float* logits, const float* soft_tar
     hipLaunchKernelGGL((softxent_grad_kernel<bf16>), dim3(B), dim3(256), 0, st, logits, soft_target, hard_target, row_stats, gout_dev, (bf16*)dlogits, C, grad_scale);
   else if (dl_dtype == DT_F32)
     hipLaunchKernelGGL((softxent_grad_kernel<float>), dim3(B), dim3(256), 0, st, logits, soft_target, hard_target, row_stats, gout_dev, (float*)dlogits, C, grad_scale);
+  else if (dl_dtype == DT_F16)
+    hipLaunchKernelGGL((softxent_grad_kernel<f16>), dim3(B), dim3(256), 0, st, logits, soft_target, hard_target, row_stats, gout_dev, (f16*)dlogits, C, grad_scale);
   else return RGBNM_EINVAL;
   LAUNCH_CHECK();
   return RGBNM_OK;
@@ -427,6 +434,8 @@ int rgbnm_softxent_grad_mix(int dl_dtype, const float* logits, const long long* 
     hipLaunchKernelGGL((softxent_grad_kernel<bf16>), dim3(B), dim3(256), 0, st, logits, (const float*)nullptr, labels, row_stats, gout_dev, (bf16*)dlogits, C, grad_scale, mix_lam);
   else if (dl_dtype == DT_F32)
     hipLaunchKernelGGL((softxent_grad_kernel<float>), dim3(B), dim3(256), 0, st, logits, (const float*)nullptr, labels, row_stats, gout_dev, (float*)dlogits, C, grad_scale, mix_lam);
+  else if (dl_dtype == DT_F16)
+    hipLaunchKernelGGL((softxent_grad_kernel<f16>), dim3(B), dim3(256), 0, st, logits, (const float*)nullptr, labels, row_stats, gout_dev, (f16*)dlogits, C, grad_scale, mix_lam);
   else return RGBNM_EINVAL;
   LAUNCH_CHECK();
   return RGBNM_OK;

@@ -13,6 +13,7 @@
 // bank-conflict free (9*i mod 16 distinct).
 #include "common.h"
 #include <mutex>
+#include <type_traits>
 #include <vector>
 #include "../../include/rgbnm.h"
 #include "internal.h"
@@ -32,8 +33,8 @@ struct GemmNT {
 constexpr int BM = 128;
 constexpr int PITCH_B = 144;  // bytes per LDS tile row
 
-// STAGED (bf16 only): the MFMA is issued with operands swapped (D rows <-> weight rows, D cols <-> tokens) so a
-// lane owns ONE token and 4 consecutive output features per register quad; the tile is rounded to bf16 into LDS
+// STAGED (16-bit T: bf16 / fp16): the MFMA is issued with operands swapped (D rows <-> weight rows, D cols <-> tokens) so a
+// lane owns ONE token and 4 consecutive output features per register quad; the tile is rounded to T into LDS
 // (8-byte writes, pitch BN+4 elements: conflict free) and leaves the CU as coalesced 16-byte rows, where the
 // residual / GELU / dGELU operands are also read as 16-byte vectors.
 template <typename T, int NB, int EPI, bool STAGED>
@@ -137,8 +138,10 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNT p) {
   }
 
   if constexpr (STAGED) {
-    // ---- pass 1: registers -> LDS (bf16(acc + bias [+ pos])) ; lane = token, quad = 4 features ----
-    bf16* Cs = reinterpret_cast<bf16*>(smem);
+    // ---- pass 1: registers -> LDS (T(acc + bias [+ pos])) ; lane = token, quad = 4 features ----
+    T* Cs = reinterpret_cast<T*>(smem);
+    using V4 = typename Vec4<T>::type;
+    using V8 = typename Vec8<T>::type;
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
       const int ml = wm * 64 + a * 32 + l31;
@@ -161,43 +164,43 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNT p) {
             const f32x4 pv = *reinterpret_cast<const f32x4*>(posr + nc);
             v += pv;
           }
-          store4<bf16>(Cs + ml * CP + nl, v);
+          store4<T>(Cs + ml * CP + nl, v);
         }
     }
     __syncthreads();
     // ---- pass 2: LDS -> global, 8 features (16 B) per thread-iteration, rows fully coalesced ----
     constexpr int VPR = BN / 8;
-    bf16* C = reinterpret_cast<bf16*>(p.C);
-    const bf16* R = reinterpret_cast<const bf16*>(p.R);
-    bf16* C2 = reinterpret_cast<bf16*>(p.C2);
+    T* C = reinterpret_cast<T*>(p.C);
+    const T* R = reinterpret_cast<const T*>(p.R);
+    T* C2 = reinterpret_cast<T*>(p.C2);
     int row = tid / VPR, vec = tid % VPR;
 #pragma unroll 4
     for (int i = 0; i < BM * VPR / 256; ++i, row += 256 / VPR, vec += 256 % VPR) {
       if (vec >= VPR) { vec -= VPR; row += 1; }
       const int gm = m0 + row, gn = n0 + vec * 8;
       if (gm >= p.M || gn >= p.N) continue;
-      const bf16x4 c0 = *reinterpret_cast<const bf16x4*>(Cs + row * CP + vec * 8);
-      const bf16x4 c1 = *reinterpret_cast<const bf16x4*>(Cs + row * CP + vec * 8 + 4);
-      bf16x8 cv = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
+      const V4 c0 = *reinterpret_cast<const V4*>(Cs + row * CP + vec * 8);
+      const V4 c1 = *reinterpret_cast<const V4*>(Cs + row * CP + vec * 8 + 4);
+      V8 cv = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
       if (EPI == EPI_GELU) {
         // one erf/exp evaluation yields gelu(u) (-> C) and gelu'(u) (-> C2, consumed by EPI_DGELU in backward)
-        bf16x8 dv;
+        V8 dv;
 #pragma unroll
         for (int e = 0; e < 8; e += 2) {
           const f32x2 u = {(float)cv[e], (float)cv[e + 1]};
           f32x2 gv, dgv;
           gelu_pair_fast(u, gv, dgv);
-          dv[e] = (bf16)dgv[0];
-          dv[e + 1] = (bf16)dgv[1];
-          cv[e] = (bf16)gv[0];
-          cv[e + 1] = (bf16)gv[1];
+          dv[e] = from_f32<T>(dgv[0]);
+          dv[e + 1] = from_f32<T>(dgv[1]);
+          cv[e] = from_f32<T>(gv[0]);
+          cv[e + 1] = from_f32<T>(gv[1]);
         }
-        *reinterpret_cast<bf16x8*>(C2 + (size_t)gm * p.ldc2 + gn) = dv;
+        *reinterpret_cast<V8*>(C2 + (size_t)gm * p.ldc2 + gn) = dv;
       }
       if (EPI != EPI_NONE && EPI != EPI_POS && EPI != EPI_GELU) {
-        bf16x8 rv;
+        V8 rv;
         if (EPI == EPI_RES || EPI == EPI_DGELU || EPI == EPI_DTANH)
-          rv = *reinterpret_cast<const bf16x8*>(R + (size_t)gm * p.ldr + gn);
+          rv = *reinterpret_cast<const V8*>(R + (size_t)gm * p.ldr + gn);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           float v = (float)cv[e];
@@ -208,10 +211,10 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNT p) {
             const float h = (float)rv[e];
             v *= (1.f - h * h);
           }
-          cv[e] = (bf16)v;
+          cv[e] = from_f32<T>(v);
         }
       }
-      *reinterpret_cast<bf16x8*>(C + (size_t)gm * p.ldc + gn) = cv;
+      *reinterpret_cast<V8*>(C + (size_t)gm * p.ldc + gn) = cv;
     }
     return;
   }
@@ -275,7 +278,9 @@ int launch_nt_epi(const GemmNT& p, int epi, hipStream_t st) {
 template <typename T, int NB>
 int launch_nt_sel(const GemmNT& p, int epi, hipStream_t st) {
   if constexpr (sizeof(T) == 2) {
-    if (p.M <= 512 && !p.pos && !p.C2 && rgbnm_get_option("nt_small")) {
+    // the small-M, k-pipelined and weight-resident kernels are bf16 only: fp16 takes the generic staged kernel
+    constexpr bool fast = std::is_same<T, bf16>::value;
+    if (fast && p.M <= 512 && !p.pos && !p.C2 && rgbnm_get_option("nt_small")) {
       // few rows (the classification head: M = batch): 32 x 32 tiles, the reduction split over a workgroup's four waves
       // (gemm_nt_small.hip); 1 = shape / epilogue not eligible
       const int rc = rgbnm_launch_nt_small(epi, p.A, p.lda, p.W, p.ldw, p.C, p.ldc, p.bias, p.R, p.ldr, p.c_f32, p.M, p.N,
@@ -284,14 +289,14 @@ int launch_nt_sel(const GemmNT& p, int epi, hipStream_t st) {
     }
     const bool ok = !p.c_f32 && (p.N % 8 == 0) && (p.ldc % 8 == 0) && (!p.R || p.ldr % 8 == 0) &&
                     (!p.C2 || p.ldc2 % 8 == 0) && rgbnm_get_option("nt_staged");
-    if (ok && !p.pos && rgbnm_get_option("nt_kpipe")) {
+    if (fast && ok && !p.pos && rgbnm_get_option("nt_kpipe")) {
       // N % 192 == 0 with a long reduction (K >= 256): 224-row panels x 192-column tiles, k-tiles through an LDS-DMA ring
       // (gemm_nt_kpipe.hip); N = 192: one row panel per CU
       const int rc = rgbnm_launch_nt_kpipe(epi, p.A, p.lda, p.W, p.ldw, p.C, p.ldc, p.bias, p.R, p.ldr, p.C2, p.ldc2, p.M,
                                            p.N, p.K, st);
       if (rc != 1) return rc;
     }
-    if (ok && !p.pos && rgbnm_get_option("nt_wres")) {
+    if (fast && ok && !p.pos && rgbnm_get_option("nt_wres")) {
       // K = 192 layers: persistent weight-resident kernel (gemm_nt_wres.hip); 1 = shape not eligible
       const int rc = rgbnm_launch_nt_wres(epi, p.A, p.lda, p.W, p.ldw, p.C, p.ldc, p.bias, p.R, p.ldr, p.C2, p.ldc2,
                                           p.M, p.N, p.K, st);
@@ -336,18 +341,19 @@ template <typename T> __device__ __forceinline__ Frag<T> gather_frag(const T* ba
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-// ds_read_b64_tr_b16: within each 16-lane group, lane i supplies the address of 4 contiguous bf16 (row i>>2 of a
+// ds_read_b64_tr_b16: within each 16-lane group, lane i supplies the address of 4 contiguous 16-bit elements (row i>>2 of a
 // 4 x 16 block, columns 4*(i&3)..+3) and receives column i of that block (4 rows).  With tiles stored in their
 // natural [token][feature] layout this hands every lane 4 tokens of ITS feature: two reads = one MFMA fragment
 // (8 reduction slots), instead of 8 strided 2-byte reads.  A and B fragments use the same token<->slot mapping.
-__device__ __forceinline__ bf16x8 tr_pack(u32x2 lo, u32x2 hi) {
+template <typename T>
+__device__ __forceinline__ typename Vec8<T>::type tr_pack(u32x2 lo, u32x2 hi) {
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(bf16x8, v);
+  return __builtin_bit_cast(typename Vec8<T>::type, v);
 }
 
-template <int NB, int PAB, int PBB>   // pitches in BYTES
-__device__ __forceinline__ void tr_load_chunk(unsigned addrA, unsigned addrB, Frag<bf16> (&fa)[2], Frag<bf16> (&fb)[NB]) {
+template <int NB, int PAB, int PBB, typename T>   // pitches in BYTES; T: bf16 or fp16
+__device__ __forceinline__ void tr_load_chunk(unsigned addrA, unsigned addrB, Frag<T> (&fa)[2], Frag<T> (&fb)[NB]) {
   u32x2 a0l, a0h, a1l, a1h, b0l, b0h, b1l, b1h, b2l, b2h;
   asm volatile(
       "ds_read_b64_tr_b16 %0, %10\n\t"
@@ -367,11 +373,11 @@ __device__ __forceinline__ void tr_load_chunk(unsigned addrA, unsigned addrB, Fr
         "i"(NB == 3 ? 128 : 0), "i"(NB == 3 ? 128 + 4 * PBB : 4 * PBB)
       : "memory");
   __builtin_amdgcn_sched_barrier(0);
-  fa[0].v = tr_pack(a0l, a0h);
-  fa[1].v = tr_pack(a1l, a1h);
-  fb[0].v = tr_pack(b0l, b0h);
-  fb[1].v = tr_pack(b1l, b1h);
-  if constexpr (NB == 3) fb[2].v = tr_pack(b2l, b2h);
+  fa[0].v = tr_pack<T>(a0l, a0h);
+  fa[1].v = tr_pack<T>(a1l, a1h);
+  fb[0].v = tr_pack<T>(b0l, b0h);
+  fb[1].v = tr_pack<T>(b1l, b1h);
+  if constexpr (NB == 3) fb[2].v = tr_pack<T>(b2l, b2h);
 }
 
 template <typename T, int NB, bool TR>
@@ -607,7 +613,7 @@ int launch_tn(GemmTN p, float* dW, float* db, int perm_heads, int accumulate, hi
   const bool nb3 = (p.Ki % 192 == 0);
   p.ctiles = nb3 ? p.Ki / 192 : cdiv(p.Ki, 128);
   const int tiles = p.rtiles * p.ctiles;
-  if constexpr (sizeof(T) == 2) {
+  if constexpr (std::is_same<T, bf16>::value) {      // grouped / pipelined weight-gradient kernels: bf16 only
     tn_check_abort();
     if (g_tn_defer && tn_groupable(p)) {
       // a grouped launch has one workgroup per output tile and at most 256 of them (rgbnm_launch_tn_pipe_group): what is queued
@@ -857,6 +863,7 @@ int rgbnm_gemm_nt(int dtype, int epi, const void* A, int lda, const void* W, int
   hipStream_t st = (hipStream_t)stream;
   if (dtype == DT_BF16) return launch_nt<bf16>(p, epi, st);
   if (dtype == DT_F32) return launch_nt<float>(p, epi, st);
+  if (dtype == DT_F16) return launch_nt<f16>(p, epi, st);
   return RGBNM_EINVAL;
 }
 
@@ -887,6 +894,7 @@ int rgbnm_gemm_tn(int dtype, const void* dY, int ldy, const void* X, int ldx, fl
   hipStream_t st = (hipStream_t)stream;
   if (dtype == DT_BF16) return launch_tn<bf16>(p, dW, db, perm_heads, accumulate, st);
   if (dtype == DT_F32) return launch_tn<float>(p, dW, db, perm_heads, accumulate, st);
+  if (dtype == DT_F16) return launch_tn<f16>(p, dW, db, perm_heads, accumulate, st);
   return RGBNM_EINVAL;
 }
 
@@ -929,6 +937,9 @@ int rgbnm_prep_weights_chain(int dtype, const rgbnm_linear_desc* descs_dev, int 
   else if (dtype == DT_F32)
     hipLaunchKernelGGL((prep_weights_kernel<float>), dim3(64, ndesc), dim3(256), 0, st, descs_dev, master, (float*)shadow, bias_perm,
                        (float*)nullptr, (float*)nullptr, 0);
+  else if (dtype == DT_F16)
+    hipLaunchKernelGGL((prep_weights_kernel<f16>), dim3(64, ndesc), dim3(256), 0, st, descs_dev, master, (f16*)shadow, bias_perm,
+                       (f16*)nullptr, (f16*)nullptr, 0);
   else return RGBNM_EINVAL;
   LAUNCH_CHECK();
   return RGBNM_OK;

@@ -359,6 +359,7 @@ int rgbnm_layernorm_fwd(int dtype, const void* x, const float* gamma, const floa
   if (!x || !gamma || !beta || !y || !mean || !rstd || M <= 0) return RGBNM_EINVAL;
   if (dtype == DT_BF16) return ln_fwd_t<bf16>(x, gamma, beta, y, mean, rstd, M, E, eps, (hipStream_t)stream);
   if (dtype == DT_F32) return ln_fwd_t<float>(x, gamma, beta, y, mean, rstd, M, E, eps, (hipStream_t)stream);
+  if (dtype == DT_F16) return ln_fwd_t<f16>(x, gamma, beta, y, mean, rstd, M, E, eps, (hipStream_t)stream);
   return RGBNM_EINVAL;
 }
 
@@ -369,6 +370,7 @@ int rgbnm_layernorm_bwd(int dtype, const void* dy, const void* x, const float* g
   if (workspace_bytes < (size_t)LN_BWD_BLOCKS * 2 * E * sizeof(float)) return RGBNM_EWORKSPACE;
   if (dtype == DT_BF16) return ln_bwd_t<bf16>(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, M, E, accumulate, (float*)workspace, (hipStream_t)stream);
   if (dtype == DT_F32) return ln_bwd_t<float>(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, M, E, accumulate, (float*)workspace, (hipStream_t)stream);
+  if (dtype == DT_F16) return ln_bwd_t<f16>(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, M, E, accumulate, (float*)workspace, (hipStream_t)stream);
   return RGBNM_EINVAL;
 }
 
@@ -387,6 +389,11 @@ int rgbnm_head_pool_fwd(int dtype, const void* x, const float* gamma, const floa
   else if (dtype == DT_F32 && E == 512) POOL(float, 2, 64);
   else if (dtype == DT_F32 && E == 768) POOL(float, 3, 64);
   else if (dtype == DT_F32 && E == 1024) POOL(float, 4, 64);
+  else if (dtype == DT_F16 && E == 192) POOL(f16, 3);
+  else if (dtype == DT_F16 && E == 384) POOL(f16, 6);
+  else if (dtype == DT_F16 && E == 512) POOL(f16, 2, 64);
+  else if (dtype == DT_F16 && E == 768) POOL(f16, 3, 64);
+  else if (dtype == DT_F16 && E == 1024) POOL(f16, 4, 64);
   else return RGBNM_EINVAL;
 #undef POOL
   LAUNCH_CHECK();
@@ -411,6 +418,11 @@ int rgbnm_head_pool_bwd(int dtype, const void* dpooled, const void* x, const flo
   else if (dtype == DT_F32 && E == 512) POOLB(float, 2, 64);
   else if (dtype == DT_F32 && E == 768) POOLB(float, 3, 64);
   else if (dtype == DT_F32 && E == 1024) POOLB(float, 4, 64);
+  else if (dtype == DT_F16 && E == 192) POOLB(f16, 3);
+  else if (dtype == DT_F16 && E == 384) POOLB(f16, 6);
+  else if (dtype == DT_F16 && E == 512) POOLB(f16, 2, 64);
+  else if (dtype == DT_F16 && E == 768) POOLB(f16, 3, 64);
+  else if (dtype == DT_F16 && E == 1024) POOLB(f16, 4, 64);
   else return RGBNM_EINVAL;
 #undef POOLB
   LAUNCH_CHECK();

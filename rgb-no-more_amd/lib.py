@@ -8,7 +8,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "librgbnm.so")
 
-DT_F32, DT_BF16 = 0, 1
+DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 EPI_NONE, EPI_RES, EPI_GELU, EPI_POS, EPI_DGELU, EPI_TANH, EPI_DTANH = range(7)
 
 _vp, _i, _f, _sz, _ll = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_longlong
@@ -228,7 +228,9 @@ def dt_of(t):
         return DT_F32
     if t == torch.bfloat16:
         return DT_BF16
-    raise TypeError(f"unsupported dtype {t} (float32 or bfloat16)")
+    if t == torch.float16:
+        return DT_F16
+    raise TypeError(f"unsupported dtype {t} (float32, bfloat16 or float16)")
 
 
 def ptr(t):

@@ -4,7 +4,7 @@
 * same constructor signature as `pvit.ViT(...)` (pipeline_utils.py:335-349) and the same 152 `state_dict()`
   keys / shapes / default init (parameter holders are ordinary nn.Linear / nn.LayerNorm modules, never called);
 * `forward(y, cbcr) -> logits (B, n_classes) fp32`;
-* compute dtype = the active autocast dtype (bf16) or fp32 when autocast is off, so train.py's
+* compute dtype = the active autocast dtype (bf16 or fp16) or fp32 when autocast is off, so train.py's
   `--amp/--ampdtype` flags and its DDP loop work unchanged;
 * one autograd node per stage (patch-embed, each encoder block, head) = one C-ABI call each; parameter
   gradients are ordinary leaf grads, so DDP's bucketed all-reduce (RCCL) overlaps with backward.
@@ -785,7 +785,7 @@ class ViT(FlatParamModule):
             ("ch_linear2", nn.Linear(E, n_classes, **kw))]))
         self._flat = None
         self._arenas = {}
-        self.compute_dtype = None      # None: follow autocast; or force torch.float32 / torch.bfloat16
+        self.compute_dtype = None      # None: follow autocast; or force torch.float32 / torch.bfloat16 / torch.float16
 
     # ---------------------------------------------------------------- flat buffers / shadows
     def _names(self):
@@ -1088,7 +1088,9 @@ class ViT(FlatParamModule):
 
     # ---------------------------------------------------------------- forward
     def forward(self, x, cbcr=None):
-        """x: Y coefficients (B,1,28,28,8,8); cbcr: (B,2,14,14,8,8); fp32 or bf16 (reference: plainvit.py:601-611)."""
+        """x: Y coefficients (B,1,28,28,8,8); cbcr: (B,2,14,14,8,8); fp32, bf16 or fp16 (reference: plainvit.py:601-611).
+        Compute dtype: compute_dtype if set, else the autocast dtype (bf16 or fp16), else fp32.  fp16 runs the per-operation
+        path on the generic kernels (the one-launch encoder and the other bf16-tuned kernels are bf16 only)."""
         if cbcr is None:
             raise ValueError("DCT path needs both Y and CbCr tensors")
         lam = None
@@ -1109,16 +1111,8 @@ class ViT(FlatParamModule):
         cdtype = self.compute_dtype
         if cdtype is None:
             cdtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else torch.float32
-        if cdtype == torch.float16 and self.compute_dtype is None:
-            # the reference's eval.py:36 hard-codes autocast(float16) whenever --amp is on, also for bf16 training; the
-            # MI355X path has no fp16 kernels: run that forward in bf16 (same 8-bit-exponent-safe range, fp32 accumulate)
-            if not getattr(self, "_warned_fp16", False):
-                warnings.warn("rgb-no-more_amd: float16 autocast requested (reference eval.py:36); running the HIP "
-                              "forward in bfloat16", stacklevel=2)
-                self._warned_fp16 = True
-            cdtype = torch.bfloat16
-        if cdtype not in (torch.float32, torch.bfloat16):
-            raise NotImplementedError(f"compute dtype {cdtype}: the MI355X path implements fp32 and bf16")
+        if cdtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise NotImplementedError(f"compute dtype {cdtype}: the MI355X path implements fp32, bf16 and fp16")
         if self.drop_p and self.training:
             raise NotImplementedError("training with dropout p > 0 is not implemented on the HIP path (cfg.TRAIN.DROP is 0 in every "
                                       "reference config, configs.py:27); model.eval() runs, where nn.Dropout is the identity")

@@ -1,0 +1,147 @@
+#!/usr/bin/env python
+"""Time the training step of the ViT in its three compute configurations, in one process, alternating:
+
+  fp16          autocast(float16): fp16 activations on the generic kernels (the bf16-tuned kernels are bf16 only)
+  bf16_generic  bf16 with exactly the bf16-only kernels switched off (BF16_ONLY_OPTS): the kernel set fp16 runs
+  bf16          bf16 with every option at its default (what bench.py times)
+
+A step is what bench.py times, launched eagerly: augment (DCT-domain, fp32 output for fp16 and bf16_generic, bf16 for bf16),
+lazy mixup, forward, soft-target loss, backward, fused clip + AdamW + weight decay.  Per arch, every configuration runs WARMUP
+steps, then the timed steps in ROUNDS interleaved blocks (device events around each block, after a synchronise); every block
+starts from the initial weights (the step has no loss scaler, and the weights must stay where fp16 activations fit).  Also reports
+the max |logit - reference| at B = 256, depth 12 (golden g20, the reference ViT on detfill weights) per configuration.
+Prints one JSON line.  usage: python tools/fp16_step.py [--steps 300] [--warmup 50] [--rounds 6] [--arch vitti vits]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import rgb_no_more_amd as rg  # noqa: E402
+from rgb_no_more_amd import custom_transforms as CT, detfill, lib as L  # noqa: E402
+from bench import synth_coefficients  # noqa: E402
+
+ARCH = {"vitti": (192, 3), "vits": (384, 6)}
+# every library option that selects a bf16-only kernel (rgbnm.h: the fp16 entries skip them)
+BF16_ONLY_OPTS = ("fwd_chain", "bwd_chain", "nt_kpipe", "nt_wres", "nt_small", "tn_pipe", "tn_wide", "mlp_fuse", "mlp_bwd",
+                  "attn_v2", "ln_fuse")
+CONFIGS = ("fp16", "bf16_generic", "bf16")
+
+
+def set_opts(defaults, off):
+    lib = L.lib()
+    for k, v in defaults.items():
+        lib.rgbnm_set_option(k.encode(), 0 if (off and k in BF16_ONLY_OPTS) else v)
+
+
+def logit_error(cfg, defaults):
+    """max |logit - reference| of JPEG-Ti, depth 12, B = 256 (tests/golden/g20_fullsize.npz)."""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "g20_fullsize.npz"))
+    m = rg.ViT(3, 16, 192, depth=12, n_classes=1000, drop_p=0.0, device="cuda", num_heads=3, head_size=64, pixel_space="DCT", ver=1)
+    shapes = {k: tuple(v.shape) for k, v in m.state_dict().items()}
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in detfill.fill_state_dict(shapes, base_seed=1).items()})
+    y = torch.from_numpy(detfill.normalish((256, 1, 28, 28, 8, 8), 71)).cuda()
+    c = torch.from_numpy(detfill.normalish((256, 2, 14, 14, 8, 8), 72)).cuda()
+    set_opts(defaults, cfg == "bf16_generic")
+    m.train()
+    with torch.autocast("cuda", dtype=torch.float16 if cfg == "fp16" else torch.bfloat16):
+        out = m(y, c)
+    torch.cuda.synchronize()
+    set_opts(defaults, False)
+    return float(np.abs(out.detach().float().cpu().numpy() - g["ti_d12_b256_logits"]).max())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=300)
+    ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=6)
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--arch", nargs="+", default=["vitti", "vits"], choices=list(ARCH))
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "needs the GPU"
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    lib = L.lib()
+    defaults = {k: lib.rgbnm_get_option(k.encode()) for k in BF16_ONLY_OPTS}
+    print(f"bf16_generic: options switched off: {', '.join(BF16_ONLY_OPTS)}", file=sys.stderr)
+    B = a.batch
+    res = {"batch": B, "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "bf16_only_options_off": list(BF16_ONLY_OPTS)}
+    for arch in a.arch:
+        emb, heads = ARCH[arch]
+        torch.manual_seed(0)
+        model = rg.ViT(3, 16, emb, depth=12, n_classes=1000, drop_p=0.0, device=dev, num_heads=heads, head_size=64,
+                       pixel_space="DCT", ver=1, use_subblock=True)
+        model.train()
+        opt = rg.custom_optims.FusedClipAdamWWD(model, lr=1e-3, eps=1e-8, weight_decay=1e-4, max_norm=1.0)
+        Yq, Cq, quant = synth_coefficients(B, dev, 1234)
+        lab = torch.randint(0, 999, (B,), device=dev)
+        legs = {}
+        for cfg in CONFIGS:
+            adt = torch.bfloat16 if cfg == "bf16" else torch.float32          # augment output (no fp16 augment output)
+            cdt = torch.float16 if cfg == "fp16" else torch.bfloat16
+            aug = CT.TrainTransform_DCT(size=28, out_dtype=adt)
+            mix = rg.cls_transforms.RandomMixup_DCT(1000, alpha=0.2)
+            mix.out_dtype = adt
+            mix.lazy, mix.lazy_target = True, True
+            legs[cfg] = (aug, CT.FastParamSampler(aug, seed=1234), mix, cdt)
+
+        def step(cfg):
+            aug, sampler, mix, cdt = legs[cfg]
+            packed, nops = sampler.sample(B, 64, 64)
+            y, c = CT.apply_packed(aug, Yq, Cq, quant, packed, nops)
+            lam = mix.sample_lambda(dev)
+            (my, mc), mt = mix((y, c), lab, lam=lam)
+            with torch.autocast("cuda", dtype=cdt):
+                logits = model(my, mc)
+            loss = rg.cls_transforms.cross_entropy(logits, mt, grad_dtype=cdt)
+            loss.backward()
+            opt.step()
+            return loss
+
+        state = {k: v.detach().clone() for k, v in model.state_dict().items()}
+        for cfg in CONFIGS:
+            set_opts(defaults, cfg == "bf16_generic")
+            model.load_state_dict(state)
+            for _ in range(a.warmup):
+                step(cfg)
+        torch.cuda.synchronize()
+        ms = {cfg: [] for cfg in CONFIGS}
+        nonfinite = {cfg: 0 for cfg in CONFIGS}      # timed blocks whose last loss was not finite
+        per = max(1, a.steps // a.rounds)
+        for r in range(a.rounds):
+            for cfg in (CONFIGS if r % 2 == 0 else CONFIGS[::-1]):
+                set_opts(defaults, cfg == "bf16_generic")
+                model.load_state_dict(state)    # every block from the same weights (no loss scaler here: keep fp16 in range)
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(per):
+                    loss = step(cfg)
+                e1.record()
+                torch.cuda.synchronize()
+                if not torch.isfinite(loss).item():
+                    nonfinite[cfg] += 1
+                ms[cfg].append(e0.elapsed_time(e1) / per)
+        set_opts(defaults, False)
+        model.load_state_dict(state)
+        out = {cfg: {"step_ms_median": float(np.median(v)), "step_ms_min": float(min(v)), "step_ms_max": float(max(v)),
+                     "nonfinite_blocks": nonfinite[cfg]} for cfg, v in ms.items()}
+        out["fp16_over_bf16_generic"] = out["fp16"]["step_ms_median"] / out["bf16_generic"]["step_ms_median"]
+        out["fp16_over_bf16"] = out["fp16"]["step_ms_median"] / out["bf16"]["step_ms_median"]
+        res[arch] = out
+        print(f"{arch}: " + ", ".join(f"{k} {v['step_ms_median']:.3f} ms" for k, v in out.items() if isinstance(v, dict)), file=sys.stderr)
+        del model, opt
+        torch.cuda.empty_cache()
+    res["max_abs_dlogit_ti_b256"] = {cfg: logit_error(cfg, defaults) for cfg in CONFIGS}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
