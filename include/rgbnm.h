@@ -15,10 +15,12 @@
  *     RGBNM_DT_F16 is accepted by: rgbnm_gemm_nt, rgbnm_gemm_tn, rgbnm_prep_weights[_chain] (without chain images),
  *     rgbnm_layernorm_fwd / _bwd, rgbnm_head_pool_fwd / _bwd, rgbnm_attention_fwd / _bwd, rgbnm_subblock_embed[_mix]
  *     (out_dtype; in_dtype fp32 / bf16 / fp16 with an fp16 output), rgbnm_softxent / _grad / _grad_mix (dl_dtype) and,
- *     through rgbnm_vit_cfg.dtype, the ViT composites (patch embedding, blocks, head).  They run the generic kernels;
+ *     through rgbnm_vit_cfg.dtype, the ViT composites (patch embedding, blocks, head); and SwinV2's own entries:
+ *     rgbnm_window_attention_fwd / _bwd, rgbnm_swin_embed (out_dtype fp16 from any in_dtype; in_dtype fp16 to any
+ *     out_dtype), rgbnm_ln_generic_fwd / _bwd, rgbnm_merge_gather and rgbnm_token_mean.  They run the generic kernels;
  *     the bf16-tuned ones (one-launch chains, k-pipelined / weight-resident / small-M GEMMs, fused MLP, attention v2,
- *     pipelined weight-gradient kernels, LayerNorm-chained epilogues) are bf16 only and are skipped for fp16.
- *     Everything else (SwinV2, the augment stage, rgbnm_mixup) takes fp32 / bf16 only.
+ *     pipelined and grouped weight-gradient kernels, LayerNorm-chained epilogues, held reductions) are bf16 only and are
+ *     skipped for fp16.  Everything else (the augment stage, rgbnm_mixup) takes fp32 / bf16 only.
  *   - tensors are dense row-major; "ld*" are row strides in elements.
  */
 #ifndef RGBNM_H
@@ -519,6 +521,7 @@ int rgbnm_head_bwd(const rgbnm_vit_cfg* cfg, const rgbnm_head_params* p, const r
 
 /* ---------------------------------------------------------------------------------------------
  * SwinV2 DCT (models/swinv2.py; BASELINE config 5) - the parts that are not plain Linears (those use rgbnm_gemm_nt/tn).
+ * dtype of the entries below: RGBNM_DT_F32, RGBNM_DT_BF16 or RGBNM_DT_F16 (the position-bias entries are fp32 only).
  * ------------------------------------------------------------------------------------------- */
 /* PatchEmbedding_DCT_Group with patch 4 (swinv2.py:505-576, plainvit.py:50-88): every 8x8 block is decomposed,
  * X' = A^T X A with convY = conversion_matrix(4,2) / convC = conversion_matrix(2,4) (8x8 fp32 each), tokens on the

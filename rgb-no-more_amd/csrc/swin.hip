@@ -1,5 +1,6 @@
 // SwinV2 DCT specifics (BASELINE config 5; reference models/swinv2.py): everything of the model
-// that is not a plain Linear - the Linears run on the GEMM family of gemm.hip.
+// that is not a plain Linear - the Linears run on the GEMM family of gemm.hip.  Element types: fp32, bf16 and fp16 (fp32 sums; every
+// fp16 store rounds the fp32 value with from_f32).
 //   swin_embed      8x8 DCT blocks DEcomposed into 4x4 (Y) / 2x2 (CbCr) sub-block tokens: X' = A^T X A per block,
 //                   einops split '(p1 pdh) (p2 pdw)' (coefficient-major!), 16 + 2*4 = 24 features per token
 //                   (swinv2.py:556-576, plainvit.py:50-88)
@@ -392,7 +393,7 @@ __global__ __launch_bounds__(256) void token_mean_fwd_kernel(const T* __restrict
       for (int n = grp; n < N; n += groups) {
         const T* p = x + ((size_t)b * N + n) * C + v * EPV;
         if constexpr (sizeof(T) == 2) {
-          const bf16x8 t = *reinterpret_cast<const bf16x8*>(p);
+          const typename Vec8<T>::type t = *reinterpret_cast<const typename Vec8<T>::type*>(p);
 #pragma unroll
           for (int e = 0; e < 8; ++e) a[e] += (float)t[e];
         } else {
@@ -575,6 +576,11 @@ int rgbnm_swin_embed(int in_dtype, int out_dtype, const void* y, const void* cbc
   else if (in_dtype == DT_F32 && out_dtype == DT_BF16) EMB(float, bf16);
   else if (in_dtype == DT_BF16 && out_dtype == DT_BF16) EMB(bf16, bf16);
   else if (in_dtype == DT_BF16 && out_dtype == DT_F32) EMB(bf16, float);
+  else if (in_dtype == DT_F32 && out_dtype == DT_F16) EMB(float, f16);
+  else if (in_dtype == DT_BF16 && out_dtype == DT_F16) EMB(bf16, f16);
+  else if (in_dtype == DT_F16 && out_dtype == DT_F16) EMB(f16, f16);
+  else if (in_dtype == DT_F16 && out_dtype == DT_F32) EMB(f16, float);
+  else if (in_dtype == DT_F16 && out_dtype == DT_BF16) EMB(f16, bf16);
   else return RGBNM_EINVAL;
 #undef EMB
   LAUNCH_CHECK();
@@ -596,6 +602,7 @@ int rgbnm_ln_generic_fwd(int dtype, const void* x, const float* gamma, const flo
   if (rgbnm_get_option("ln_rows") && ln_rows_lpr(E)) {
     if (dtype == DT_BF16) ln_rows_fwd<bf16>(x, gamma, beta, res, sample_scale, rows_per_sample, y, mean, rstd, M, E, eps, st);
     else if (dtype == DT_F32) ln_rows_fwd<float>(x, gamma, beta, res, sample_scale, rows_per_sample, y, mean, rstd, M, E, eps, st);
+    else if (dtype == DT_F16) ln_rows_fwd<f16>(x, gamma, beta, res, sample_scale, rows_per_sample, y, mean, rstd, M, E, eps, st);
     else return RGBNM_EINVAL;
     LAUNCH_CHECK();
     return RGBNM_OK;
@@ -606,6 +613,8 @@ int rgbnm_ln_generic_fwd(int dtype, const void* x, const float* gamma, const flo
     hipLaunchKernelGGL(ln_generic_fwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)x, gamma, beta, (const bf16*)res, sample_scale, rows_per_sample, (bf16*)y, mean, rstd, M, E, eps);
   else if (dtype == DT_F32)
     hipLaunchKernelGGL(ln_generic_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, gamma, beta, (const float*)res, sample_scale, rows_per_sample, (float*)y, mean, rstd, M, E, eps);
+  else if (dtype == DT_F16)
+    hipLaunchKernelGGL(ln_generic_fwd_kernel<f16>, dim3(grid), dim3(256), 0, st, (const f16*)x, gamma, beta, (const f16*)res, sample_scale, rows_per_sample, (f16*)y, mean, rstd, M, E, eps);
   else return RGBNM_EINVAL;
   LAUNCH_CHECK();
   return RGBNM_OK;
@@ -625,11 +634,14 @@ int rgbnm_ln_generic_bwd(int dtype, const void* dy, const void* x, const float* 
   if (rgbnm_get_option("ln_rows") && ln_rows_lpr(E)) {
     if (dtype == DT_BF16) grid = ln_rows_bwd<bf16>(dy, x, gamma, mean, rstd, sample_scale, rows_per_sample, dx, part, M, E, st);
     else if (dtype == DT_F32) grid = ln_rows_bwd<float>(dy, x, gamma, mean, rstd, sample_scale, rows_per_sample, dx, part, M, E, st);
+    else if (dtype == DT_F16) grid = ln_rows_bwd<f16>(dy, x, gamma, mean, rstd, sample_scale, rows_per_sample, dx, part, M, E, st);
     else return RGBNM_EINVAL;
   } else if (dtype == DT_BF16)
     hipLaunchKernelGGL(ln_generic_bwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)dy, (const bf16*)x, gamma, mean, rstd, sample_scale, rows_per_sample, (bf16*)dx, part, M, E);
   else if (dtype == DT_F32)
     hipLaunchKernelGGL(ln_generic_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)dy, (const float*)x, gamma, mean, rstd, sample_scale, rows_per_sample, (float*)dx, part, M, E);
+  else if (dtype == DT_F16)
+    hipLaunchKernelGGL(ln_generic_bwd_kernel<f16>, dim3(grid), dim3(256), 0, st, (const f16*)dy, (const f16*)x, gamma, mean, rstd, sample_scale, rows_per_sample, (f16*)dx, part, M, E);
   else return RGBNM_EINVAL;
   LAUNCH_CHECK();
   RgbnmReduceJob j;
@@ -657,6 +669,7 @@ int rgbnm_merge_gather(int dtype, const void* in, void* out, int B, int res, int
   hipStream_t st = (hipStream_t)stream;
   if (dtype == DT_BF16) hipLaunchKernelGGL(merge_gather_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)in, (bf16*)out, B, res, C, inverse);
   else if (dtype == DT_F32) hipLaunchKernelGGL(merge_gather_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)in, (float*)out, B, res, C, inverse);
+  else if (dtype == DT_F16) hipLaunchKernelGGL(merge_gather_kernel<f16>, dim3(grid), dim3(256), 0, st, (const f16*)in, (f16*)out, B, res, C, inverse);
   else return RGBNM_EINVAL;
   LAUNCH_CHECK();
   return RGBNM_OK;
@@ -672,6 +685,7 @@ int rgbnm_token_mean(int dtype, const void* in, void* out, int B, int N, int C, 
            else hipLaunchKernelGGL(token_mean_fwd_scalar_kernel<T>, dim3(B), dim3(256), 0, st, (const T*)in, (T*)out, N, C); } } while (0)
   if (dtype == DT_BF16) TM(bf16);
   else if (dtype == DT_F32) TM(float);
+  else if (dtype == DT_F16) TM(f16);
   else return RGBNM_EINVAL;
 #undef TM
   LAUNCH_CHECK();

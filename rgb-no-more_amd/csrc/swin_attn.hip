@@ -20,7 +20,8 @@
 // (bf16; registers are free at one wave per SIMD, which the LDS tiles dictate).  Backward: the wave keeps its head's d(bias)
 // in 64 registers (accumulator layout) over all its windows; it leaves as one partial slice per wave, summed by the batched
 // deterministic reduction (no atomics); d(logit_scale) leaves as one partial per (window, head).
-// Templated on T in {float, bf16} (fp32 = exact 32x32x2 MFMA, the parity mode).
+// Templated on T in {float, bf16, f16} (fp32 = exact 32x32x2 MFMA, the parity mode).  fp16 shares the bf16 geometry (same 16-bit
+// lanes, same 32x32x16 MFMA shape): only the conversions differ -- every fp16 store forms the fp32 value and rounds it with from_f32.
 #include "common.h"
 #include <type_traits>
 #include "../../include/rgbnm.h"
@@ -57,7 +58,7 @@ template <typename T> struct WA {
   static constexpr int ROW_T = WT * RP * (int)sizeof(T);  // bytes of a row-major tile
   static constexpr int TR_T = HD * TP * (int)sizeof(T);   // bytes of a transposed tile
   static constexpr int SMALL = 5 * WT * 4;                // lse, D, |q|, |k|, mask id
-  // bf16 reads operands whose reduction axis is the token axis (V^T, K^T, Q^T, dO^T) out of the ROW-major tiles with
+  // 16-bit T reads operands whose reduction axis is the token axis (V^T, K^T, Q^T, dO^T) out of the ROW-major tiles with
   // ds_read_b64_tr_b16; fp32 has no transposing read and parks transposed copies
   static constexpr bool TRREAD = sizeof(T) == 2;
   static constexpr int FWD_WAVE = 2 * ROW_T + (TRREAD ? ROW_T : TR_T) + WT * 4;   // Qn, Kn, V (bf16) / V^T (fp32), mask id
@@ -78,22 +79,31 @@ template <typename T> struct WA {
 };
 
 template <typename T> __device__ __forceinline__ void unpack16(const u32x4& r, float (&f)[WA<T>::EP]) {
-  if constexpr (sizeof(T) == 2) {
+  if constexpr (std::is_same<T, bf16>::value) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       f[2 * i] = __builtin_bit_cast(float, r[i] << 16);
       f[2 * i + 1] = __builtin_bit_cast(float, r[i] & 0xffff0000u);
     }
+  } else if constexpr (std::is_same<T, f16>::value) {      // v_cvt_f32_f16 (exact)
+    const f16x8 hv = __builtin_bit_cast(f16x8, r);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[i] = (float)hv[i];
   } else {
     const f32x4 t = __builtin_bit_cast(f32x4, r);
     f[0] = t[0]; f[1] = t[1]; f[2] = t[2]; f[3] = t[3];
   }
 }
 template <typename T> __device__ __forceinline__ u32x4 pack16(const float (&f)[WA<T>::EP]) {
-  if constexpr (sizeof(T) == 2) {
+  if constexpr (std::is_same<T, bf16>::value) {
     bf16x8 v;
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = (bf16)f[i];
+    return __builtin_bit_cast(u32x4, v);
+  } else if constexpr (std::is_same<T, f16>::value) {
+    f16x8 v;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = from_f32<f16>(f[i]);
     return __builtin_bit_cast(u32x4, v);
   } else {
     return (u32x4){__builtin_bit_cast(unsigned, f[0]), __builtin_bit_cast(unsigned, f[1]), __builtin_bit_cast(unsigned, f[2]),
@@ -205,24 +215,26 @@ template <typename T> __device__ __forceinline__ Frag<T> tfrag(const T* img, int
   Frag<T> f;
   if constexpr (sizeof(T) == 2) {
     const T* p = img + d * TP + 32 * t + 16 * fi + 4 * g;
-    const bf16x4 lo = *reinterpret_cast<const bf16x4*>(p);
-    const bf16x4 hi = *reinterpret_cast<const bf16x4*>(p + 8);
-    f.v = (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    using V4 = typename Vec4<T>::type;       // bf16 or fp16
+    const V4 lo = *reinterpret_cast<const V4*>(p);
+    const V4 hi = *reinterpret_cast<const V4*>(p + 8);
+    f.v = (typename Vec8<T>::type){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   } else {
     f.v = *reinterpret_cast<const f32x4*>(img + d * TP + 32 * t + 8 * fi + 4 * g);
   }
   return f;
 }
-// bf16: the same fragment as tfrag(img, d = lane & 31, t, fi, g) read from the row-major tile [token][RP].  A 16-lane group
+// 16-bit T (bf16 / fp16: the read moves 16-bit lanes whatever they hold): the same fragment as tfrag(img, d = lane & 31, t, fi, g)
+// read from the row-major tile [token][RP].  A 16-lane group
 // (fixed g, G1) hands ds_read_b64_tr_b16 a 4-row x 16-column block -- lane (k, l3) points at row 4 g + k, columns
 // 16 G1 + 4 l3 .. +3 -- and gets back column 16 G1 + 4 k + l3 (= lane & 31) of rows 4 g .. 4 g + 3; the second read takes the
 // rows 8 further down (tfrag's `hi` half).
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned tr_base(const bf16* tile, int lane) {
+template <typename T> __device__ __forceinline__ unsigned tr_base(const T* tile, int lane) {
   const int g = lane >> 5, G1 = (lane >> 4) & 1, k = (lane >> 2) & 3, l3 = lane & 3;
   return (unsigned)(size_t)tile + (unsigned)((4 * g + k) * RP * 2 + (16 * G1 + 4 * l3) * 2);
 }
-__device__ __forceinline__ Frag<bf16> trfrag(unsigned a) {   // a = tr_base + byte offset of fragment (t, fi): (32 t + 16 fi) rows
+template <typename T> __device__ __forceinline__ Frag<T> trfrag(unsigned a) {   // a = tr_base + byte offset of fragment (t, fi): (32 t + 16 fi) rows
   u32x2 lo, hi;
   asm volatile(
       "ds_read_b64_tr_b16 %0, %2\n\t"
@@ -231,14 +243,14 @@ __device__ __forceinline__ Frag<bf16> trfrag(unsigned a) {   // a = tr_base + by
       : "=&v"(lo), "=&v"(hi)
       : "v"(a), "i"(8 * RP * 2)
       : "memory");
-  Frag<bf16> f;
-  f.v = __builtin_bit_cast(bf16x8, (u32x4){lo[0], lo[1], hi[0], hi[1]});
+  Frag<T> f;
+  f.v = __builtin_bit_cast(typename Vec8<T>::type, (u32x4){lo[0], lo[1], hi[0], hi[1]});
   return f;
 }
-// fragment (t, fi) of a token-reduced operand: transposing read of the row tile (bf16) or plain read of the transposed copy
+// fragment (t, fi) of a token-reduced operand: transposing read of the row tile (16-bit) or plain read of the transposed copy
 template <typename T>
 __device__ __forceinline__ Frag<T> tok_frag(unsigned trb, const T* timg, int l31, int t, int fi, int g) {
-  if constexpr (sizeof(T) == 2) return trfrag(trb + (unsigned)((32 * t + 16 * fi) * RP * 2));
+  if constexpr (sizeof(T) == 2) return trfrag<T>(trb + (unsigned)((32 * t + 16 * fi) * RP * 2));
   else return tfrag<T>(timg, l31, t, fi, g);
 }
 
@@ -289,7 +301,7 @@ __global__ __launch_bounds__(256) void win_attn_fwd_kernel(const T* __restrict__
   unsigned char* base = win_smem + A::BIAS + w * A::FWD_WAVE;
   T* Qn = reinterpret_cast<T*>(base);
   T* Kn = reinterpret_cast<T*>(base + A::ROW_T);
-  T* Vt = reinterpret_cast<T*>(base + 2 * A::ROW_T);          // bf16: V row-major [token][RP]; fp32: V^T [d][TP]
+  T* Vt = reinterpret_cast<T*>(base + 2 * A::ROW_T);          // 16-bit: V row-major [token][RP]; fp32: V^T [d][TP]
   int* Mid = reinterpret_cast<int*>(base + A::FWD_WAVE - WT * 4);
   unsigned trV = 0;
   if constexpr (A::TRREAD) trV = tr_base(Vt, lane);
@@ -476,7 +488,7 @@ __global__ __launch_bounds__(64 * WA<T>::BWD_WAVES) void win_attn_bwd_kernel(
   T* Knt = reinterpret_cast<T*>(base + 4 * A::ROW_T);          // transposed copies: fp32 only
   T* Qnt = reinterpret_cast<T*>(base + 4 * A::ROW_T + A::TR_T);
   T* Gt = reinterpret_cast<T*>(base + 4 * A::ROW_T + 2 * A::TR_T);
-  T* St = reinterpret_cast<T*>(base + A::BWD_WAVE - A::SMALL - A::ROW_T);      // bf16 only
+  T* St = reinterpret_cast<T*>(base + A::BWD_WAVE - A::SMALL - A::ROW_T);      // 16-bit only
   float* Ls = reinterpret_cast<float*>(base + A::BWD_WAVE - A::SMALL);
   unsigned trK = 0, trQ = 0, trG = 0;
   if constexpr (A::TRREAD) {
@@ -638,7 +650,7 @@ __global__ __launch_bounds__(64 * WA<T>::BWD_WAVES) void win_attn_bwd_kernel(
       }
       proj += __shfl_xor(proj, 32, 64);
       const float ir = Rq[q];
-      // bf16: rows go to the staging tile and leave as whole 64-byte token slices (16 lines per store instruction instead of 64)
+      // 16-bit: rows go to the staging tile and leave as whole 64-byte token slices (16 lines per store instruction instead of 64)
       T* drow = A::STAGE_DQ ? St + q * RP : dqkv + ((size_t)b * res * res + tokq) * 3 * C + h * HD;
 #pragma unroll
       for (int rq = 0; rq < 4; ++rq) {
@@ -860,16 +872,20 @@ int rgbnm_window_attention_fwd(int dtype, const void* qkv, const float* bias, co
   hipStream_t st = (hipStream_t)stream;
   if (dtype == DT_BF16) return launch_fwd<bf16>(qkv, bias, scale, out, lse, B, res, C, heads, shift, st);
   if (dtype == DT_F32) return launch_fwd<float>(qkv, bias, scale, out, lse, B, res, C, heads, shift, st);
+  if (dtype == DT_F16) return launch_fwd<f16>(qkv, bias, scale, out, lse, B, res, C, heads, shift, st);
   return RGBNM_EINVAL;
 }
 
 size_t rgbnm_window_attention_bwd_workspace(int B, int res, int heads) {
-  // one d(bias) slice per wave: the fp32 geometry (2 waves per workgroup, as many workgroups) bounds both dtypes
+  // one d(bias) slice per wave: the largest wave count of the three dtypes (fp16 has the bf16 geometry)
   const long long nwin = (long long)B * (res / WS) * (res / WS);
   // (head-major slots >= XCD-aware slots, so the head-major count bounds both mappings)
   const long long waves_bf = (long long)bwd_grid<bf16>(nwin, heads).bph * WA<bf16>::BWD_WAVES;
   const long long waves_f = (long long)bwd_grid<float>(nwin, heads).bph * WA<float>::BWD_WAVES;
-  return (size_t)(waves_bf > waves_f ? waves_bf : waves_f) * heads * WT * WT * sizeof(float);
+  const long long waves_h = (long long)bwd_grid<f16>(nwin, heads).bph * WA<f16>::BWD_WAVES;
+  long long waves = waves_bf > waves_f ? waves_bf : waves_f;
+  if (waves_h > waves) waves = waves_h;
+  return (size_t)waves * heads * WT * WT * sizeof(float);
 }
 
 int rgbnm_window_attention_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* bias,
@@ -886,6 +902,8 @@ int rgbnm_window_attention_bwd(int dtype, const void* qkv, const void* out, cons
     return launch_bwd<bf16>(qkv, out, dout, bias, scale, lse, dqkv, dbias, dscale_part, dscale, dpart, B, res, C, heads, shift, st);
   if (dtype == DT_F32)
     return launch_bwd<float>(qkv, out, dout, bias, scale, lse, dqkv, dbias, dscale_part, dscale, dpart, B, res, C, heads, shift, st);
+  if (dtype == DT_F16)
+    return launch_bwd<f16>(qkv, out, dout, bias, scale, lse, dqkv, dbias, dscale_part, dscale, dpart, B, res, C, heads, shift, st);
   return RGBNM_EINVAL;
 }
 

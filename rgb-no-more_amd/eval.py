@@ -12,7 +12,7 @@ import torch.distributed as dist
 @torch.no_grad()
 def evaluate_model(model, dataloader, criterion=None, device=None, amp_dtype=None, process_group=None, verbose=False):
     """-> (accuracy, loss).  dataloader yields ((Y, CbCr), labels) or (Y, CbCr, labels); tensors are moved to `device`
-    (default: the model's first parameter).  amp_dtype: the autocast dtype -- torch.bfloat16, or torch.float16 (the reference's hard-coded eval dtype, eval.py:36), which the HIP ViT computes in fp16 (SwinV2 refuses it) -- or None for fp32."""
+    (default: the model's first parameter).  amp_dtype: the autocast dtype -- torch.bfloat16, or torch.float16 (the reference's hard-coded eval dtype, eval.py:36), which the HIP ViT and SwinV2 compute in fp16 -- or None for fp32."""
     if device is None:
         device = next(model.parameters()).device
     device = torch.device(device)

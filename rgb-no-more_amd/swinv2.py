@@ -402,7 +402,7 @@ class _MlpFn(torch.autograd.Function):
             t1 = _tn_issue(du, x, True, False, 1)
         else:
             if br is not None and br.active:
-                br.pause()                     # row-paired (stage 1) or fp32: what is queued runs first
+                br.pause()                     # row-paired (stage 1), fp32 or fp16: what is queued runs first
             if grouped:
                 L.lib().rgbnm_gemm_tn_group_begin()
             try:
@@ -775,7 +775,7 @@ class SwinTransformerV2(FlatParamModule):
                 for n in (blk.norm1, blk.norm2):
                     nn.init.constant_(n.bias, 0)
                     nn.init.constant_(n.weight, 0)
-        self.compute_dtype = None                   # None: follow autocast; or torch.float32 / torch.bfloat16
+        self.compute_dtype = None                   # None: follow autocast; or torch.float32 / torch.bfloat16 / torch.float16
         # one weight-gradient bracket around the backward pass (_DwBracket).  Default off, like ViT.defer_grad_reduction: the
         # weight gradients then exist only when backward() has returned, which torch DDP's reducer hooks do not wait for
         self.group_dw_backward = False
@@ -826,14 +826,15 @@ class SwinTransformerV2(FlatParamModule):
         cdt = self.compute_dtype
         if cdt is None:
             cdt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else torch.float32
-        if cdt not in (torch.float32, torch.bfloat16):
-            raise NotImplementedError(f"compute dtype {cdt}")
+        # (fp16 runs the generic GEMMs: the bf16-tuned ones, the grouped dW bracket and the held reductions are bf16 only)
+        if cdt not in (torch.float32, torch.bfloat16, torch.float16):
+            raise NotImplementedError(f"compute dtype {cdt}: the MI355X path implements fp32, bf16 and fp16")
         dev = y.device
         if self._conv is None or self._conv[0].device != dev:
             self._conv = (self.patch_embed.conv_Y.to(dev).contiguous(), self.patch_embed.conv_C.to(dev).contiguous())
         y, cbcr = y.contiguous(), cbcr.contiguous()
-        if y.dtype not in (torch.float32, torch.bfloat16) or cbcr.dtype != y.dtype:
-            raise TypeError("Y and CbCr must be fp32 or bf16 and share a dtype")
+        if y.dtype not in (torch.float32, torch.bfloat16, torch.float16) or cbcr.dtype != y.dtype:
+            raise TypeError("Y and CbCr must be fp32, bf16 or fp16 and share a dtype")
         feat = torch.empty(B * res * res, 24, device=dev, dtype=cdt)
         L.check(L.lib().rgbnm_swin_embed(L.dt_of(y.dtype), L.dt_of(cdt), y.data_ptr(), cbcr.data_ptr(),
                                          self._conv[0].data_ptr(), self._conv[1].data_ptr(), feat.data_ptr(), B, Hb, Wb,

@@ -1,16 +1,20 @@
 #!/usr/bin/env python
-"""Time the training step of the ViT in its three compute configurations, in one process, alternating:
+"""Time the training step of the ViT (JPEG-Ti / JPEG-S) or of SwinV2-T in its three compute configurations, in one process,
+alternating:
 
   fp16          autocast(float16): fp16 activations on the generic kernels (the bf16-tuned kernels are bf16 only)
-  bf16_generic  bf16 with exactly the bf16-only kernels switched off (BF16_ONLY_OPTS): the kernel set fp16 runs
-  bf16          bf16 with every option at its default (what bench.py times)
+  bf16_generic  bf16 with exactly the bf16-only kernels switched off (BF16_ONLY_OPTS; SwinV2-T: also the backward-wide weight-
+                gradient bracket and the held reductions, group_dw_backward): the kernel set fp16 runs
+  bf16          bf16 with every option at its default (what bench.py times; SwinV2-T: group_dw_backward + hold_reductions on,
+                drop_path_rate 0.2, as bench.py --arch swinv2t)
 
 A step is what bench.py times, launched eagerly: augment (DCT-domain, fp32 output for fp16 and bf16_generic, bf16 for bf16),
 lazy mixup, forward, soft-target loss, backward, fused clip + AdamW + weight decay.  Per arch, every configuration runs WARMUP
 steps, then the timed steps in ROUNDS interleaved blocks (device events around each block, after a synchronise); every block
 starts from the initial weights (the step has no loss scaler, and the weights must stay where fp16 activations fit).  Also reports
-the max |logit - reference| at B = 256, depth 12 (golden g20, the reference ViT on detfill weights) per configuration.
-Prints one JSON line.  usage: python tools/fp16_step.py [--steps 300] [--warmup 50] [--rounds 6] [--arch vitti vits]
+the max |logit - reference| at B = 256 per configuration: JPEG-Ti depth 12 (golden g20) for the ViT archs, SwinV2-T (golden g21)
+for swinv2t -- the reference models on detfill weights.
+Prints one JSON line.  usage: python tools/fp16_step.py [--steps 300] [--warmup 50] [--rounds 6] [--arch vitti vits swinv2t]
 """
 import argparse
 import json
@@ -27,7 +31,7 @@ import rgb_no_more_amd as rg  # noqa: E402
 from rgb_no_more_amd import custom_transforms as CT, detfill, lib as L  # noqa: E402
 from bench import synth_coefficients  # noqa: E402
 
-ARCH = {"vitti": (192, 3), "vits": (384, 6)}
+ARCH = {"vitti": (192, 3), "vits": (384, 6), "swinv2t": (96, 3)}
 # every library option that selects a bf16-only kernel (rgbnm.h: the fp16 entries skip them)
 BF16_ONLY_OPTS = ("fwd_chain", "bwd_chain", "nt_kpipe", "nt_wres", "nt_small", "tn_pipe", "tn_wide", "mlp_fuse", "mlp_bwd",
                   "attn_v2", "ln_fuse")
@@ -38,6 +42,30 @@ def set_opts(defaults, off):
     lib = L.lib()
     for k, v in defaults.items():
         lib.rgbnm_set_option(k.encode(), 0 if (off and k in BF16_ONLY_OPTS) else v)
+
+
+def swin_model(dev, drop_path_rate):
+    return rg.SwinTransformerV2(img_size=256, patch_size=4, embed_dim=96, depths=[2, 2, 6, 2], num_heads=[3, 6, 12, 24],
+                                window_size=8, drop_path_rate=drop_path_rate, device=dev, pixel_space="dct")
+
+
+def swin_logit_error(cfg, defaults):
+    """max |logit - reference| of SwinV2-T, B = 256 (tests/golden/g21_b256.npz; the fill of bench.py's parity check)."""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "g21_b256.npz"))
+    m = swin_model("cuda", 0.0)
+    names = [str(n) for n in g["swt_b256_names"]]
+    shapes = {n: tuple(p.shape) for n, p in m.named_parameters()}
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in detfill.fill_swin_params({n: shapes[n] for n in names}).items()},
+                      strict=False)
+    y = torch.from_numpy(detfill.normalish((256, 1, 32, 32, 8, 8), 171)).cuda()
+    c = torch.from_numpy(detfill.normalish((256, 2, 16, 16, 8, 8), 172)).cuda()
+    set_opts(defaults, cfg == "bf16_generic")
+    m.train()
+    with torch.autocast("cuda", dtype=torch.float16 if cfg == "fp16" else torch.bfloat16):
+        out = m(y, c)
+    torch.cuda.synchronize()
+    set_opts(defaults, False)
+    return float(np.abs(out.detach().float().cpu().numpy() - g["swt_b256_logits"]).max())
 
 
 def logit_error(cfg, defaults):
@@ -76,8 +104,12 @@ def main():
     for arch in a.arch:
         emb, heads = ARCH[arch]
         torch.manual_seed(0)
-        model = rg.ViT(3, 16, emb, depth=12, n_classes=1000, drop_p=0.0, device=dev, num_heads=heads, head_size=64,
-                       pixel_space="DCT", ver=1, use_subblock=True)
+        swin = arch == "swinv2t"
+        if swin:
+            model = swin_model(dev, 0.2)
+        else:
+            model = rg.ViT(3, 16, emb, depth=12, n_classes=1000, drop_p=0.0, device=dev, num_heads=heads, head_size=64,
+                           pixel_space="DCT", ver=1, use_subblock=True)
         model.train()
         opt = rg.custom_optims.FusedClipAdamWWD(model, lr=1e-3, eps=1e-8, weight_decay=1e-4, max_norm=1.0)
         Yq, Cq, quant = synth_coefficients(B, dev, 1234)
@@ -86,11 +118,16 @@ def main():
         for cfg in CONFIGS:
             adt = torch.bfloat16 if cfg == "bf16" else torch.float32          # augment output (no fp16 augment output)
             cdt = torch.float16 if cfg == "fp16" else torch.bfloat16
-            aug = CT.TrainTransform_DCT(size=28, out_dtype=adt)
+            aug = CT.TrainTransform_DCT(size=32 if swin else 28, out_dtype=adt)
             mix = rg.cls_transforms.RandomMixup_DCT(1000, alpha=0.2)
             mix.out_dtype = adt
             mix.lazy, mix.lazy_target = True, True
             legs[cfg] = (aug, CT.FastParamSampler(aug, seed=1234), mix, cdt)
+
+        def configure(cfg):
+            set_opts(defaults, cfg == "bf16_generic")
+            if swin:                            # the backward-wide bracket and the held reductions: bf16 default only
+                model.group_dw_backward = model.hold_reductions = cfg == "bf16"
 
         def step(cfg):
             aug, sampler, mix, cdt = legs[cfg]
@@ -107,7 +144,7 @@ def main():
 
         state = {k: v.detach().clone() for k, v in model.state_dict().items()}
         for cfg in CONFIGS:
-            set_opts(defaults, cfg == "bf16_generic")
+            configure(cfg)
             model.load_state_dict(state)
             for _ in range(a.warmup):
                 step(cfg)
@@ -117,7 +154,7 @@ def main():
         per = max(1, a.steps // a.rounds)
         for r in range(a.rounds):
             for cfg in (CONFIGS if r % 2 == 0 else CONFIGS[::-1]):
-                set_opts(defaults, cfg == "bf16_generic")
+                configure(cfg)
                 model.load_state_dict(state)    # every block from the same weights (no loss scaler here: keep fp16 in range)
                 torch.cuda.synchronize()
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -139,7 +176,10 @@ def main():
         print(f"{arch}: " + ", ".join(f"{k} {v['step_ms_median']:.3f} ms" for k, v in out.items() if isinstance(v, dict)), file=sys.stderr)
         del model, opt
         torch.cuda.empty_cache()
-    res["max_abs_dlogit_ti_b256"] = {cfg: logit_error(cfg, defaults) for cfg in CONFIGS}
+    if any(x != "swinv2t" for x in a.arch):
+        res["max_abs_dlogit_ti_b256"] = {cfg: logit_error(cfg, defaults) for cfg in CONFIGS}
+    if "swinv2t" in a.arch:
+        res["max_abs_dlogit_swinv2t_b256"] = {cfg: swin_logit_error(cfg, defaults) for cfg in CONFIGS}
     print(json.dumps(res))
 
 
