@@ -500,8 +500,10 @@ def test_attention_bf16_both_generations(option, v2):
 
 @pytest.mark.parametrize("M,N", [(4096, 576), (64 * 67, 768), (6400, 192), (64 * 263, 96), (50176, 768)])
 def test_gemm_nt_bf16_weight_resident_path(option, M, N):
-    """K = 192, M % 64 == 0, N % 96 == 0 shapes take the persistent weight-resident kernel (nt_wres=1): same bits as
-    the tile-per-workgroup kernel (identical accumulation and rounding order), and both agree with the fp32 product."""
+    """K = 192, N % 192 == 0, M % 32 == 0, M >= 4096 shapes take the persistent weight-resident kernel (nt_wres=1,
+    gemm_nt_wres.hip:283): same bits as the tile-per-workgroup kernel (identical accumulation and rounding order), and both
+    agree with the fp32 product.  N = 96 is not eligible: that case compares the tile-per-workgroup kernel with itself (a
+    generic-kernel case).  tests/test_kernel_edges.py asserts which kernel each shape reaches."""
     dt, K = torch.bfloat16, 192
     A = dev(detfill.normalish((M, K), 31), dt)
     W = dev(detfill.uniform((N, K), 32, -0.1, 0.1), dt)
