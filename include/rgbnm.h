@@ -46,6 +46,11 @@ extern "C" {
 #define RGBNM_EPI_DGELU 4  /* C = (A.W^T) * R, R = the C2 (gelu') saved by RGBNM_EPI_GELU         */
 #define RGBNM_EPI_TANH 5   /* C = tanh(A.W^T + bias)                    (ClassificationHead :553-554)  */
 #define RGBNM_EPI_DTANH 6  /* C = (A.W^T) * (1 - R^2)                                             */
+/* dropout epilogues (nn.Dropout after the attention projection, after GELU and after fc2, plainvit.py:485-529): rgbnm_gemm_nt_drop
+ * only.  keep / scale as in the dropout mask contract below; the mask is applied to the fp32 value EPI_RES adds to R and to the
+ * gelu / gelu' values EPI_GELU stores, so p = 0 gives EPI_RES's / EPI_GELU's bits. */
+#define RGBNM_EPI_RES_DROP 7   /* C = R + keep scale (A.W^T + bias)                                         */
+#define RGBNM_EPI_GELU_DROP 8  /* u = A.W^T + bias ; C = keep scale gelu_erf(u), C2 = keep scale gelu_erf'(u) */
 
 int rgbnm_abi_version(void);
 /* Runtime switches: every one selects between parity-tested kernels (tests/ run both sides); defaults in the middle column.
@@ -102,6 +107,24 @@ const char* rgbnm_strerror(int code);
 int rgbnm_gemm_nt(int dtype, int epi, const void* A, int lda, const void* W, int ldw, void* C, int ldc,
                   const float* bias, const void* R, int ldr, void* C2, int ldc2, const float* pos, int pos_period,
                   int M, int N, int K, int c_f32, void* stream);
+
+/* Dropout mask contract (every kernel that draws a mask uses csrc/philox.h):
+ *   element (row, col) of dropout site `site` (0 after the attention projection, 1 after GELU, 2 after fc2) of encoder block `block`
+ *   is KEPT when  word >= thr,  word = word (col & 3) of Philox4x32-10 with
+ *     counter = (col >> 2, row, block * 4 + site, 0),  key = (low 32 bits, high 32 bits) of the 64-bit seed at `seed`
+ *     (device memory, read by the kernels: a captured graph replays with the seed the step drew),  thr = llround(p 2^32);
+ *   kept elements are multiplied by the fp32 scale = 1.0f / (1.0f - p), dropped ones become 0 (nn.Dropout's inverted scaling;
+ *   the bits are this library's, not torch's).  row = the token row in [0, B N), col = the feature.  p in [0, 1); p = 0 keeps all.
+ * One counter covers 4 consecutive columns: the staged epilogue and rgbnm_dropout_apply take 8 columns per thread (two counters);
+ * the direct (fp32) epilogue holds one column per lane and evaluates a counter per element, using one of its four words. */
+/* rgbnm_gemm_nt with epi RGBNM_EPI_RES_DROP or RGBNM_EPI_GELU_DROP (pos must be NULL) on the generic gemm_nt kernel (staged or
+ * direct epilogue, never the bf16-tuned variants). */
+int rgbnm_gemm_nt_drop(int dtype, int epi, const void* A, int lda, const void* W, int ldw, void* C, int ldc,
+                       const float* bias, const void* R, int ldr, void* C2, int ldc2, const float* pos, int pos_period,
+                       int M, int N, int K, int c_f32, const void* seed, float p, int site, int block, void* stream);
+/* y[M,N] = keep scale x (in place allowed: y == x, ldy == ldx). */
+int rgbnm_dropout_apply(int dtype, const void* seed, float p, int site, int block, const void* x, int ldx, void* y, int ldy,
+                        int M, int N, void* stream);
 
 /* dW[No,Ki] (fp32) = dY[M,No]^T . X[M,Ki]; db[No] = column sums of dY (db may be NULL).
  * perm_heads > 0: rows of dW/db are written in the reference's interleaved '(h d qkv)' order
@@ -386,6 +409,25 @@ int rgbnm_vit_block_fwd_chain(const rgbnm_vit_cfg* cfg, const rgbnm_block_params
 int rgbnm_vit_block_bwd(const rgbnm_vit_cfg* cfg, const rgbnm_block_params* p, const rgbnm_block_acts* a,
                         const rgbnm_block_grads* g, const rgbnm_block_scratch* s, const void* dy, void* dx,
                         void* stream);
+
+/* Encoder block with dropout p > 0 (training; reference: eb_drop1, the FeedForwardBlock's nn.Dropout and eb_drop2 of
+ * plainvit.py:485-529, all p = drop_p).  The forward runs LN1, qkv and attention as rgbnm_vit_block_fwd, then proj with
+ * RGBNM_EPI_RES_DROP (site 0), LN2, fc1 with RGBNM_EPI_GELU_DROP (site 1: a->gl and a->u hold the masked gelu / gelu') and fc2 with
+ * RGBNM_EPI_RES_DROP (site 2); no LayerNorm chaining, no fused MLP.  The backward regenerates the masks from the same seed:
+ * dy_m = mask2(dy) feeds dW2 / db2 and d(gl), dxmid_m = mask0(d x_mid) feeds dWproj / dbproj and d(attn); the residual paths keep
+ * the unmasked gradients.  dy_m / dxmid_m: caller-owned [M,E] buffers of the compute dtype (backward only), alive until the call
+ * returns.  No mask is stored. */
+typedef struct rgbnm_dropout {
+  const void* seed;   /* device pointer to the step's 64-bit seed */
+  float p;            /* [0, 1) */
+  int block;          /* encoder block index (counter word 2 = block * 4 + site) */
+  void *dy_m, *dxmid_m;
+} rgbnm_dropout;
+int rgbnm_vit_block_fwd_drop(const rgbnm_vit_cfg* cfg, const rgbnm_block_params* p, const rgbnm_block_acts* a,
+                             const rgbnm_dropout* d, void* stream);
+int rgbnm_vit_block_bwd_drop(const rgbnm_vit_cfg* cfg, const rgbnm_block_params* p, const rgbnm_block_acts* a,
+                             const rgbnm_block_grads* g, const rgbnm_block_scratch* s, const rgbnm_dropout* d, const void* dy,
+                             void* dx, void* stream);
 
 /* ---- The whole encoder forward as ONE launch, one workgroup per image (csrc/vit_chain.hip) --------------------------------
  * Reference: the `depth` TransformerEncoderBlocks of models/plainvit.py:493-529 applied in sequence (:601-611).  bf16, E = 192,

@@ -17,10 +17,14 @@
 #include <vector>
 #include "../../include/rgbnm.h"
 #include "internal.h"
+#include "philox.h"
 
 namespace {
 
-enum { EPI_NONE = 0, EPI_RES = 1, EPI_GELU = 2, EPI_POS = 3, EPI_DGELU = 4, EPI_TANH = 5, EPI_DTANH = 6 };
+// 7 / 8: the dropout epilogues, rgbnm_gemm_nt_drop only (philox.h): the mask multiplies the fp32 value EPI_RES adds to R / EPI_GELU
+// feeds to gelu and gelu' (C2 = keep scale gelu'(u): the backward's EPI_DGELU then needs no mask of its own)
+enum { EPI_NONE = 0, EPI_RES = 1, EPI_GELU = 2, EPI_POS = 3, EPI_DGELU = 4, EPI_TANH = 5, EPI_DTANH = 6, EPI_RES_DROP = 7,
+       EPI_GELU_DROP = 8 };
 
 struct GemmNT {
   const void* A; const void* W; void* C; const float* bias; const void* R; void* C2; const float* pos;
@@ -28,6 +32,7 @@ struct GemmNT {
   int M, N, K;
   int c_f32;
   int mtiles, ntiles;
+  DropArgs d;      // EPI_RES_DROP / EPI_GELU_DROP only
 };
 
 constexpr int BM = 128;
@@ -39,6 +44,7 @@ constexpr int PITCH_B = 144;  // bytes per LDS tile row
 // residual / GELU / dGELU operands are also read as 16-byte vectors.
 template <typename T, int NB, int EPI, bool STAGED>
 __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNT p) {
+  constexpr bool DROP = EPI == EPI_RES_DROP || EPI == EPI_GELU_DROP;
   constexpr int BN = 64 * NB;
   constexpr int CP = BN + 4;                    // staging pitch (elements)
   constexpr int TILE_BYTES = (BM + BN) * PITCH_B;
@@ -137,6 +143,12 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNT p) {
     }
   }
 
+  uint32_t kd0 = 0, kd1 = 0;                      // Philox key = the seed's two halves
+  if constexpr (DROP) {
+    const unsigned long long sd = *p.d.seed;
+    kd0 = (uint32_t)sd;
+    kd1 = (uint32_t)(sd >> 32);
+  }
   if constexpr (STAGED) {
     // ---- pass 1: registers -> LDS (T(acc + bias [+ pos])) ; lane = token, quad = 4 features ----
     T* Cs = reinterpret_cast<T*>(smem);
@@ -182,7 +194,12 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNT p) {
       const V4 c0 = *reinterpret_cast<const V4*>(Cs + row * CP + vec * 8);
       const V4 c1 = *reinterpret_cast<const V4*>(Cs + row * CP + vec * 8 + 4);
       V8 cv = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
-      if (EPI == EPI_GELU) {
+      uint32_t dw[8];                             // mask words of columns gn .. gn + 7 (gn % 8 == 0: two Philox counters)
+      if constexpr (DROP) {
+        const uint4 w0 = drop_words(kd0, kd1, p.d.stream, gm, gn >> 2), w1 = drop_words(kd0, kd1, p.d.stream, gm, (gn >> 2) + 1);
+        dw[0] = w0.x; dw[1] = w0.y; dw[2] = w0.z; dw[3] = w0.w; dw[4] = w1.x; dw[5] = w1.y; dw[6] = w1.z; dw[7] = w1.w;
+      }
+      if (EPI == EPI_GELU || EPI == EPI_GELU_DROP) {
         // one erf/exp evaluation yields gelu(u) (-> C) and gelu'(u) (-> C2, consumed by EPI_DGELU in backward)
         V8 dv;
 #pragma unroll
@@ -190,6 +207,12 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNT p) {
           const f32x2 u = {(float)cv[e], (float)cv[e + 1]};
           f32x2 gv, dgv;
           gelu_pair_fast(u, gv, dgv);
+          if constexpr (DROP) {
+            gv[0] = drop_one(p.d, dw[e], gv[0]);
+            gv[1] = drop_one(p.d, dw[e + 1], gv[1]);
+            dgv[0] = drop_one(p.d, dw[e], dgv[0]);
+            dgv[1] = drop_one(p.d, dw[e + 1], dgv[1]);
+          }
           dv[e] = from_f32<T>(dgv[0]);
           dv[e + 1] = from_f32<T>(dgv[1]);
           cv[e] = from_f32<T>(gv[0]);
@@ -197,13 +220,14 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNT p) {
         }
         *reinterpret_cast<V8*>(C2 + (size_t)gm * p.ldc2 + gn) = dv;
       }
-      if (EPI != EPI_NONE && EPI != EPI_POS && EPI != EPI_GELU) {
+      if (EPI != EPI_NONE && EPI != EPI_POS && EPI != EPI_GELU && EPI != EPI_GELU_DROP) {
         V8 rv;
-        if (EPI == EPI_RES || EPI == EPI_DGELU || EPI == EPI_DTANH)
+        if (EPI == EPI_RES || EPI == EPI_DGELU || EPI == EPI_DTANH || EPI == EPI_RES_DROP)
           rv = *reinterpret_cast<const V8*>(R + (size_t)gm * p.ldr + gn);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           float v = (float)cv[e];
+          if constexpr (EPI == EPI_RES_DROP) v = drop_one(p.d, dw[e], v) + (float)rv[e];
           if (EPI == EPI_RES) v += (float)rv[e];
           if (EPI == EPI_DGELU) v *= (float)rv[e];
           if (EPI == EPI_TANH) v = tanhf(v);
@@ -231,16 +255,33 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNT p) {
     const float bv = p.bias ? p.bias[col] : 0.f;
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
+      uint32_t keep = 0;                          // bit r: row acc_row(r) of this column is kept (one Philox counter per element
+      if constexpr (DROP) {                       // here: a rolled loop, so that the fragment loop below stays unrolled)
+#pragma nounroll
+        for (int r = 0; r < 16; ++r) {
+          const uint4 ws = drop_words(kd0, kd1, p.d.stream, m0 + wm * 64 + a * 32 + acc_row(r, lane), col >> 2);
+          const int q = col & 3;
+          const uint32_t w = q == 0 ? ws.x : (q == 1 ? ws.y : (q == 2 ? ws.z : ws.w));
+          keep |= (uint32_t)(w >= p.d.thr) << r;
+        }
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = m0 + wm * 64 + a * 32 + acc_row(r, lane);
         if (row >= p.M) continue;
         float v = acc[a][b][r] + bv;
+        const uint32_t w = ((keep >> r) & 1) ? 0xFFFFFFFFu : 0u;    // (a word drop_one keeps / drops for any threshold < 2^32)
         if (EPI == EPI_RES) v += to_f32(R[(size_t)row * p.ldr + col]);
+        if constexpr (EPI == EPI_RES_DROP) v = drop_one(p.d, w, v) + to_f32(R[(size_t)row * p.ldr + col]);
         if (EPI == EPI_GELU) {
           const float u = to_f32(from_f32<T>(v));   // pre-activation at the activation dtype's precision
           C2[(size_t)row * p.ldc2 + col] = from_f32<T>(dgelu_f(u));
           v = gelu_f(u);
+        }
+        if constexpr (EPI == EPI_GELU_DROP) {
+          const float u = to_f32(from_f32<T>(v));
+          C2[(size_t)row * p.ldc2 + col] = from_f32<T>(drop_one(p.d, w, dgelu_f(u)));
+          v = drop_one(p.d, w, gelu_f(u));
         }
         if (EPI == EPI_POS) v += p.pos[(size_t)(row % p.pos_period) * p.N + col];
         if (EPI == EPI_DGELU) v *= to_f32(R[(size_t)row * p.ldr + col]);
@@ -275,6 +316,12 @@ int launch_nt_epi(const GemmNT& p, int epi, hipStream_t st) {
   return RGBNM_OK;
 }
 
+// the staged (16-byte row) epilogue of a 16-bit gemm_nt_kernel: every output row a whole number of 16-byte vectors
+bool nt_staged_ok(const GemmNT& p) {
+  return !p.c_f32 && (p.N % 8 == 0) && (p.ldc % 8 == 0) && (!p.R || p.ldr % 8 == 0) && (!p.C2 || p.ldc2 % 8 == 0) &&
+         rgbnm_get_option("nt_staged");
+}
+
 template <typename T, int NB>
 int launch_nt_sel(const GemmNT& p, int epi, hipStream_t st) {
   if constexpr (sizeof(T) == 2) {
@@ -287,8 +334,7 @@ int launch_nt_sel(const GemmNT& p, int epi, hipStream_t st) {
                                            p.K, st);
       if (rc != 1) return rc;
     }
-    const bool ok = !p.c_f32 && (p.N % 8 == 0) && (p.ldc % 8 == 0) && (!p.R || p.ldr % 8 == 0) &&
-                    (!p.C2 || p.ldc2 % 8 == 0) && rgbnm_get_option("nt_staged");
+    const bool ok = nt_staged_ok(p);
     if (fast && ok && !p.pos && rgbnm_get_option("nt_kpipe")) {
       // N % 192 == 0 with a long reduction (K >= 256): 224-row panels x 192-column tiles, k-tiles through an LDS-DMA ring
       // (gemm_nt_kpipe.hip); N = 192: one row panel per CU
@@ -319,6 +365,36 @@ int launch_nt(GemmNT p, int epi, hipStream_t st) {
   }
   p.ntiles = cdiv(p.N, 128);
   return launch_nt_sel<T, 2>(p, epi, st);
+}
+
+// dropout epilogues: always the generic kernel (staged for 16-bit types when nt_staged_ok, else direct)
+template <typename T, int NB, bool STAGED>
+int launch_nt_drop_epi(const GemmNT& p, int epi, hipStream_t st) {
+  const int grid = ((p.mtiles + 7) / 8) * 8 * p.ntiles;
+  const double esz = sizeof(T), mn = (double)p.M * p.N;
+  const int slot = rgbnm_trace_begin(TR_NT, 2.0 * mn * p.K,
+                                     ((double)p.M * p.K + (double)p.N * p.K) * esz + mn * (p.c_f32 ? 4.0 : esz) + mn * esz, st);
+  if (epi == EPI_RES_DROP)
+    hipLaunchKernelGGL((gemm_nt_kernel<T, NB, EPI_RES_DROP, STAGED>), dim3(grid), dim3(256), 0, st, p);
+  else
+    hipLaunchKernelGGL((gemm_nt_kernel<T, NB, EPI_GELU_DROP, STAGED>), dim3(grid), dim3(256), 0, st, p);
+  rgbnm_trace_end(slot, st);
+  LAUNCH_CHECK();
+  return RGBNM_OK;
+}
+
+template <typename T>
+int launch_nt_drop(GemmNT p, int epi, hipStream_t st) {
+  if (p.M <= 0 || p.N <= 0 || p.K <= 0) return RGBNM_EINVAL;
+  const int epv = 16 / (int)sizeof(T);
+  if (p.K % epv || p.lda % epv || p.ldw % epv) return RGBNM_EINVAL;
+  p.mtiles = cdiv(p.M, BM);
+  const bool nb3 = p.N % 192 == 0;
+  p.ntiles = nb3 ? p.N / 192 : cdiv(p.N, 128);
+  if constexpr (sizeof(T) == 2) {
+    if (nt_staged_ok(p)) return nb3 ? launch_nt_drop_epi<T, 3, true>(p, epi, st) : launch_nt_drop_epi<T, 2, true>(p, epi, st);
+  }
+  return nb3 ? launch_nt_drop_epi<T, 3, false>(p, epi, st) : launch_nt_drop_epi<T, 2, false>(p, epi, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -856,6 +932,7 @@ int rgbnm_gemm_nt(int dtype, int epi, const void* A, int lda, const void* W, int
   p.A = A; p.W = W; p.C = C; p.bias = bias; p.R = R; p.C2 = C2; p.pos = pos;
   p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr; p.ldc2 = ldc2; p.pos_period = pos_period > 0 ? pos_period : 1;
   p.M = M; p.N = N; p.K = K; p.c_f32 = c_f32; p.mtiles = p.ntiles = 0;
+  p.d = DropArgs{};
   if (!A || !W || !C) return RGBNM_EINVAL;
   if ((epi == EPI_RES || epi == EPI_DGELU || epi == EPI_DTANH) && !R) return RGBNM_EINVAL;
   if (epi == EPI_GELU && !C2) return RGBNM_EINVAL;
@@ -864,6 +941,28 @@ int rgbnm_gemm_nt(int dtype, int epi, const void* A, int lda, const void* W, int
   if (dtype == DT_BF16) return launch_nt<bf16>(p, epi, st);
   if (dtype == DT_F32) return launch_nt<float>(p, epi, st);
   if (dtype == DT_F16) return launch_nt<f16>(p, epi, st);
+  return RGBNM_EINVAL;
+}
+
+int rgbnm_gemm_nt_drop(int dtype, int epi, const void* A, int lda, const void* W, int ldw, void* C, int ldc,
+                       const float* bias, const void* R, int ldr, void* C2, int ldc2, const float* pos, int pos_period,
+                       int M, int N, int K, int c_f32, const void* seed, float p_drop, int site, int block, void* stream) {
+  GemmNT p;
+  p.A = A; p.W = W; p.C = C; p.bias = bias; p.R = R; p.C2 = C2; p.pos = pos;
+  p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr; p.ldc2 = ldc2; p.pos_period = pos_period > 0 ? pos_period : 1;
+  p.M = M; p.N = N; p.K = K; p.c_f32 = c_f32; p.mtiles = p.ntiles = 0;
+  DropArgs& d = p.d;
+  if (!A || !W || !C || !seed || pos || site < 0 || site > 3 || block < 0 || !drop_host_args(p_drop, d.thr, d.scale))
+    return RGBNM_EINVAL;
+  if (epi == EPI_RES_DROP) { if (!R) return RGBNM_EINVAL; p.C2 = nullptr; }
+  else if (epi == EPI_GELU_DROP) { if (!C2) return RGBNM_EINVAL; p.R = nullptr; }
+  else return RGBNM_EINVAL;
+  d.seed = reinterpret_cast<const unsigned long long*>(seed);
+  d.stream = (uint32_t)block * 4u + (uint32_t)site;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == DT_BF16) return launch_nt_drop<bf16>(p, epi, st);
+  if (dtype == DT_F32) return launch_nt_drop<float>(p, epi, st);
+  if (dtype == DT_F16) return launch_nt_drop<f16>(p, epi, st);
   return RGBNM_EINVAL;
 }
 

@@ -232,9 +232,31 @@ int rgbnm_vit_block_fwd(const rgbnm_vit_cfg* c, const rgbnm_block_params* p, con
   return rgbnm_vit_block_fwd_chain(c, p, a, 0, nullptr, nullptr, st);
 }
 
-int rgbnm_vit_block_bwd(const rgbnm_vit_cfg* c, const rgbnm_block_params* p, const rgbnm_block_acts* a,
-                        const rgbnm_block_grads* g, const rgbnm_block_scratch* s, const void* dy, void* dx, void* st) {
+int rgbnm_vit_block_fwd_drop(const rgbnm_vit_cfg* c, const rgbnm_block_params* p, const rgbnm_block_acts* a, const rgbnm_dropout* d,
+                             void* st) {
+  if (!c || !p || !a || !d) return RGBNM_EINVAL;
+  const int dt = c->dtype, M = c->B * c->N, E = c->E, I = c->heads * 64;
+  TRY(rgbnm_layernorm_fwd(dt, a->x_in, p->ln1_g, p->ln1_b, a->xn1, a->mean1, a->rstd1, M, E, c->ln_eps, st));
+  TRY(rgbnm_gemm_nt(dt, RGBNM_EPI_NONE, a->xn1, E, p->wqkv, E, a->qkv, 3 * I, p->bqkv_perm, 0, 0, 0, 0, 0, 0, M,
+                    3 * I, E, 0, st));
+  TRY(rgbnm_attention_fwd(dt, a->qkv, a->attn, a->lse, c->B, c->N, c->heads, c->attn_scale, st));
+  // x_mid = x_in + drop0(proj(attn)) ; xn2 = LN2(x_mid)
+  TRY(rgbnm_gemm_nt_drop(dt, RGBNM_EPI_RES_DROP, a->attn, I, p->wproj, I, a->x_mid, E, p->bproj, a->x_in, E, 0, 0, 0, 0, M, E, I,
+                         0, d->seed, d->p, 0, d->block, st));
+  TRY(rgbnm_layernorm_fwd(dt, a->x_mid, p->ln2_g, p->ln2_b, a->xn2, a->mean2, a->rstd2, M, E, c->ln_eps, st));
+  // gl = drop1(gelu(fc1(xn2))), u = drop1(gelu'(.)) ; x_out = x_mid + drop2(fc2(gl))
+  TRY(rgbnm_gemm_nt_drop(dt, RGBNM_EPI_GELU_DROP, a->xn2, E, p->w1, E, a->gl, 4 * E, p->b1, 0, 0, a->u, 4 * E, 0, 0, M, 4 * E, E,
+                         0, d->seed, d->p, 1, d->block, st));
+  TRY(rgbnm_gemm_nt_drop(dt, RGBNM_EPI_RES_DROP, a->gl, 4 * E, p->w2, 4 * E, a->x_out, E, p->b2, a->x_mid, E, 0, 0, 0, 0, M, E,
+                         4 * E, 0, d->seed, d->p, 2, d->block, st));
+  return RGBNM_OK;
+}
+
+// d == NULL: rgbnm_vit_block_bwd; else the dropout backward (rgbnm_vit_block_bwd_drop)
+static int block_bwd(const rgbnm_vit_cfg* c, const rgbnm_block_params* p, const rgbnm_block_acts* a, const rgbnm_block_grads* g,
+                     const rgbnm_block_scratch* s, const rgbnm_dropout* d, const void* dy, void* dx, void* st) {
   if (!c || !p || !a || !g || !s || !dy || !dx) return RGBNM_EINVAL;
+  if (d && (!d->dy_m || !d->dxmid_m || d->dy_m == d->dxmid_m)) return RGBNM_EINVAL;
   const int dt = c->dtype, M = c->B * c->N, E = c->E, I = c->heads * 64;
   size_t off[7];
   if (s->ws_bytes < block_ws_offsets(M, E, I, off)) return RGBNM_EWORKSPACE;
@@ -254,12 +276,19 @@ int rgbnm_vit_block_bwd(const rgbnm_vit_cfg* c, const rgbnm_block_params* p, con
   const bool wide4 = rgbnm_get_option("tn_wide") && E % 384 == 0 && I % 384 == 0 && M % 64 == 0;
   if (group == 2 && E > 192 && !wide4) group = 1;
   if (group) { rgbnm_tn_defer_begin(); tn_open = true; }
-  TRY(rgbnm_gemm_tn(dt, dy, E, a->gl, 4 * E, g->dw2, g->db2, M, E, 4 * E, 0, 0, WS(0), st));
-  // du = (dy . W2) * gelu'(u) and dx_mid = dy + LN2'(du . W1) in ONE launch when eligible (mlp_fused.hip, option mlp_bwd)
-  const bool mlp_bwd_fused = fused_mlp_bwd(dt, dy, p->w2_t, p->w1_t, a->u, s->du, a->x_mid, p->ln2_g, a->mean2, a->rstd2,
-                                           s->dx_mid, g->dln2_g, g->dln2_b, M, E, WS(4), (hipStream_t)st);
+  // dropout: fc2's output gradient is drop2(dy) (dy_m); the residual keeps dy.  (dy_m lives until the queued dW GEMMs have run.)
+  const void* dyg = dy;
+  if (d) {
+    TRY(rgbnm_dropout_apply(dt, d->seed, d->p, 2, d->block, dy, E, d->dy_m, E, M, E, st));
+    dyg = d->dy_m;
+  }
+  TRY(rgbnm_gemm_tn(dt, dyg, E, a->gl, 4 * E, g->dw2, g->db2, M, E, 4 * E, 0, 0, WS(0), st));
+  // du = (dy . W2) * gelu'(u) and dx_mid = dy + LN2'(du . W1) in ONE launch when eligible (mlp_fused.hip, option mlp_bwd; not with
+  // dropout: it reads one dy as the GEMM operand and the residual)
+  const bool mlp_bwd_fused = !d && fused_mlp_bwd(dt, dy, p->w2_t, p->w1_t, a->u, s->du, a->x_mid, p->ln2_g, a->mean2, a->rstd2,
+                                                 s->dx_mid, g->dln2_g, g->dln2_b, M, E, WS(4), (hipStream_t)st);
   if (!mlp_bwd_fused)
-    TRY(rgbnm_gemm_nt(dt, RGBNM_EPI_DGELU, dy, E, p->w2_t, E, s->du, 4 * E, 0, a->u, 4 * E, 0, 0, 0, 0, M, 4 * E, E, 0,
+    TRY(rgbnm_gemm_nt(dt, RGBNM_EPI_DGELU, dyg, E, p->w2_t, E, s->du, 4 * E, 0, a->u, 4 * E, 0, 0, 0, 0, M, 4 * E, E, 0,
                       st));
   TRY(rgbnm_gemm_tn(dt, s->du, 4 * E, a->xn2, E, g->dw1, g->db1, M, 4 * E, E, 0, 0, WS(1), st));
   if (group == 1) { tn_open = false; TRY(rgbnm_tn_defer_flush((hipStream_t)st)); }
@@ -273,9 +302,15 @@ int rgbnm_vit_block_bwd(const rgbnm_vit_cfg* c, const rgbnm_block_params* p, con
                             M, E, 0, WS(4), st));
   }
   // ---- attention branch: x_mid = x_in + proj(attn(qkv(LN1(x_in)))) -------------------------------
+  // dropout: the projection's output gradient is drop0(d x_mid) (dxmid_m); LN1's backward keeps d x_mid as its residual
+  const void* dxmg = s->dx_mid;
+  if (d) {
+    TRY(rgbnm_dropout_apply(dt, d->seed, d->p, 0, d->block, s->dx_mid, E, d->dxmid_m, E, M, E, st));
+    dxmg = d->dxmid_m;
+  }
   if (group == 1) { rgbnm_tn_defer_begin(); tn_open = true; }
-  TRY(rgbnm_gemm_tn(dt, s->dx_mid, E, a->attn, I, g->dwproj, g->dbproj, M, E, I, 0, 0, WS(2), st));
-  TRY(rgbnm_gemm_nt(dt, RGBNM_EPI_NONE, s->dx_mid, E, p->wproj_t, E, s->dattn, I, 0, 0, 0, 0, 0, 0, 0, M, I, E, 0, st));
+  TRY(rgbnm_gemm_tn(dt, dxmg, E, a->attn, I, g->dwproj, g->dbproj, M, E, I, 0, 0, WS(2), st));
+  TRY(rgbnm_gemm_nt(dt, RGBNM_EPI_NONE, dxmg, E, p->wproj_t, E, s->dattn, I, 0, 0, 0, 0, 0, 0, 0, M, I, E, 0, st));
   TRY(rgbnm_attention_bwd(dt, a->qkv, a->attn, s->dattn, a->lse, s->dqkv, c->B, c->N, c->heads, c->attn_scale, st));
   TRY(rgbnm_gemm_tn(dt, s->dqkv, 3 * I, a->xn1, E, g->dwqkv, g->dbqkv, M, 3 * I, E, c->heads, 0, WS(3), st));
   if (group) { tn_open = false; TRY(rgbnm_tn_defer_flush((hipStream_t)st)); }
@@ -292,6 +327,18 @@ int rgbnm_vit_block_bwd(const rgbnm_vit_cfg* c, const rgbnm_block_params* p, con
   const int rt = tn_open ? rgbnm_tn_defer_flush((hipStream_t)st) : RGBNM_OK;      // only an error leaves the grouping open
   const int rf = rgbnm_reduce_defer_flush((hipStream_t)st);
   return rc != RGBNM_OK ? rc : (rt != RGBNM_OK ? rt : rf);
+}
+
+int rgbnm_vit_block_bwd(const rgbnm_vit_cfg* c, const rgbnm_block_params* p, const rgbnm_block_acts* a,
+                        const rgbnm_block_grads* g, const rgbnm_block_scratch* s, const void* dy, void* dx, void* st) {
+  return block_bwd(c, p, a, g, s, nullptr, dy, dx, st);
+}
+
+int rgbnm_vit_block_bwd_drop(const rgbnm_vit_cfg* c, const rgbnm_block_params* p, const rgbnm_block_acts* a,
+                             const rgbnm_block_grads* g, const rgbnm_block_scratch* s, const rgbnm_dropout* d, const void* dy,
+                             void* dx, void* st) {
+  if (!d) return RGBNM_EINVAL;
+  return block_bwd(c, p, a, g, s, d, dy, dx, st);
 }
 
 // The weight / bias / LayerNorm-parameter gradients of n blocks after rgbnm_vit_chain_bwd (vit_chain_bwd.hip) has run their data

@@ -10,6 +10,7 @@ LIB_PATH = os.path.join(HERE, "librgbnm.so")
 
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 EPI_NONE, EPI_RES, EPI_GELU, EPI_POS, EPI_DGELU, EPI_TANH, EPI_DTANH = range(7)
+EPI_RES_DROP, EPI_GELU_DROP = 7, 8      # rgbnm_gemm_nt_drop only
 
 _vp, _i, _f, _sz, _ll = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_longlong
 # seconds the host spent blocked on the pinned-slot rings of the per-step records (augment parameters, mixup lambda): the host runs
@@ -45,6 +46,10 @@ class BlockGrads(C.Structure):
 class BlockScratch(C.Structure):
     _fields_ = [("du", _vp), ("dxn", _vp), ("dx_mid", _vp), ("dattn", _vp), ("dqkv", _vp), ("ws", _vp),
                 ("ws_bytes", _sz)]
+
+
+class Dropout(C.Structure):
+    _fields_ = [("seed", _vp), ("p", _f), ("block", _i), ("dy_m", _vp), ("dxmid_m", _vp)]
 
 
 class HeadParams(C.Structure):
@@ -92,6 +97,9 @@ PROTOTYPES = {
     "rgbnm_trace_collect": (_i, [_i, _vp, _vp, _vp, _vp]),
     "rgbnm_trace_reserve": (_i, [_i]),
     "rgbnm_gemm_nt": (_i, [_i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    "rgbnm_gemm_nt_drop": (_i, [_i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _f, _i,
+                                _i, _vp]),
+    "rgbnm_dropout_apply": (_i, [_i, _vp, _f, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     "rgbnm_gemm_tn_workspace": (_sz, [_i, _i, _i]),
     "rgbnm_gemm_tn_workspace_splits": (_sz, [_i, _i, _i]),
     "rgbnm_gemm_tn": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
@@ -165,6 +173,9 @@ PROTOTYPES = {
     "rgbnm_vit_block_fwd_chain": (_i, [_P(VitCfg), _P(BlockParams), _P(BlockActs), _i, _P(BlockParams), _P(BlockActs), _vp]),
     "rgbnm_vit_block_bwd": (_i, [_P(VitCfg), _P(BlockParams), _P(BlockActs), _P(BlockGrads), _P(BlockScratch), _vp,
                                  _vp, _vp]),
+    "rgbnm_vit_block_fwd_drop": (_i, [_P(VitCfg), _P(BlockParams), _P(BlockActs), _P(Dropout), _vp]),
+    "rgbnm_vit_block_bwd_drop": (_i, [_P(VitCfg), _P(BlockParams), _P(BlockActs), _P(BlockGrads), _P(BlockScratch), _P(Dropout),
+                                      _vp, _vp, _vp]),
     "rgbnm_patch_embed_fwd": (_i, [_P(VitCfg), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "rgbnm_patch_embed_fwd_mix": (_i, [_P(VitCfg), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "rgbnm_patch_embed_bwd": (_i, [_P(VitCfg), _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -203,6 +203,7 @@ class _FwdState:
     def __init__(self, model, arena, gbuf):
         self.model, self.arena, self.gbuf = model, arena, gbuf
         self.holding = False
+        self.drop = self.drop_seed = None      # dropout p > 0: per-block rgbnm_dropout structs and this forward's device seed
 
     # ---- held gradient reductions (rgbnm.h rgbnm_reduce_hold_*; ViT.defer_grad_reduction): opened after the head's backward,
     # closed in front of the patch embedding's, whose own reductions run at once (both nodes run on the same autograd thread:
@@ -475,6 +476,12 @@ class _BlockFn(torch.autograd.Function):
     def forward(ctx, x, st, idx, *params):
         m, a = st.model, st.arena
         assert x.data_ptr() == a.xbuf(idx).data_ptr()
+        if st.drop is not None:
+            # dropout p > 0 (ViT.train_dropout): the per-block entries with the masked epilogues (rgbnm.h rgbnm_vit_block_fwd_drop)
+            L.check(L.lib().rgbnm_vit_block_fwd_drop(C.byref(a.cfg), C.byref(m._bparams[idx]), C.byref(a.acts[idx]),
+                                                     C.byref(st.drop[idx]), L.stream()), "vit_block_fwd_drop")
+            ctx.st, ctx.idx = st, idx
+            return a.xbuf(idx + 1).detach()
         # the whole encoder forward as ONE launch (rgbnm.h rgbnm_vit_chain_fwd): block 0's node runs it, the nodes of the other
         # blocks only hand their output buffer on -- the autograd graph (one backward node per block) stays what it was
         if idx == 0:
@@ -508,10 +515,15 @@ class _BlockFn(torch.autograd.Function):
         # that runs (the last block); each node then only launches its weight-gradient GEMMs and reductions
         if idx == m.depth - 1:
             m._check_prep_gen(st)
-            st.chain_bwd = m._chain_backward(a, dy)
+            st.chain_bwd = st.drop is None and m._chain_backward(a, dy)
             st.dw_pending = []
         try:
-            if getattr(st, "chain_bwd", False):
+            if st.drop is not None:
+                # the masks are regenerated from this forward's seed (st.drop_seed); dy_m / dxmid_m live in the arena
+                L.check(L.lib().rgbnm_vit_block_bwd_drop(C.byref(a.cfg), C.byref(m._bparams[idx]), C.byref(a.acts[idx]),
+                                                         C.byref(g), C.byref(scratch), C.byref(st.drop[idx]), dy.data_ptr(),
+                                                         dx.data_ptr(), L.stream()), "vit_block_bwd_drop")
+            elif getattr(st, "chain_bwd", False):
                 # the weight-gradient GEMMs of several blocks share ONE grouped launch (rgbnm_vit_blocks_bwd_dw: the more blocks,
                 # the fewer token splits); a block's gradients are final -- and handed to the exchange -- when its group has run
                 dx = a.dx_blk[idx]
@@ -727,6 +739,11 @@ class ViT(FlatParamModule):
     defer_grad_reduction = False
     dw_group_overlapped = 4        # blocks per grouped weight-gradient launch while gradient slices are exchanged during the backward
     single_encoder_node = True     # all blocks as one autograd node when the one-launch forward is on (_EncoderFn); False: one node per block
+    # training with drop_p > 0: False refuses (NotImplementedError); True runs the reference's three dropout sites per block on the device
+    # (rgbnm.h, dropout mask contract): masks from this library's Philox stream, not torch's, and the per-block kernels instead of
+    # the one-launch encoder
+    train_dropout = False
+    last_dropout_seed = None       # device int64 tensor: the seed of the latest training forward with dropout (the masks: rgbnm.h)
 
     def __init__(self, in_channels: int = 3, patch_size: int = 16, emb_size: int = 768, input_embed: int = -1,
                  depth: int = 12, n_classes: int = 1000, drop_p=0.1, pixel_space="RGB", ver=1, use_subblock=True,
@@ -740,7 +757,7 @@ class ViT(FlatParamModule):
         if ver in (1, 3) and not use_subblock:
             raise NotImplementedError("embed_type 1 / 3 without sub-block conversion are not in any reference config")
         # nn.Dropout(drop_p) of plainvit.py:489, 515, 525 is the identity in eval mode: a model built with the constructor's default
-        # (0.1) evaluates fine; TRAINING with p > 0 (no reference config: cfg.TRAIN.DROP = 0, configs.py:27) is refused at forward()
+        # (0.1) evaluates fine; TRAINING with p > 0 (train.py --drop) needs train_dropout = True, else forward() refuses
         if not 0.0 <= float(drop_p) < 1.0:
             raise ValueError("dropout probability has to be in [0, 1)")
         self.drop_p = float(drop_p)
@@ -940,14 +957,14 @@ class ViT(FlatParamModule):
         assert max(idx.max(), idb.max()) < 2 ** 31
         return torch.from_numpy(idx.astype(np.int32)).to(dev), torch.from_numpy(idb.astype(np.int32)).to(dev)
 
-    def _prep(self, cdtype):
+    def _prep(self, cdtype, chains=True):
         """fp32 masters -> operand shadows (cast, qkv de-interleave, transposes) and, for the one-launch encoder kernels, their
-        chain images -- ONE launch per step."""
+        chain images -- ONE launch per step.  chains=False: a step on the per-block kernels (dropout): shadows only."""
         if cdtype not in self._shadow:
             self._shadow[cdtype] = torch.zeros(self._sh_total, device=self._flat.device, dtype=cdtype)
         self._cur_dtype = cdtype
         self._prep_gen = getattr(self, "_prep_gen", 0) + 1        # (the shadows and the chain images are model-global: see _check_prep_gen)
-        chain = cdtype == torch.bfloat16 and self._chain_idx is not None
+        chain = chains and cdtype == torch.bfloat16 and self._chain_idx is not None
         img_f = self._chain_img.data_ptr() if chain and L.lib().rgbnm_get_option(b"fwd_chain") else None
         img_b = (self._chain_img_bwd.data_ptr() if chain and L.lib().rgbnm_get_option(b"bwd_chain") and torch.is_grad_enabled()
                  else None)
@@ -1113,19 +1130,22 @@ class ViT(FlatParamModule):
             cdtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else torch.float32
         if cdtype not in (torch.float32, torch.bfloat16, torch.float16):
             raise NotImplementedError(f"compute dtype {cdtype}: the MI355X path implements fp32, bf16 and fp16")
-        if self.drop_p and self.training:
-            raise NotImplementedError("training with dropout p > 0 is not implemented on the HIP path (cfg.TRAIN.DROP is 0 in every "
-                                      "reference config, configs.py:27); model.eval() runs, where nn.Dropout is the identity")
+        drop = bool(self.drop_p and self.training)
+        if drop and not self.train_dropout:
+            raise NotImplementedError("training with dropout p > 0 runs only with model.train_dropout = True (masks from this "
+                                      "library's Philox stream, not torch's); model.eval() runs, where nn.Dropout is the identity")
         self._ensure_flat()
         B = x.shape[0]
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self._named.values())
         if need_grad and self._grad_sync is not None:
             self._grad_sync.begin_step()
-        self._prep(cdtype)
+        self._prep(cdtype, chains=not drop)
         arena = self._acquire_arena(B, cdtype, need_grad)
         st = _FwdState(self, arena, self._grad_buffer() if need_grad else None)
         st.prep_gen = self._prep_gen
-        st.ln_chain = bool(L.lib().rgbnm_vit_ln_chain(C.byref(arena.cfg)))
+        st.ln_chain = bool(L.lib().rgbnm_vit_ln_chain(C.byref(arena.cfg))) and not drop
+        if drop:
+            self._begin_dropout(st)
         named = self._named
         if self.embed_kind == "group":
             h = _PatchEmbedFn.apply(x, cbcr, st, named["patchembed.projection.0.weight"],
@@ -1136,7 +1156,7 @@ class ViT(FlatParamModule):
             h = _PatchEmbedSepFn.apply(x, cbcr, st, *[named[n] for n in _PES_NAMES])
         else:
             h = _PatchEmbedConcatFn.apply(x, cbcr, st, *[named[n] for n in _PE3_NAMES])
-        if (self.single_encoder_node and cdtype == torch.bfloat16 and self._chain_idx is not None
+        if (not drop and self.single_encoder_node and cdtype == torch.bfloat16 and self._chain_idx is not None
                 and L.lib().rgbnm_get_option(b"fwd_chain")):
             h = _EncoderFn.apply(h, st, *self._all_block_params())
         else:
@@ -1147,6 +1167,21 @@ class ViT(FlatParamModule):
             out, edge = out
             out._rgbnm_grad_edge = edge      # cls_transforms.cross_entropy: the compute-dtype gradient edge of these logits
         return out
+
+    def _begin_dropout(self, st):
+        """A fresh 64-bit seed for this forward, drawn on the device from torch's default generator (no host sync; a captured
+        graph draws a new one on every replay), owned by the forward's state: the backward regenerates the same masks from it,
+        whatever other forwards ran in between.  The latest one is model.last_dropout_seed."""
+        a = st.arena
+        st.drop_seed = torch.empty(1, device=self._flat.device, dtype=torch.int64).random_(-2 ** 63, None)
+        self.last_dropout_seed = st.drop_seed
+        if a.need_grad and getattr(a, "drop_dy", None) is None:
+            M, E = a.B * self.n_tokens, self.emb_size
+            a.drop_dy = torch.empty(M, E, device=self._flat.device, dtype=a.cdtype)       # masked dy / d(x_mid) of one block's backward
+            a.drop_dxmid = torch.empty(M, E, device=self._flat.device, dtype=a.cdtype)
+        dy_m = a.drop_dy.data_ptr() if a.need_grad else None
+        dxm_m = a.drop_dxmid.data_ptr() if a.need_grad else None
+        st.drop = [L.Dropout(st.drop_seed.data_ptr(), self.drop_p, i, dy_m, dxm_m) for i in range(self.depth)]
 
     def _all_block_params(self):
         named = self._named
