@@ -582,7 +582,8 @@ int rgbnm_ln_generic_bwd(int dtype, const void* dy, const void* x, const float* 
                          void* stream);
 /* WindowAttention + cyclic shift + window partition / reverse (swinv2.py:143-182, 273-300) on token-major tensors:
  * qkv [B, res*res, 3C] (q | k | v, heads of 32), bias [heads, 64, 64] fp32 (= 16 sigmoid(cpb_mlp(table))[index]),
- * scale [heads] fp32 (= exp(min(logit_scale, ln 100))), shift in {0, 4}: window 8x8, cosine attention, shift mask -100.
+ * scale [heads] fp32 (= exp(min(logit_scale, ln 100))), 0 <= shift < 8 (the model uses 0 and 4; else RGBNM_EINVAL): window 8x8,
+ * cosine attention, shift mask -100.
  * out [B, res*res, C]; lse [B * nW * heads * 64] saved for backward.  Backward writes dbias (per-wave partials in the
  * workspace, deterministic reduction), one partial d(scale) per (window, head) into dscale_part [B * nW * heads] and -- when
  * dscale is not NULL -- their sum into dscale [heads] (a job of the same batched reduction). */
