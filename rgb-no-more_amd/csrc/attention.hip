@@ -75,14 +75,6 @@ __device__ __forceinline__ Frag<T> tfrag(const T* img, int d, int t, int fi, int
   return f;
 }
 
-// B-operand fragment from 16 accumulator-layout values of one tile.
-template <typename T> __device__ __forceinline__ Frag<T> pfrag(const float (&p)[16], int fi) {
-  Frag<T> f;
-#pragma unroll
-  for (int j = 0; j < Frag<T>::EPL; ++j) f.v[j] = from_f32<T>(p[fi * Frag<T>::EPL + j]);
-  return f;
-}
-
 // ------------------------------------------------------------------------------------------- forward
 template <typename T, int NT>
 __global__ __launch_bounds__(AN<NT>::NTHREADS) void attn_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ out,

@@ -12,29 +12,21 @@
 #include "common.h"
 #include <type_traits>
 #include "internal.h"
+#include "tile128.h"
 #include "../../include/rgbnm.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef const __attribute__((address_space(1))) void* glb_ptr;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int HD = 64;
 constexpr int NTILE = 7;
 constexpr int NPAD = NTILE * 32;          // 224 token rows per LDS array
-constexpr int ROWB = 128;                 // bytes per token row
 constexpr int ARR = NPAD * ROWB;          // 28 KB
 constexpr int NTHREADS = NTILE * 64;
 constexpr int NTHREADS3 = NTHREADS + 64;   // attn3_bwd_kernel: 7 compute waves + 1 DMA wave
 
-__device__ __forceinline__ int fswz(int row) {
-  return (((row >> 1) & 1) << 2) | ((row >> 2) & 1) | (((row >> 3) & 1) << 1);
-}
-
 // LDS-DMA one [N][64] bf16 matrix (row stride ld elements): 28 instructions of 1 KB (8 rows); wave w issues
 // w, w+7, w+14, w+21.  Rows >= N replicate row N-1 (finite data; their probabilities are masked to zero).
+// (All 28 from ONE wave, the DMA wave of attn3_bwd_kernel: tile128.h dma_matrix_all.)
 __device__ __forceinline__ void dma_matrix(const bf16* __restrict__ src, int ld, int N, unsigned char* dst, int w,
                                            int lane) {
 #pragma unroll
@@ -47,20 +39,10 @@ __device__ __forceinline__ void dma_matrix(const bf16* __restrict__ src, int ld,
   }
 }
 
-// rowfrag with the per-lane part folded into one offset rb = l31 * ROWB + ((g ^ fswz(l31)) << 4): chunk c of the row is at
-// rb ^ (c << 5) because (2c + g) ^ fl = 2c ^ (g ^ fl).  rb is re-derived (made opaque) at the start of each phase so the
-// per-array, per-chunk addresses are not kept in registers -- or spilled -- across the whole persistent loop.
-__device__ __forceinline__ Frag<bf16> rowfrag_x(const unsigned char* arr, unsigned rb, int t, int c) {
-  Frag<bf16> f;
-  f.v = *reinterpret_cast<const bf16x8*>(arr + (rb ^ (unsigned)(c << 5)) + t * 32 * ROWB);
-  return f;
-}
-
 // MFMA groups of one 32-row tile with their row fragments in a PINNED order (sched_barrier after every step).  Left alone the
 // compiler emits read - wait - MFMA with ONE fragment buffer: an exposed LDS latency per MFMA (36 of attn3_fwd's 80 MFMAs, 50 of
-// attn3_bwd's 196).  row_mma4: one accumulator, the four fragments requested together; row_pair_mma: two accumulators (scores and
-// their gradient), four fragments ahead, every MFMA followed by the read of the fragment two steps on.  Same MFMA order per
-// accumulator: same bits.  -DAV2_ROWPIPE=0: the plain loops (experiments).
+// attn3_bwd's 196).  row_mma4: one accumulator, the four fragments requested together; row_pair_mma (tile128.h): two accumulators.
+// Same MFMA order per accumulator: same bits.  -DAV2_ROWPIPE=0: the plain loops (experiments).
 #ifndef AV2_ROWPIPE
 #define AV2_ROWPIPE 1
 #endif
@@ -79,61 +61,12 @@ __device__ __forceinline__ void row_mma4(f32x16& acc, const unsigned char* arr, 
   for (int c = 0; c < 4; ++c) mma(acc, rowfrag_x(arr, rb, t, c), x[c]);
 #endif
 }
-__device__ __forceinline__ void row_pair_mma(f32x16& sa, f32x16& da, const unsigned char* arrS, const unsigned char* arrD, unsigned rb,
-                                             int t, const Frag<bf16> (&xs)[4], const Frag<bf16> (&xd)[4]) {
-#if AV2_ROWPIPE
-#define AV2_SB __builtin_amdgcn_sched_barrier(0)
-  Frag<bf16> fs[4], fd[4];
-  AV2_SB;
-  fs[0] = rowfrag_x(arrS, rb, t, 0);
-  fd[0] = rowfrag_x(arrD, rb, t, 0);
-  fs[1] = rowfrag_x(arrS, rb, t, 1);
-  fd[1] = rowfrag_x(arrD, rb, t, 1);
-  AV2_SB;
-  mma(sa, fs[0], xs[0]); AV2_SB;
-  fs[2] = rowfrag_x(arrS, rb, t, 2); AV2_SB;
-  mma(da, fd[0], xd[0]); AV2_SB;
-  fd[2] = rowfrag_x(arrD, rb, t, 2); AV2_SB;
-  mma(sa, fs[1], xs[1]); AV2_SB;
-  fs[3] = rowfrag_x(arrS, rb, t, 3); AV2_SB;
-  mma(da, fd[1], xd[1]); AV2_SB;
-  fd[3] = rowfrag_x(arrD, rb, t, 3); AV2_SB;
-  mma(sa, fs[2], xs[2]);
-  mma(da, fd[2], xd[2]);
-  mma(sa, fs[3], xs[3]);
-  mma(da, fd[3], xd[3]);
-  AV2_SB;
-#undef AV2_SB
-#else
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    mma(sa, rowfrag_x(arrS, rb, t, c), xs[c]);
-    mma(da, rowfrag_x(arrD, rb, t, c), xd[c]);
-  }
-#endif
-}
-
-// The same 28 instructions issued by ONE wave (the DMA wave of attn3_bwd_kernel).
-__device__ __forceinline__ void dma_matrix_all(const bf16* __restrict__ src, int ld, int N, unsigned char* dst, int lane) {
-#pragma unroll 4
-  for (int i = 0; i < 28; ++i) {
-    const int row = 8 * i + (lane >> 3), pc = lane & 7;
-    const int lc = pc ^ fswz(row);
-    const int srow = row < N ? row : N - 1;
-    __builtin_amdgcn_global_load_lds((glb_ptr)(src + (size_t)srow * ld + lc * 8), (lds_ptr)(dst + i * 1024), 16, 0, 0);
-  }
-}
 
 // MFMA operand with the head dim as reduction axis: lane <-> token row (32t + l31), 32-byte chunk c, half g.
 __device__ __forceinline__ Frag<bf16> rowfrag(const unsigned char* arr, int t, int l31, int c, int g, int fl) {
   Frag<bf16> f;
   f.v = *reinterpret_cast<const bf16x8*>(arr + (32 * t + l31) * ROWB + (((2 * c + g) ^ fl) << 4));
   return f;
-}
-
-__device__ __forceinline__ bf16x8 pack8(u32x2 lo, u32x2 hi) {
-  u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(bf16x8, v);
 }
 
 // Transposed operands (tokens as reduction axis) of tile T, fragment FI, for both 32-wide d tiles:
@@ -156,32 +89,7 @@ __device__ __forceinline__ void tfrag2(unsigned a0, Frag<bf16>& f0, Frag<bf16>& 
   f1.v = pack8(y0, y1);
 }
 
-// Both fragments (FI = 0, 1) x both d tiles of tile T from ONE array: 8 reads, one wait.
-template <int T>
-__device__ __forceinline__ void tfrag4(unsigned a0, Frag<bf16> (&f)[4]) {
-  u32x2 r0, r1, r2, r3, r4, r5, r6, r7;
-  const unsigned a00 = a0, a01 = (a0 ^ 32u) + 1024u, a10 = a0 ^ 64u, a11 = (a0 ^ 96u) + 1024u;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %8 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %1, %9 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %2, %10 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %3, %11 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %4, %8 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %5, %9 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %6, %10 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %7, %11 offset:%13\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5), "=&v"(r6), "=&v"(r7)
-      : "v"(a00), "v"(a01), "v"(a10), "v"(a11), "i"(T * 4096), "i"(T * 4096 + 2048)
-      : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  f[0].v = pack8(r0, r1);   // fi=0, dt=0
-  f[1].v = pack8(r2, r3);   // fi=0, dt=1
-  f[2].v = pack8(r4, r5);   // fi=1, dt=0
-  f[3].v = pack8(r6, r7);   // fi=1, dt=1
-}
-
-// The same for TWO arrays (phase B of backward: dO^T and Q^T): 16 reads, one wait.
+// tile128.h tfrag4 for TWO arrays (phase B of backward: dO^T and Q^T): 16 reads, one wait.
 template <int T>
 __device__ __forceinline__ void tfrag8(unsigned a0, unsigned b0, Frag<bf16> (&fa)[4], Frag<bf16> (&fb)[4]) {
   u32x2 r0, r1, r2, r3, r4, r5, r6, r7, q0, q1, q2, q3, q4, q5, q6, q7;
@@ -215,39 +123,6 @@ __device__ __forceinline__ void tfrag8(unsigned a0, unsigned b0, Frag<bf16> (&fa
   fb[0].v = pack8(q0, q1); fb[1].v = pack8(q2, q3); fb[2].v = pack8(q4, q5); fb[3].v = pack8(q6, q7);
 }
 
-__device__ __forceinline__ Frag<bf16> pfrag(const float (&p)[16], int fi) {
-  Frag<bf16> f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) f.v[j] = (bf16)p[fi * 8 + j];
-  return f;
-}
-
-struct LaneGeo {
-  int lane, l31, g, fl;
-  unsigned tr0;    // byte offset inside an array of the (t=0, fi=0, dt=0, rd=0) transpose read
-};
-__device__ __forceinline__ LaneGeo lane_geo() {
-  LaneGeo L;
-  L.lane = threadIdx.x & 63;
-  L.l31 = L.lane & 31;
-  L.g = L.lane >> 5;
-  L.fl = fswz(L.l31);
-  const int k = (L.lane >> 2) & 3, G1 = (L.lane >> 4) & 1, l3 = L.lane & 3;
-  const int pc = (2 * G1 + (l3 >> 1)) ^ (((k >> 1) << 2) | L.g);
-  L.tr0 = (unsigned)((4 * L.g + k) * ROWB + pc * 16 + 8 * (l3 & 1));
-  return L;
-}
-
-template <int T> struct TileLoop {
-  template <typename F> static __device__ __forceinline__ void run(F&& f) {
-    TileLoop<T - 1>::run(f);
-    f(std::integral_constant<int, T - 1>{});
-  }
-};
-template <> struct TileLoop<0> {
-  template <typename F> static __device__ __forceinline__ void run(F&&) {}
-};
-
 // ------------------------------------------------------------------------------------------------ forward
 template <int NTOK, int T> __device__ __forceinline__ bool tile_on(int N) {
   if constexpr (NTOK > 0) return T * 32 < NTOK;
@@ -272,7 +147,7 @@ __global__ __launch_bounds__(NTHREADS) void attn2_fwd_kernel(const bf16* __restr
   const bf16* Q = qkv + (size_t)b * N * ld + h * HD;
   const bf16* K = Q + inner;
   const bf16* V = Q + 2 * inner;
-  const LaneGeo L = lane_geo();
+  const Geo L = make_geo();
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
   dma_matrix(K, ld, N, Ks, w, L.lane);
@@ -334,10 +209,10 @@ __global__ __launch_bounds__(NTHREADS) void attn2_fwd_kernel(const bf16* __restr
       }
       Frag<bf16> vv[4];
       tfrag4<t>(vt, vv);
-      Frag<bf16> pf = pfrag(pr, 0);
+      Frag<bf16> pf = pfrag<bf16>(pr, 0);
       mma(o[0], vv[0], pf);
       mma(o[1], vv[1], pf);
-      pf = pfrag(pr, 1);
+      pf = pfrag<bf16>(pr, 1);
       mma(o[0], vv[2], pf);
       mma(o[1], vv[3], pf);
     }
@@ -382,7 +257,7 @@ __global__ __launch_bounds__(NTHREADS) void attn2_bwd_kernel(const bf16* __restr
   const bf16* V = Q + 2 * inner;
   const bf16* O = out + (size_t)b * N * inner + h * HD;
   const bf16* dO = dout + (size_t)b * N * inner + h * HD;
-  const LaneGeo L = lane_geo();
+  const Geo L = make_geo();
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
   APROF(0);
@@ -445,10 +320,10 @@ __global__ __launch_bounds__(NTHREADS) void attn2_bwd_kernel(const bf16* __restr
         }
         Frag<bf16> kk[4];
         tfrag4<t>(kt, kk);
-        Frag<bf16> sf = pfrag(ds, 0);
+        Frag<bf16> sf = pfrag<bf16>(ds, 0);
         mma(dq[0], kk[0], sf);
         mma(dq[1], kk[1], sf);
-        sf = pfrag(ds, 1);
+        sf = pfrag<bf16>(ds, 1);
         mma(dq[0], kk[2], sf);
         mma(dq[1], kk[3], sf);
       }
@@ -504,16 +379,16 @@ __global__ __launch_bounds__(NTHREADS) void attn2_bwd_kernel(const bf16* __restr
       }
       Frag<bf16> gg[4], qq4[4];
       tfrag8<t>(gt_, qt_, gg, qq4);
-      Frag<bf16> f = pfrag(pp, 0);
+      Frag<bf16> f = pfrag<bf16>(pp, 0);
       mma(dv[0], gg[0], f);
       mma(dv[1], gg[1], f);
-      f = pfrag(pp, 1);
+      f = pfrag<bf16>(pp, 1);
       mma(dv[0], gg[2], f);
       mma(dv[1], gg[3], f);
-      f = pfrag(ds, 0);
+      f = pfrag<bf16>(ds, 0);
       mma(dk[0], qq4[0], f);
       mma(dk[1], qq4[1], f);
-      f = pfrag(ds, 1);
+      f = pfrag<bf16>(ds, 1);
       mma(dk[0], qq4[2], f);
       mma(dk[1], qq4[3], f);
     }
@@ -559,54 +434,9 @@ __global__ __launch_bounds__(NTHREADS) void attn2_bwd_kernel(const bf16* __restr
 // NTOK > 0: the token count is a compile-time constant (196 for JPEG-Ti/S): every tile test folds away and only the
 // ragged last tile carries a mask.  (With a runtime N the compiler kept 14 tile predicates and 100+ lane masks alive in
 // SGPRs and spilled them through v_writelane / v_readlane: 650 of the kernel's 2900 VALU instructions.)
-// Gradient rows leave the persistent backward as full 128-byte lines, and not from the compute waves.  In the swapped
-// orientation a lane owns one token and 4 consecutive head-dim values per accumulator quad, so direct stores are 8 bytes
-// per lane at a 1152-byte stride; worse, every CU reaches its store / load burst at the same time and a vmem instruction
-// then takes ~700-1000 cycles to ISSUE (cycle stamps: 40 % of a pair's time went to issuing 24 stores, 13 loads and 16
-// LDS-DMAs per wave).  So the compute waves only park their 32 x 64 bf16 tiles in LDS (8-byte writes, conflict free):
-//   dQ -> the wave's own rows of Ks (free after the mid barrier),  dK -> a private 4.5 KB tile,  dV -> own rows of Gs
-// and the DMA wave reads them back as 16 B per lane, 8 lanes per row, and issues every global store (whole lines).
-constexpr int STG_PITCH = 144;
-constexpr int STG_WAVE = 32 * STG_PITCH;       // 4.5 KB per wave
-__device__ __forceinline__ void tile_park_private(unsigned char* stg, const f32x16 (&acc)[2], float mul, const LaneGeo& L) {
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int rq = 0; rq < 4; ++rq) {
-      f32x4 v = {acc[dt][rq * 4 + 0], acc[dt][rq * 4 + 1], acc[dt][rq * 4 + 2], acc[dt][rq * 4 + 3]};
-      store4<bf16>(reinterpret_cast<bf16*>(stg + L.l31 * STG_PITCH) + dt * 32 + rq * 8 + L.g * 4, v * mul);
-    }
-}
-// rows w*32 .. w*32+31 of a 128-byte-pitch array; 16-byte chunk c of row r sits at chunk c ^ (r & 7)
-__device__ __forceinline__ void tile_park_rows(unsigned char* arr, int w, const f32x16 (&acc)[2], float mul, const LaneGeo& L) {
-  // one opaque base offset, chunk selected by XOR with a constant: the 8 swizzled addresses are loop invariants that the
-  // compiler otherwise hoists to the kernel prologue and then SPILLS (each reload a serialised scratch round trip)
-  const int ln = lane_id_here();   // (and off0 itself is recomputed here, not kept live across the pair)
-  const unsigned off0 = (unsigned)((w * 32 + (ln & 31)) * ROWB + ((ln & 7) << 4) + (ln >> 5) * 8);
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int rq = 0; rq < 4; ++rq) {
-      f32x4 v = {acc[dt][rq * 4 + 0], acc[dt][rq * 4 + 1], acc[dt][rq * 4 + 2], acc[dt][rq * 4 + 3]};
-      store4<bf16>(reinterpret_cast<bf16*>(arr + (off0 ^ (unsigned)((dt * 4 + rq) << 4))), v * mul);
-    }
-}
-// DMA wave: the parked tiles of all compute waves -> registers -> global rows (column block of 64 at g0, row stride ld)
-template <bool PRIVATE>
-__device__ __forceinline__ void tiles_read(const unsigned char* src, int N, int lane, u32x4 (&v)[NTILE][4]) {
-  const int rl = lane >> 3, seg = lane & 7;
-#pragma unroll
-  for (int wv = 0; wv < NTILE; ++wv) {
-    if (wv * 32 < N) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int r = i * 8 + rl;
-        v[wv][i] = PRIVATE ? *reinterpret_cast<const u32x4*>(src + wv * STG_WAVE + r * STG_PITCH + seg * 16)
-                           : *reinterpret_cast<const u32x4*>(src + (wv * 32 + r) * ROWB + ((seg ^ (r & 7)) << 4));
-      }
-    }
-  }
-}
+// Gradient rows leave the persistent backward as full 128-byte lines, and not from the compute waves: parked in LDS and read back
+// by the DMA wave (tile128.h), which sends them on to global rows (column block of 64 at g0, row stride ld).  Sibling of
+// vit_chain_bwd.hip tiles_write, which has the constant token count and that file's store switches (gstore)
 __device__ __forceinline__ void tiles_write(const u32x4 (&v)[NTILE][4], bf16* __restrict__ g0, size_t ld, int N, int lane) {
   const int rl = lane >> 3, seg = lane & 7;
 #pragma unroll
@@ -638,7 +468,7 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __rest
   float* L2_s = reinterpret_cast<float*>(smem + 4 * ARR);   // [NPAD] lse * log2(e)
   float* D_s = L2_s + NPAD;                                 // [NPAD] rowsum(dO * O)
   const int inner = heads * HD, ld = 3 * inner;
-  const LaneGeo L = lane_geo();
+  const Geo L = make_geo();
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   unsigned char* stg = smem + 4 * ARR + 2 * NPAD * (int)sizeof(float) + w * STG_WAVE;   // this wave's store tile
   const unsigned rb0 = (unsigned)(L.l31 * ROWB + ((L.g ^ L.fl) << 4));
@@ -799,7 +629,7 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __rest
           f32x16 sa, da;
 #pragma unroll
           for (int r = 0; r < 16; ++r) { sa[r] = 0.f; da[r] = 0.f; }
-          row_pair_mma(sa, da, Ks, Vs, rb, t, qf, gf);
+          row_pair_mma<AV2_ROWPIPE != 0>(sa, da, Ks, Vs, rb, t, qf, gf);
           float ds[16];
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
@@ -813,10 +643,10 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __rest
           }
           Frag<bf16> kk[4];
           tfrag4<t>(kt, kk);
-          Frag<bf16> sf = pfrag(ds, 0);
+          Frag<bf16> sf = pfrag<bf16>(ds, 0);
           mma(dq[0], kk[0], sf);
           mma(dq[1], kk[1], sf);
-          sf = pfrag(ds, 1);
+          sf = pfrag<bf16>(ds, 1);
           mma(dq[0], kk[2], sf);
           mma(dq[1], kk[3], sf);
         }
@@ -850,7 +680,7 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __rest
           f32x16 sa, da;
 #pragma unroll
           for (int r = 0; r < 16; ++r) { sa[r] = 0.f; da[r] = 0.f; }
-          row_pair_mma(sa, da, Qs, Gs, rb, t, kf, vf);
+          row_pair_mma<AV2_ROWPIPE != 0>(sa, da, Qs, Gs, rb, t, kf, vf);
           float pp[16], ds[16];
 #pragma unroll
           for (int q4 = 0; q4 < 4; ++q4) {   // accumulator rows 4 q4 .. 4 q4 + 3 = queries t*32 + 8 q4 + 4 g + 0..3
@@ -871,17 +701,17 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __rest
           }
           Frag<bf16> gg[4];
           tfrag4<t>(gt_, gg);
-          Frag<bf16> f = pfrag(pp, 0);
+          Frag<bf16> f = pfrag<bf16>(pp, 0);
           mma(dv[0], gg[0], f);
           mma(dv[1], gg[1], f);
-          f = pfrag(pp, 1);
+          f = pfrag<bf16>(pp, 1);
           mma(dv[0], gg[2], f);
           mma(dv[1], gg[3], f);
           tfrag4<t>(qt_, gg);
-          f = pfrag(ds, 0);
+          f = pfrag<bf16>(ds, 0);
           mma(dk[0], gg[0], f);
           mma(dk[1], gg[1], f);
-          f = pfrag(ds, 1);
+          f = pfrag<bf16>(ds, 1);
           mma(dk[0], gg[2], f);
           mma(dk[1], gg[3], f);
         }
@@ -896,7 +726,7 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __rest
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();          // end: every wave is done with Q,dO, D_s, L2_s; dK tiles parked
       APROF3(6);
-      tile_park_rows(Gs, w, dv, 1.0f, L);
+      tile_park_rows(Gs, w, dv, 1.0f);
     } else {
       if (nxt < nbh) load_own_qg(nxt);
       __builtin_amdgcn_s_barrier();          // end
@@ -924,7 +754,7 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_fwd_kernel(const bf16* __rest
   const int N = NTOK > 0 ? NTOK : N_rt;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int inner = heads * HD, ld = 3 * inner;
-  const LaneGeo L = lane_geo();
+  const Geo L = make_geo();
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int bh = blockIdx.x;
   if (bh >= nbh) return;
@@ -1029,10 +859,10 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_fwd_kernel(const bf16* __rest
         }
         Frag<bf16> vv[4];
         tfrag4<t>(vt, vv);
-        Frag<bf16> pf = pfrag(pr, 0);
+        Frag<bf16> pf = pfrag<bf16>(pr, 0);
         mma(o[0], vv[0], pf);
         mma(o[1], vv[1], pf);
-        pf = pfrag(pr, 1);
+        pf = pfrag<bf16>(pr, 1);
         mma(o[0], vv[2], pf);
         mma(o[1], vv[3], pf);
       }

@@ -136,6 +136,14 @@ __device__ __forceinline__ int lane_id_here() {
   return l;
 }
 
+// B-operand fragment fi from 16 accumulator-layout values of one tile (the probabilities / score gradients of the attention kernels)
+template <typename T> __device__ __forceinline__ Frag<T> pfrag(const float (&p)[16], int fi) {
+  Frag<T> f;
+#pragma unroll
+  for (int j = 0; j < Frag<T>::EPL; ++j) f.v[j] = from_f32<T>(p[fi * Frag<T>::EPL + j]);
+  return f;
+}
+
 template <typename T> __device__ __forceinline__ void store4(T* p, f32x4 v) {
   typename Vec4<T>::type o;
   o[0] = from_f32<T>(v[0]); o[1] = from_f32<T>(v[1]); o[2] = from_f32<T>(v[2]); o[3] = from_f32<T>(v[3]);

@@ -17,6 +17,7 @@
 #include <vector>
 #include "../../include/rgbnm.h"
 #include "internal.h"
+#include "lds_common.h"
 #include "philox.h"
 
 namespace {
@@ -415,15 +416,12 @@ template <typename T> __device__ __forceinline__ Frag<T> gather_frag(const T* ba
   return f;
 }
 
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 // ds_read_b64_tr_b16: within each 16-lane group, lane i supplies the address of 4 contiguous 16-bit elements (row i>>2 of a
 // 4 x 16 block, columns 4*(i&3)..+3) and receives column i of that block (4 rows).  With tiles stored in their
 // natural [token][feature] layout this hands every lane 4 tokens of ITS feature: two reads = one MFMA fragment
 // (8 reduction slots), instead of 8 strided 2-byte reads.  A and B fragments use the same token<->slot mapping.
 template <typename T>
 __device__ __forceinline__ typename Vec8<T>::type tr_pack(u32x2 lo, u32x2 hi) {
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
   return __builtin_bit_cast(typename Vec8<T>::type, v);
 }

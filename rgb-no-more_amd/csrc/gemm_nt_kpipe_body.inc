@@ -8,9 +8,6 @@ __device__ unsigned long long g_kp_prof[4096 * 4];
 #define KPROF(i) do { } while (0)
 #endif
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef const __attribute__((address_space(1))) void* glb_ptr;
-
 // Two geometries (this file is included twice by gemm_nt_kpipe.hip):
 //   kp7: 7 waves x 32 rows = 224-row panels, 3-stage ring (156 KB): ONE workgroup per CU, one image per workgroup at B = 256;
 //   kp8: 8 waves x 32 rows = 256-row panels, 2-stage ring (112 KB), plain epilogues: the SwinV2 row counts.
@@ -67,10 +64,6 @@ constexpr int TAB_RESERVE = rgbnm::GELU_TAB_RESERVE;
 constexpr bool TAB_PERSIST_OK = NSTAGE >= 3 && BM * CP * 2 + TAB_RESERVE <= (NSTAGE - 1) * STAGE;
 constexpr bool TAB_RESIDENT_OK = (SMEM + TAB_RESERVE) * (NWAVES <= 4 ? 2 : 1) <= 160 * 1024;   // image below the whole ring (kp8)
 
-
-__device__ __forceinline__ int fswz(int row) {
-  return (((row >> 1) & 1) << 2) | ((row >> 2) & 1) | (((row >> 3) & 1) << 1);
-}
 
 // The 24 MFMAs of one 64-wide k-tile with their fragment reads and this wave's DMA requests in a PINNED order
 // (sched_barrier after every step): all fragments of the first 16 k, then one MFMA at a time, behind it one fragment of the next

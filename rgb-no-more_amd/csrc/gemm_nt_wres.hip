@@ -15,11 +15,9 @@
 // ring with only 2 waves per CU was 2x slower (too few waves to overlap the phases).
 #include "common.h"
 #include "internal.h"
+#include "lds_common.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef const __attribute__((address_space(1))) void* glb_ptr;
 
 constexpr int K = 192;
 constexpr int ROWB = K * 2;                 // 384 B per row
@@ -43,12 +41,6 @@ struct WresArgs {
   int lda, ldw, ldc, ldr, ldc2;
   int M, N, ntiles, msplit, tiles_per_split;
 };
-
-__device__ __forceinline__ int fswz(int row) {
-  return (((row >> 1) & 1) << 2) | ((row >> 2) & 1) | (((row >> 3) & 1) << 1);
-}
-// physical 16-byte chunk (0..23) of logical chunk lc in `row` (an involution)
-__device__ __forceinline__ int pchunk(int lc, int row) { return (lc & ~7) | ((lc & 7) ^ fswz(row)); }
 
 #ifdef WRES_PROF
 __device__ unsigned long long g_wres_prof[320 * 8 * 32];

@@ -13,6 +13,7 @@
 #include "common.h"
 #include <string.h>
 #include "internal.h"
+#include "lds_common.h"
 #include "../../include/rgbnm.h"
 
 // Operand streams: TN_NT bit 0 = the dY slices (read by ONE workgroup, once) non-temporal (aux = 2 of global_load_lds), bit 1 = the
@@ -22,11 +23,6 @@
 #endif
 
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef const __attribute__((address_space(1))) void* glb_ptr;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TK = 64;                         // tokens per stage
 constexpr int A_ROW = 256, B_ROW = 384;        // bytes per token row (128 / 192 bf16 features)
@@ -65,11 +61,6 @@ struct TnGroup {
   unsigned char unit_job[256], unit_tile[256];
 };
 
-__device__ __forceinline__ bf16x8 pack8(u32x2 lo, u32x2 hi) {
-  u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
 // all 8 transpose reads of chunk C (16 tokens) for this wave: 1 A fragment + 3 B fragments
 template <int C>
 __device__ __forceinline__ void tr_chunk(unsigned aA, unsigned aB0, unsigned aB1, unsigned aB2, Frag<bf16>& fa,
@@ -100,11 +91,6 @@ __device__ __forceinline__ void tr_chunk(unsigned aA, unsigned aB0, unsigned aB1
 // other): 1 = the same eight reads through the builtin with the next chunk's reads under the current MFMAs -- MEASURED +50 % on the
 // launch: the compiler drains vmcnt in front of every builtin LDS read that follows an LDS-DMA, which empties the ring;
 // 2 = asm reads without the wait, lgkmcnt counted by hand: +-0.5 % (the kernel waits for its operand stream, not for LDS).
-typedef bf16 bf16x4v __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4v* lds_b64_ptr;
-__device__ __forceinline__ u32x2 tr_read(const unsigned char* smem, unsigned off) {
-  return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b64_ptr)(smem + off)));
-}
 template <int C>
 __device__ __forceinline__ void tr_chunk_b(const unsigned char* sp, unsigned oA, unsigned oB0, unsigned oB1, unsigned oB2,
                                            Frag<bf16>& fa, Frag<bf16> (&fb)[3]) {

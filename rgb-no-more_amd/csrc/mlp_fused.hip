@@ -46,13 +46,11 @@
 #include "common.h"
 #include <mutex>
 #include "internal.h"
+#include "lds_common.h"
 #include "ln_bwd_rows.h"
 #include "../../include/rgbnm.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef const __attribute__((address_space(1))) void* glb_ptr;
 
 constexpr int E = 192, H = 768, CH = 64, NCHUNK = H / CH;
 constexpr int NCW = 7, NTHREADS = 64 * (NCW + 1), CTHREADS = 64 * NCW, BM = 32 * NCW;   // 224 panel rows
@@ -91,11 +89,6 @@ struct MlpArgs {
   unsigned kneg, kpos, klo, koff, ksgn;    // packed-key constants of the table window
   const float* gamma; const float* beta; bf16* Y2; float* mean_o; float* rstd_o; float eps; int ldy2;   // gamma == null: no LN
 };
-
-__device__ __forceinline__ int fswz(int row) {
-  return (((row >> 1) & 1) << 2) | ((row >> 2) & 1) | (((row >> 3) & 1) << 1);
-}
-__device__ __forceinline__ int pchunk(int lc, int row) { return (lc & ~7) | ((lc & 7) ^ fswz(row)); }
 
 // x_out = acc2 + b2 + R [, LayerNorm of x_out]: the arithmetic of gemm_nt_kpipe's EPI_RES_LN (same bits as ln_fwd_kernel).
 // Called by the compute waves only (the DMA wave has ended); uses the weight ring as the staging tile.
@@ -213,7 +206,6 @@ __device__ unsigned long long g_mlp_trace[16 * 8 * 80];
 
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef bf16 bf16x2v __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 // TAB = false: the arithmetic GELU, fc1 bias resident, 32-row staging tiles (any panel height up to 224 rows).

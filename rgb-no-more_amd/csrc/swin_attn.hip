@@ -26,6 +26,7 @@
 #include <type_traits>
 #include "../../include/rgbnm.h"
 #include "internal.h"
+#include "lds_common.h"
 
 namespace {
 
@@ -48,7 +49,6 @@ constexpr int WS = 8, WT = 64, HD = 32;
 constexpr int RP = HD + 8;        // row-major tile pitch (elements): 16-byte aligned rows, staggered banks
 constexpr int TP = WT + 4;        // transposed tile pitch
 constexpr int BP = WT + 4;        // position-bias pitch in LDS (floats): float4 row reads and column reads both conflict free
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 template <typename T> struct WA {
   static constexpr int EPL = Frag<T>::EPL;
@@ -229,7 +229,6 @@ template <typename T> __device__ __forceinline__ Frag<T> tfrag(const T* img, int
 // (fixed g, G1) hands ds_read_b64_tr_b16 a 4-row x 16-column block -- lane (k, l3) points at row 4 g + k, columns
 // 16 G1 + 4 l3 .. +3 -- and gets back column 16 G1 + 4 k + l3 (= lane & 31) of rows 4 g .. 4 g + 3; the second read takes the
 // rows 8 further down (tfrag's `hi` half).
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 template <typename T> __device__ __forceinline__ unsigned tr_base(const T* tile, int lane) {
   const int g = lane >> 5, G1 = (lane >> 4) & 1, k = (lane >> 2) & 3, l3 = lane & 3;
   return (unsigned)(size_t)tile + (unsigned)((4 * g + k) * RP * 2 + (16 * G1 + 4 * l3) * 2);
@@ -254,12 +253,6 @@ __device__ __forceinline__ Frag<T> tok_frag(unsigned trb, const T* timg, int l31
   else return tfrag<T>(timg, l31, t, fi, g);
 }
 
-template <typename T> __device__ __forceinline__ Frag<T> pfrag(const float (&p)[16], int fi) {
-  Frag<T> f;
-#pragma unroll
-  for (int j = 0; j < Frag<T>::EPL; ++j) f.v[j] = from_f32<T>(p[fi * Frag<T>::EPL + j]);
-  return f;
-}
 template <typename T> __device__ __forceinline__ void put_row(T* tile, int row, const float (&v)[HD], float s) {
 #pragma unroll
   for (int d = 0; d < HD; d += 4) store4<T>(tile + row * RP + d, (f32x4){v[d] * s, v[d + 1] * s, v[d + 2] * s, v[d + 3] * s});

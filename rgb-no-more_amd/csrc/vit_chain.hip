@@ -32,19 +32,13 @@
 #include <string.h>
 #include <type_traits>
 #include "internal.h"
+#include "tile128.h"
 #include "../../include/rgbnm.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef const __attribute__((address_space(1))) void* glb_ptr;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef bf16 bf16x2v __attribute__((ext_vector_type(2)));
-
 constexpr int E = 192, HID = 768, HD = 64, HEADS = 3, NTOK = 196, NTILE = 7, NPAD = 224, INNER = HEADS * HD;
 constexpr int NCW = 7, NTHREADS = 64 * (NCW + 1);
-constexpr int ROWB = 128;
 constexpr int SLOT = 24576;                       // one 64 x 192 (or 192 x 64) bf16 weight chunk
 // ---- LDS, attention part of a block
 constexpr int A_SLOT0 = 0;                        // three chunk slots
@@ -104,114 +98,6 @@ struct ChainArgs {            // passed BY VALUE (kernel argument segment): noth
   unsigned kneg, kpos, klo, koff, ksgn;
 };
 
-__device__ __forceinline__ int fswz(int row) {
-  return (((row >> 1) & 1) << 2) | ((row >> 2) & 1) | (((row >> 3) & 1) << 1);
-}
-
-struct Geo {
-  int lane, l31, g, fl;
-  unsigned tr0;    // byte offset inside a [token][64] array of the (t=0, fi=0, dt=0, rd=0) transpose read (attention_v2.hip)
-};
-__device__ __forceinline__ Geo make_geo() {
-  Geo L;
-  L.lane = threadIdx.x & 63;
-  L.l31 = L.lane & 31;
-  L.g = L.lane >> 5;
-  L.fl = fswz(L.l31);
-  const int k = (L.lane >> 2) & 3, G1 = (L.lane >> 4) & 1, l3 = L.lane & 3;
-  const int pc = (2 * G1 + (l3 >> 1)) ^ (((k >> 1) << 2) | L.g);
-  L.tr0 = (unsigned)((4 * L.g + k) * ROWB + pc * 16 + 8 * (l3 & 1));
-  return L;
-}
-
-// The same from a lane id the optimiser cannot trace (common.h lane_id_here): every phase derives its per-lane constants anew, so
-// none of them is live -- or spilled -- across the register-heavy phases in between
-__device__ __forceinline__ Geo fresh_geo() {
-  Geo L;
-  L.lane = lane_id_here();
-  L.l31 = L.lane & 31;
-  L.g = L.lane >> 5;
-  L.fl = fswz(L.l31);
-  const int k = (L.lane >> 2) & 3, G1 = (L.lane >> 4) & 1, l3 = L.lane & 3;
-  const int pc = (2 * G1 + (l3 >> 1)) ^ (((k >> 1) << 2) | L.g);
-  L.tr0 = (unsigned)((4 * L.g + k) * ROWB + pc * 16 + 8 * (l3 & 1));
-  return L;
-}
-
-template <int T> struct TileLoop {
-  template <typename F> static __device__ __forceinline__ void run(F&& f) {
-    TileLoop<T - 1>::run(f);
-    f(std::integral_constant<int, T - 1>{});
-  }
-};
-template <> struct TileLoop<0> {
-  template <typename F> static __device__ __forceinline__ void run(F&&) {}
-};
-
-__device__ __forceinline__ bf16x8 pack8(u32x2 lo, u32x2 hi) {
-  u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-// Both fragments (FI = 0, 1) x both d tiles of key tile T of the V array (tokens as reduction axis): 8 transpose reads, one wait
-template <int T>
-__device__ __forceinline__ void tfrag4(unsigned a0, Frag<bf16> (&f)[4]) {
-  u32x2 r0, r1, r2, r3, r4, r5, r6, r7;
-  const unsigned a00 = a0, a01 = (a0 ^ 32u) + 1024u, a10 = a0 ^ 64u, a11 = (a0 ^ 96u) + 1024u;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %8 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %1, %9 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %2, %10 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %3, %11 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %4, %8 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %5, %9 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %6, %10 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %7, %11 offset:%13\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5), "=&v"(r6), "=&v"(r7)
-      : "v"(a00), "v"(a01), "v"(a10), "v"(a11), "i"(T * 4096), "i"(T * 4096 + 2048)
-      : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  f[0].v = pack8(r0, r1);   // fi=0, dt=0
-  f[1].v = pack8(r2, r3);   // fi=0, dt=1
-  f[2].v = pack8(r4, r5);   // fi=1, dt=0
-  f[3].v = pack8(r6, r7);   // fi=1, dt=1
-}
-// The same through the compiler's builtin: the reads are ordinary DS loads to the scheduler (they can be requested ahead and
-// waited for where they are used; the asm form above waits on the spot)
-typedef bf16 bf16x4v __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4v* lds_b64_ptr;
-__device__ __forceinline__ u32x2 tr_read(const unsigned char* smem, unsigned off) {
-  return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b64_ptr)(smem + off)));
-}
-template <int T>
-__device__ __forceinline__ void tfrag4_b(const unsigned char* smem, unsigned a0, Frag<bf16> (&f)[4]) {
-  const unsigned a00 = a0, a01 = (a0 ^ 32u) + 1024u, a10 = a0 ^ 64u, a11 = (a0 ^ 96u) + 1024u;
-  f[0].v = pack8(tr_read(smem, a00 + T * 4096), tr_read(smem, a01 + T * 4096));
-  f[1].v = pack8(tr_read(smem, a10 + T * 4096), tr_read(smem, a11 + T * 4096));
-  f[2].v = pack8(tr_read(smem, a00 + T * 4096 + 2048), tr_read(smem, a01 + T * 4096 + 2048));
-  f[3].v = pack8(tr_read(smem, a10 + T * 4096 + 2048), tr_read(smem, a11 + T * 4096 + 2048));
-}
-__device__ __forceinline__ Frag<bf16> pfrag(const float (&p)[16], int fi) {
-  Frag<bf16> f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) f.v[j] = (bf16)p[fi * 8 + j];
-  return f;
-}
-
-// A per-lane value the optimiser must treat as new: addresses derived from it are re-derived where they are used (one XOR / add
-// each) instead of being hoisted out of the block loop as invariants and spilled (common.h, lane_id_here)
-__device__ __forceinline__ unsigned opaque(unsigned v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-// workgroup barrier that the compiler may not move LDS / global accesses across (the builtin alone is "no memory")
-__device__ __forceinline__ void wg_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 // Global stores of the saved tensors: NON-TEMPORAL (`global_store_dwordx4 ... nt`).  Nobody reads them for a millisecond (the
 // backward), so they should not push the weight images and the next phases' lines out of L2: -3 % on this launch and -1.3 % on
 // the backward launch behind it (interleaved A/B; the same hint did nothing for the per-operation kernels of
@@ -232,23 +118,7 @@ __device__ __forceinline__ void gstore(P* ptr, const V& v) {
 #endif
 }
 
-// Between a wave's accesses to ITS OWN LDS tile (write the fragment layout, read row pieces back, overwrite with the next tile) no
-// wait is needed: the LDS executes one wave's DS instructions in order, and the compiler counts lgkmcnt for the registers that are
-// used.  What must not happen is the compiler reordering the accesses (differently typed pointers): a compiler-only fence.  The
-// drains that stood here cost two LDS round trips per stored tile (~50 tiles per block and wave).  -DX_LDSWAIT restores them.
-#ifdef X_LDSWAIT
-__device__ __forceinline__ void own_tile_fence() { wait_lds(); }
-#else
-__device__ __forceinline__ void own_tile_fence() { asm volatile("" ::: "memory"); }
-#endif
-
-// ---- DMA wave helpers: linear 1 KB pieces
-template <int NKB>
-__device__ __forceinline__ void dma_linear(const unsigned char* src, unsigned char* dst, int lane) {
-#pragma unroll
-  for (int i = 0; i < NKB; ++i)
-    __builtin_amdgcn_global_load_lds((glb_ptr)(src + i * 1024 + lane * 16), (lds_ptr)(dst + i * 1024), 16, 0, 0);
-}
+// ---- DMA wave helpers (linear 1 KB pieces: lds_common.h dma_linear)
 __device__ __forceinline__ void dma_f32x192(const float* src, unsigned char* dst, int lane) {
 #pragma unroll
   for (int i = 0; i < 3; ++i)
@@ -261,13 +131,6 @@ __device__ __forceinline__ void dma_f32x192(const float* src, unsigned char* dst
 struct Rows { u32x4 v[12]; };
 __device__ __forceinline__ float bf_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
 __device__ __forceinline__ float bf_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-__device__ __forceinline__ unsigned pack2(float a, float b) {       // two fp32 -> bf16 pair (round to nearest even), a in the low half
-  const bf16x2v v = {(bf16)a, (bf16)b};
-  unsigned r = __builtin_bit_cast(unsigned, v);
-  asm volatile("" : "+v"(r));     // packed HERE: the optimiser otherwise sinks the conversion to the (conditional) use and keeps the fp32 pair
-  return r;
-}
-__device__ __forceinline__ bf16x8 as_bf16x8(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
 
 __device__ __forceinline__ void ln_stats(const Rows& x, float& mu, float& rs, float eps) {
   float s0 = 0.f, s1 = 0.f;
@@ -773,10 +636,10 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
           }
           Frag<bf16> vv[4];
           tfrag4<t>(vt, vv);
-          Frag<bf16> pf = pfrag(pr, 0);
+          Frag<bf16> pf = pfrag<bf16>(pr, 0);
           mma(o[0], vv[0], pf);
           mma(o[1], vv[1], pf);
-          pf = pfrag(pr, 1);
+          pf = pfrag<bf16>(pr, 1);
           mma(o[0], vv[2], pf);
           mma(o[1], vv[3], pf);
         });
@@ -813,10 +676,10 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
               if (t * 32 + 32 > NTOK && t * 32 + acc_row(r, L.lane) >= NTOK) pr[r] = 0.f;
               sum += pr[r];
             }
-            Frag<bf16> pf = pfrag(pr, 0);
+            Frag<bf16> pf = pfrag<bf16>(pr, 0);
             mma(o[0], vv[0], pf);
             mma(o[1], vv[1], pf);
-            pf = pfrag(pr, 1);
+            pf = pfrag<bf16>(pr, 1);
             mma(o[0], vv[2], pf);
             mma(o[1], vv[3], pf);
             __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);

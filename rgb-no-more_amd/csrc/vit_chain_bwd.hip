@@ -25,19 +25,14 @@
 #include <type_traits>
 #include "internal.h"
 #include "ln_bwd_rows.h"
+#include "tile128.h"
 #include "../../include/rgbnm.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef const __attribute__((address_space(1))) void* glb_ptr;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef bf16 bf16x2v __attribute__((ext_vector_type(2)));
-
 constexpr int E = 192, HID = 768, HD = 64, HEADS = 3, NTOK = 196, NTILE = 7, NPAD = 224, INNER = HEADS * HD, LDQ = 3 * INNER;
 constexpr int NCW = 7, NTHREADS = 64 * (NCW + 1), CTHREADS = 64 * NCW, BM = 32 * NCW;
-constexpr int ROWB = 128, ARR = NPAD * ROWB, SLOT = 24576, STAGE = 2 * SLOT, CH = 64, NCHUNK = HID / CH;
+constexpr int ARR = NPAD * ROWB, SLOT = 24576, STAGE = 2 * SLOT, CH = 64, NCHUNK = HID / CH;
 constexpr int CP = E + 4;                           // pitch (elements) of the LayerNorm-backward staging tile
 constexpr int SMEM = 163840;
 #ifndef PIPE_P
@@ -61,7 +56,6 @@ constexpr int P_SLOT0 = 132096, P_SLOT1 = 0, P_TILES = 98304;     // chunks 0, 2
 static_assert(P_SLOT0 + SLOT <= SMEM && P_TILES + NCW * TILE <= P_SLOT0, "LDS");
 // ---- A: the layout of attn3_bwd_kernel
 constexpr int A_Q = 0, A_K = ARR, A_V = 2 * ARR, A_G = 3 * ARR, A_L2 = 4 * ARR, A_D = A_L2 + NPAD * 4, A_STG = A_D + NPAD * 4;
-constexpr int STG_PITCH = 144, STG_WAVE = 32 * STG_PITCH;
 constexpr int A_SIDE = A_STG + NCW * STG_WAVE;      // 1 KB per wave: rows 0..7 of the wave's own next Q tile (see load_own_q)
 static_assert(A_SIDE + NCW * 1024 <= SMEM, "LDS");
 // ---- X: three weight slots | three sets of d(qkv) row tiles
@@ -86,136 +80,10 @@ struct BwdArgs {              // passed BY VALUE (kernel argument segment): noth
   float scale;
 };
 
-__device__ __forceinline__ int fswz(int row) {
-  return (((row >> 1) & 1) << 2) | ((row >> 2) & 1) | (((row >> 3) & 1) << 1);
-}
-struct Geo {
-  int lane, l31, g, fl;
-  unsigned tr0;
-};
-__device__ __forceinline__ Geo make_geo() {
-  Geo L;
-  L.lane = threadIdx.x & 63;
-  L.l31 = L.lane & 31;
-  L.g = L.lane >> 5;
-  L.fl = fswz(L.l31);
-  const int k = (L.lane >> 2) & 3, G1 = (L.lane >> 4) & 1, l3 = L.lane & 3;
-  const int pc = (2 * G1 + (l3 >> 1)) ^ (((k >> 1) << 2) | L.g);
-  L.tr0 = (unsigned)((4 * L.g + k) * ROWB + pc * 16 + 8 * (l3 & 1));
-  return L;
-}
-// The same from a lane id the optimiser cannot trace (common.h lane_id_here): every phase derives its per-lane constants anew, so
-// none of them is live -- or spilled -- across the register-heavy phases in between
-__device__ __forceinline__ Geo fresh_geo() {
-  Geo L;
-  L.lane = lane_id_here();
-  L.l31 = L.lane & 31;
-  L.g = L.lane >> 5;
-  L.fl = fswz(L.l31);
-  const int k = (L.lane >> 2) & 3, G1 = (L.lane >> 4) & 1, l3 = L.lane & 3;
-  const int pc = (2 * G1 + (l3 >> 1)) ^ (((k >> 1) << 2) | L.g);
-  L.tr0 = (unsigned)((4 * L.g + k) * ROWB + pc * 16 + 8 * (l3 & 1));
-  return L;
-}
-template <int T> struct TileLoop {
-  template <typename F> static __device__ __forceinline__ void run(F&& f) {
-    TileLoop<T - 1>::run(f);
-    f(std::integral_constant<int, T - 1>{});
-  }
-};
-template <> struct TileLoop<0> {
-  template <typename F> static __device__ __forceinline__ void run(F&&) {}
-};
-__device__ __forceinline__ bf16x8 pack8(u32x2 lo, u32x2 hi) {
-  u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-template <int T>
-__device__ __forceinline__ void tfrag4(unsigned a0, Frag<bf16> (&f)[4]) {
-  u32x2 r0, r1, r2, r3, r4, r5, r6, r7;
-  const unsigned a00 = a0, a01 = (a0 ^ 32u) + 1024u, a10 = a0 ^ 64u, a11 = (a0 ^ 96u) + 1024u;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %8 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %1, %9 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %2, %10 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %3, %11 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %4, %8 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %5, %9 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %6, %10 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %7, %11 offset:%13\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5), "=&v"(r6), "=&v"(r7)
-      : "v"(a00), "v"(a01), "v"(a10), "v"(a11), "i"(T * 4096), "i"(T * 4096 + 2048)
-      : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  f[0].v = pack8(r0, r1);
-  f[1].v = pack8(r2, r3);
-  f[2].v = pack8(r4, r5);
-  f[3].v = pack8(r6, r7);
-}
-__device__ __forceinline__ Frag<bf16> pfrag(const float (&p)[16], int fi) {
-  Frag<bf16> f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) f.v[j] = (bf16)p[fi * 8 + j];
-  return f;
-}
-__device__ __forceinline__ Frag<bf16> rowfrag_x(const unsigned char* arr, unsigned rb, int t, int c) {
-  Frag<bf16> f;
-  f.v = *reinterpret_cast<const bf16x8*>(arr + (rb ^ (unsigned)(c << 5)) + t * 32 * ROWB);
-  return f;
-}
-// The eight MFMAs of one 32-row tile in the attention phases (scores and their gradient: two accumulators, K = 64 in four steps)
-// with their eight row fragments in a PINNED order: four fragments ahead, every MFMA followed by the read of the fragment two steps
-// on (into registers an earlier MFMA has read -- the sixteen the transposed fragments of the tile's second half take afterwards).
-// Left alone the compiler emits read - wait - MFMA eight times with ONE fragment buffer: an exposed LDS latency per MFMA, 336 of
-// them per block and wave.  XB_ROWPIPE=0: the plain loop (experiments).  Same order per accumulator: same bits.
+// the attention phases' row_pair_mma (tile128.h) in its pinned order; XB_ROWPIPE=0: the plain loop (experiments)
 #ifndef XB_ROWPIPE
 #define XB_ROWPIPE 1
 #endif
-__device__ __forceinline__ void row_pair_mma(f32x16& sa, f32x16& da, const unsigned char* arrS, const unsigned char* arrD, unsigned rb,
-                                             int t, const Frag<bf16> (&xs)[4], const Frag<bf16> (&xd)[4]) {
-#if XB_ROWPIPE
-#define XB_SB __builtin_amdgcn_sched_barrier(0)
-  Frag<bf16> fs[4], fd[4];
-  XB_SB;
-  fs[0] = rowfrag_x(arrS, rb, t, 0);
-  fd[0] = rowfrag_x(arrD, rb, t, 0);
-  fs[1] = rowfrag_x(arrS, rb, t, 1);
-  fd[1] = rowfrag_x(arrD, rb, t, 1);
-  XB_SB;
-  mma(sa, fs[0], xs[0]); XB_SB;
-  fs[2] = rowfrag_x(arrS, rb, t, 2); XB_SB;
-  mma(da, fd[0], xd[0]); XB_SB;
-  fd[2] = rowfrag_x(arrD, rb, t, 2); XB_SB;
-  mma(sa, fs[1], xs[1]); XB_SB;
-  fs[3] = rowfrag_x(arrS, rb, t, 3); XB_SB;
-  mma(da, fd[1], xd[1]); XB_SB;
-  fd[3] = rowfrag_x(arrD, rb, t, 3); XB_SB;
-  mma(sa, fs[2], xs[2]);
-  mma(da, fd[2], xd[2]);
-  mma(sa, fs[3], xs[3]);
-  mma(da, fd[3], xd[3]);
-  XB_SB;
-#undef XB_SB
-#else
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    mma(sa, rowfrag_x(arrS, rb, t, c), xs[c]);
-    mma(da, rowfrag_x(arrD, rb, t, c), xd[c]);
-  }
-#endif
-}
-__device__ __forceinline__ unsigned opaque(unsigned v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-__device__ __forceinline__ void wg_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 // Global stores: XB_NT bit 0 = du (read again only by the weight-gradient launch) non-temporal, bit 1 = the gradient tiles the DMA
 // wave writes (d(q, k, v): read back by phase X of the same workgroup), bit 2 = d(attention output) tiles (read back by phase A)
 #ifndef XB_NT
@@ -225,6 +93,7 @@ __device__ __forceinline__ void wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)"
 #ifndef XB_NTLD
 #define XB_NTLD 0
 #endif
+constexpr int A_AUX = (XB_NTLD & 2) ? 2 : 0;
 template <bool NT, typename V, typename P>
 __device__ __forceinline__ void gstore(P* ptr, const V& v) {
 #ifdef XB_NOSTORE     // (experiments only, wrong gradients downstream: the kernel without the stores this helper issues)
@@ -235,40 +104,8 @@ __device__ __forceinline__ void gstore(P* ptr, const V& v) {
   else *reinterpret_cast<V*>(ptr) = v;
 }
 
-// Between a wave's accesses to ITS OWN LDS tile (write the fragment layout, read row pieces back, overwrite with the next tile) no
-// wait is needed: the LDS executes one wave's DS instructions in order, and the compiler counts lgkmcnt for the registers that are
-// used.  What must not happen is the compiler reordering the accesses (differently typed pointers): a compiler-only fence.  The
-// drains that stood here cost two LDS round trips per stored tile (~50 tiles per block and wave).  -DX_LDSWAIT restores them.
-#ifdef X_LDSWAIT
-__device__ __forceinline__ void own_tile_fence() { wait_lds(); }
-#else
-__device__ __forceinline__ void own_tile_fence() { asm volatile("" ::: "memory"); }
-#endif
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  const bf16x2v v = {(bf16)a, (bf16)b};
-  unsigned r = __builtin_bit_cast(unsigned, v);
-  asm volatile("" : "+v"(r));
-  return r;
-}
-__device__ __forceinline__ bf16x8 as_bf16x8(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
 struct Rows { u32x4 v[12]; };      // 12 operand fragments: features 16 c + 8 g + (0..7) of the lane's token (vit_chain.hip)
 
-template <int NKB>
-__device__ __forceinline__ void dma_linear(const unsigned char* src, unsigned char* dst, int lane) {
-#pragma unroll
-  for (int i = 0; i < NKB; ++i)
-    __builtin_amdgcn_global_load_lds((glb_ptr)(src + i * 1024 + lane * 16), (lds_ptr)(dst + i * 1024), 16, 0, 0);
-}
-// [N][64] bf16 matrix (row stride ld) -> LDS array, chunk q of row r at q ^ fswz(r): 28 pieces of 1 KB; rows >= N repeat row N - 1
-__device__ __forceinline__ void dma_matrix_all(const bf16* __restrict__ src, int ld, unsigned char* dst, int lane) {
-#pragma unroll 4
-  for (int i = 0; i < 28; ++i) {
-    const int row = 8 * i + (lane >> 3), pc = lane & 7;
-    const int lc = pc ^ fswz(row);
-    const int srow = row < NTOK ? row : NTOK - 1;
-    __builtin_amdgcn_global_load_lds((glb_ptr)(src + (size_t)srow * ld + lc * 8), (lds_ptr)(dst + i * 1024), 16, 0, (XB_NTLD & 2) ? 2 : 0);
-  }
-}
 // the seven waves' own 32 x 64 pieces of a [N][ld] matrix (columns c0 .. c0 + 63) -> row tiles, chunk q of row r at q ^ (r & 7)
 __device__ __forceinline__ void dma_row_tiles(const bf16* __restrict__ src, int ld, unsigned char* dst, int lane) {
 #pragma unroll 4
@@ -350,54 +187,8 @@ __device__ __forceinline__ void gemm_k192x2(f32x16& a0, f32x16& a1, const unsign
   for (int i = 0; i < DEPTH; ++i) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
   __builtin_amdgcn_sched_barrier(0);
 }
-// transpose reads through the compiler's builtin: ordinary DS loads to the scheduler (requested ahead, waited for at the use)
-typedef bf16 bf16x4v __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4v* lds_b64_ptr;
-__device__ __forceinline__ u32x2 tr_read(const unsigned char* smem, unsigned off) {
-  return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b64_ptr)(smem + off)));
-}
-template <int T>
-__device__ __forceinline__ void tfrag4_b(const unsigned char* smem, unsigned a0, Frag<bf16> (&f)[4]) {
-  const unsigned a00 = a0, a01 = (a0 ^ 32u) + 1024u, a10 = a0 ^ 64u, a11 = (a0 ^ 96u) + 1024u;
-  f[0].v = pack8(tr_read(smem, a00 + T * 4096), tr_read(smem, a01 + T * 4096));
-  f[1].v = pack8(tr_read(smem, a10 + T * 4096), tr_read(smem, a11 + T * 4096));
-  f[2].v = pack8(tr_read(smem, a00 + T * 4096 + 2048), tr_read(smem, a01 + T * 4096 + 2048));
-  f[3].v = pack8(tr_read(smem, a10 + T * 4096 + 2048), tr_read(smem, a11 + T * 4096 + 2048));
-}
-
-// ---- gradient tiles of the attention backward (attention_v2.hip)
-__device__ __forceinline__ void tile_park_private(unsigned char* stg, const f32x16 (&acc)[2], float mul, const Geo& L) {
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int rq = 0; rq < 4; ++rq) {
-      f32x4 v = {acc[dt][rq * 4 + 0], acc[dt][rq * 4 + 1], acc[dt][rq * 4 + 2], acc[dt][rq * 4 + 3]};
-      store4<bf16>(reinterpret_cast<bf16*>(stg + L.l31 * STG_PITCH) + dt * 32 + rq * 8 + L.g * 4, v * mul);
-    }
-}
-__device__ __forceinline__ void tile_park_rows(unsigned char* arr, int w, const f32x16 (&acc)[2], float mul) {
-  const int ln = lane_id_here();
-  const unsigned off0 = (unsigned)((w * 32 + (ln & 31)) * ROWB + ((ln & 7) << 4) + (ln >> 5) * 8);
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int rq = 0; rq < 4; ++rq) {
-      f32x4 v = {acc[dt][rq * 4 + 0], acc[dt][rq * 4 + 1], acc[dt][rq * 4 + 2], acc[dt][rq * 4 + 3]};
-      store4<bf16>(reinterpret_cast<bf16*>(arr + (off0 ^ (unsigned)((dt * 4 + rq) << 4))), v * mul);
-    }
-}
-template <bool PRIVATE>
-__device__ __forceinline__ void tiles_read(const unsigned char* src, int lane, u32x4 (&v)[NTILE][4]) {
-  const int rl = lane >> 3, seg = lane & 7;
-#pragma unroll
-  for (int wv = 0; wv < NTILE; ++wv)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = i * 8 + rl;
-      v[wv][i] = PRIVATE ? *reinterpret_cast<const u32x4*>(src + wv * STG_WAVE + r * STG_PITCH + seg * 16)
-                         : *reinterpret_cast<const u32x4*>(src + (wv * 32 + r) * ROWB + ((seg ^ (r & 7)) << 4));
-    }
-}
+// ---- gradient tiles of the attention backward: parked and read back by tile128.h; sibling of attention_v2.hip tiles_write, which
+// has a run-time token count and plain stores (here: NTOK, and the XB_NT / XB_NOSTORE switches of gstore)
 __device__ __forceinline__ void tiles_write(const u32x4 (&v)[NTILE][4], bf16* __restrict__ g0, size_t ld, int lane) {
   const int rl = lane >> 3, seg = lane & 7;
 #pragma unroll
@@ -515,11 +306,11 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
       bf16* dq0 = b.dqkv + (size_t)img * NTOK * LDQ;
       const unsigned char* stg0 = smem + A_STG;
       auto issue_kv = [&](int h) {
-        dma_matrix_all(qkv0 + INNER + h * HD, LDQ, smem + A_K, lane);
-        dma_matrix_all(qkv0 + 2 * INNER + h * HD, LDQ, smem + A_V, lane);
+        dma_matrix_all<A_AUX>(qkv0 + INNER + h * HD, LDQ, NTOK, smem + A_K, lane);
+        dma_matrix_all<A_AUX>(qkv0 + 2 * INNER + h * HD, LDQ, NTOK, smem + A_V, lane);
       };
-      auto issue_q = [&](int h) { dma_matrix_all(qkv0 + h * HD, LDQ, smem + A_Q, lane); };
-      auto issue_g = [&](int h) { dma_matrix_all(do0 + h * HD, INNER, smem + A_G, lane); };
+      auto issue_q = [&](int h) { dma_matrix_all<A_AUX>(qkv0 + h * HD, LDQ, NTOK, smem + A_Q, lane); };
+      auto issue_g = [&](int h) { dma_matrix_all<A_AUX>(do0 + h * HD, INNER, NTOK, smem + A_G, lane); };
       const unsigned char* xw = wimg + (size_t)NCHUNK * STAGE + 3 * SLOT;                 // the nine qkv chunks
       auto issue_xt = [&](int j) { dma_row_tiles(dq0 + j * 64, LDQ, smem + X_TILES + (j % 3) * X_TSET, lane); };
       wait_vm<0>();                                       // chunk 0 (fetched during the epilogue) has landed long ago
@@ -544,7 +335,7 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
           wait_vm<0>();                                   // Q, dO landed (and the previous head's stores are done)
           BAR(B_A + 1 + 4 * h);                           // mid
           u32x4 tq[NTILE][4];
-          tiles_read<true>(stg0, lane, tq);               // dQ tiles
+          tiles_read<true>(stg0, NTOK, lane, tq);         // dQ tiles
           wait_lds();
           BAR(B_A + 2 + 4 * h);                           // mid2
           tiles_write(tq, g0, LDQ, lane);
@@ -555,11 +346,11 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
           }
           wait_vm<0>();
           BAR(B_A + 3 + 4 * h);                           // end
-          tiles_read<true>(stg0, lane, tq);               // dK tiles
+          tiles_read<true>(stg0, NTOK, lane, tq);         // dK tiles
           wait_lds();
           BAR(B_A + 4 + 4 * h);                           // end2
           tiles_write(tq, g0 + INNER, LDQ, lane);
-          tiles_read<false>(smem + A_G, lane, tq);        // dV
+          tiles_read<false>(smem + A_G, NTOK, lane, tq);  // dV
           wait_lds();
           if (h + 1 < HEADS) {
             issue_q(h + 1);
@@ -916,7 +707,7 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
             f32x16 sa, da;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { sa[r] = 0.f; da[r] = 0.f; }
-            row_pair_mma(sa, da, Ks, Vs, rb, t, qf, gf);
+            row_pair_mma<XB_ROWPIPE != 0>(sa, da, Ks, Vs, rb, t, qf, gf);
             float ds[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -930,10 +721,10 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
             }
             Frag<bf16> kk[4];
             tfrag4<t>(kt, kk);
-            Frag<bf16> sf = pfrag(ds, 0);
+            Frag<bf16> sf = pfrag<bf16>(ds, 0);
             mma(dq[0], kk[0], sf);
             mma(dq[1], kk[1], sf);
-            sf = pfrag(ds, 1);
+            sf = pfrag<bf16>(ds, 1);
             mma(dq[0], kk[2], sf);
             mma(dq[1], kk[3], sf);
           });
@@ -962,7 +753,7 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
             f32x16 sa, da;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { sa[r] = 0.f; da[r] = 0.f; }
-            row_pair_mma(sa, da, Qs, Gs, rb, t, kf, vf);
+            row_pair_mma<XB_ROWPIPE != 0>(sa, da, Qs, Gs, rb, t, kf, vf);
             float pp[16], ds[16];
 #pragma unroll
             for (int q4 = 0; q4 < 4; ++q4) {
@@ -983,17 +774,17 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
             }
             Frag<bf16> gg[4];
             tfrag4<t>(gt_, gg);
-            Frag<bf16> f = pfrag(pp, 0);
+            Frag<bf16> f = pfrag<bf16>(pp, 0);
             mma(dv[0], gg[0], f);
             mma(dv[1], gg[1], f);
-            f = pfrag(pp, 1);
+            f = pfrag<bf16>(pp, 1);
             mma(dv[0], gg[2], f);
             mma(dv[1], gg[3], f);
             tfrag4<t>(qt_, gg);
-            f = pfrag(ds, 0);
+            f = pfrag<bf16>(ds, 0);
             mma(dk[0], gg[0], f);
             mma(dk[1], gg[1], f);
-            f = pfrag(ds, 1);
+            f = pfrag<bf16>(ds, 1);
             mma(dk[0], gg[2], f);
             mma(dk[1], gg[3], f);
           });
