@@ -231,9 +231,11 @@ int rgbnm_attention_bwd(int dtype, const void* qkv, const void* out, const void*
 int rgbnm_subblock_embed(int in_dtype, int out_dtype, const void* y, const void* cbcr, const float* conv16,
                          void* feat, int B, int Hb, int Wb, int transpose_a, void* stream);
 /* The same on a batch that RandomMixup_DCT (utils/cls_transforms.py:163-176) has NOT been applied to yet: lam_dev (device, two
- * floats, may be NULL = no mixing) mixes image b with image b - 1 (mod B) as the values are loaded, rounded to in_dtype exactly
- * as rgbnm_mixup(in_dtype -> in_dtype) stores them -- the same bits as rgbnm_mixup followed by rgbnm_subblock_embed without the
- * mixed batch ever existing in memory (two launches and a round trip of the batch less per step). */
+ * floats, may be NULL = no mixing) mixes image b with image b - 1 (mod B) as the values are loaded:
+ *   x[b] <- round_in_dtype( fma(x[b - 1], lam[1], x[b] * lam[0]) )       (fp32 product, fp32 fma, ONE rounding to in_dtype)
+ * for every in_dtype the entry accepts, fp16 included.  For fp32 and bf16 input that is what rgbnm_mixup(in_dtype -> in_dtype)
+ * stores (rgbnm_mixup itself does not take fp16): the same bits as rgbnm_mixup followed by rgbnm_subblock_embed without the mixed
+ * batch ever existing in memory (two launches and a round trip of the batch less per step). */
 int rgbnm_subblock_embed_mix(int in_dtype, int out_dtype, const void* y, const void* cbcr, const float* lam_dev, const float* conv16,
                              void* feat, int B, int Hb, int Wb, int transpose_a, void* stream);
 
@@ -313,7 +315,10 @@ int rgbnm_dct_augment_packed(const int16_t* Ypacked, const int16_t* Cpacked, con
  * ------------------------------------------------------------------------------------------- */
 /* CrossEntropyLoss (pipeline_utils.py:535) with soft [B,C] fp32 or hard int64 [B] targets (exactly one non-NULL).
  * loss[0] = mean over rows; dlogits (dtype dl_dtype, may be NULL) = d loss / d logits * grad_scale*B... see .hip:
- * dlogits = (softmax*sum(t) - t) * grad_scale, pass grad_scale = 1/B for the mean reduction. */
+ * dlogits = (softmax*sum(t) - t) * grad_scale, pass grad_scale = 1/B for the mean reduction.
+ * Hard labels must lie in [0, C): the kernels do not check them.  A label outside that range matches no class, so its row has
+ * target mass 0, loss row 0 and dlogits 0 (with mixing: the in-range partner alone counts) and no memory outside the row is
+ * touched.  That is the contract of all three entry families (checking on the host would cost the step a device sync). */
 int rgbnm_softxent(int dl_dtype, const float* logits, const float* soft_target, const long long* hard_target,
                    float* loss_rows, float* loss, void* dlogits, int B, int C, float grad_scale, void* stream);
 /* The same loss as one launch per direction (round 6).  _loss: loss_rows [B], row_stats [2B] (log-sum-exp, target mass per row)

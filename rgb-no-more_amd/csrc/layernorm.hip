@@ -403,7 +403,7 @@ int rgbnm_head_pool_fwd(int dtype, const void* x, const float* gamma, const floa
 int rgbnm_head_pool_bwd(int dtype, const void* dpooled, const void* x, const float* gamma, const float* mean,
                         const float* rstd, void* dx, float* dgamma, float* dbeta, int B, int N, int E, int accumulate,
                         void* workspace, size_t workspace_bytes, void* stream) {
-  if (!dpooled || !x || !gamma || !mean || !rstd || !dx || !dgamma || !dbeta || !workspace) return RGBNM_EINVAL;
+  if (!dpooled || !x || !gamma || !mean || !rstd || !dx || !dgamma || !dbeta || !workspace || B <= 0 || N <= 0) return RGBNM_EINVAL;
   if (workspace_bytes < (size_t)B * 2 * E * sizeof(float)) return RGBNM_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
