@@ -445,7 +445,10 @@ int rgbnm_vit_block_bwd_drop(const rgbnm_vit_cfg* cfg, const rgbnm_block_params*
  * wimg: the block's "chain image" -- its four weight matrices as they lie in LDS (rows permuted, 16-byte chunks swizzled,
  *   consumption order), rgbnm_chain_image_elems() bf16 elements, written per step by rgbnm_chain_gather(src = operand shadows,
  *   idx = constant int32 table built on the host: rgb-no-more_amd/chain.py documents the layout).
- * Returns RGBNM_OK, 1 when the configuration is not eligible (the caller runs the blocks one by one), or a negative error. */
+ * Returns RGBNM_OK, 1 when the configuration is not eligible (the caller runs the blocks one by one), or a negative error.
+ * Not eligible: anything but bf16, E = 192, 3 heads, N = 196, B >= 1, depth <= 12, or no GELU table on the device.  A NULL cfg /
+ * blocks / x0 or depth <= 0 is RGBNM_EINVAL.  Both are decided before anything is launched: the call has then touched no buffer
+ * (tests/test_block_edges.py), so the caller can run the per-operation entries on the same arguments. */
 typedef struct rgbnm_chain_block {
   const void* wimg;
   const float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *bqkv_perm, *bproj, *b1, *b2;
@@ -467,7 +470,9 @@ int rgbnm_vit_chain_fwd(const rgbnm_vit_cfg* cfg, const rgbnm_chain_block* block
  * then runs rgbnm_vit_block_bwd_dw per block (any order), which launches the four weight-gradient GEMMs and submits the
  * reductions exactly as rgbnm_vit_block_bwd does.  blocks: HOST array of `depth` (<= 12) rgbnm_chain_bwd_block (copied into the
  * kernel's argument segment); blk[i].dy must be blk[i + 1].dx for i < depth - 1.  wimg: the backward chain image (rgb-no-more_amd/chain.py, from the TRANSPOSED operand
- * shadows by rgbnm_chain_gather).  dattn: [B * 196, 192] scratch.  Returns RGBNM_OK, 1 = not eligible, negative = error. */
+ * shadows by rgbnm_chain_gather).  dattn: [B * 196, 192] scratch.  Returns RGBNM_OK, 1 = not eligible, negative = error; the
+ * same contract as rgbnm_vit_chain_fwd (it does not need the GELU table): 1 or RGBNM_EINVAL (NULL cfg / blocks / dattn, depth <= 0)
+ * means that nothing was launched and no buffer was touched. */
 typedef struct rgbnm_chain_bwd_block {
   const void* wimg;
   const float *ln1_g, *ln2_g;
