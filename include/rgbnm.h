@@ -421,7 +421,9 @@ int rgbnm_vit_block_bwd(const rgbnm_vit_cfg* cfg, const rgbnm_block_params* p, c
  * RGBNM_EPI_RES_DROP (site 2); no LayerNorm chaining, no fused MLP.  The backward regenerates the masks from the same seed:
  * dy_m = mask2(dy) feeds dW2 / db2 and d(gl), dxmid_m = mask0(d x_mid) feeds dWproj / dbproj and d(attn); the residual paths keep
  * the unmasked gradients.  dy_m / dxmid_m: caller-owned [M,E] buffers of the compute dtype (backward only), alive until the call
- * returns.  No mask is stored. */
+ * returns.  No mask is stored.
+ * Both entries check d before they enqueue anything: a NULL d, seed, dy_m or dxmid_m (backward), dy_m == dxmid_m, p outside [0, 1)
+ * or block < 0 return RGBNM_EINVAL, a short workspace RGBNM_EWORKSPACE, with no kernel launched. */
 typedef struct rgbnm_dropout {
   const void* seed;   /* device pointer to the step's 64-bit seed */
   float p;            /* [0, 1) */
@@ -563,9 +565,15 @@ typedef struct rgbnm_head_grads {
   float *dln_g, *dln_b, *dw1, *db1, *dw2, *db2;
 } rgbnm_head_grads;
 int rgbnm_head_fwd(const rgbnm_vit_cfg* cfg, const rgbnm_head_params* p, const rgbnm_head_acts* a, void* stream);
-/* dlogits [B,C] in cfg->dtype; da, dpooled: [B,E] scratch; dx [M,E] out. */
-/* Workspace that lets rgbnm_head_bwd keep its three sets of split partial sums side by side (needed when the call sits inside
- * a rgbnm_reduce_hold_begin / _end bracket; with less -- rgbnm_vit_workspace_ex -- they re-use one region, outside a bracket). */
+/* dlogits [B,C] in cfg->dtype; da, dpooled: [B,E] scratch; dx [M,E] out.
+ * n_classes: rgbnm_head_fwd takes any C >= 1; rgbnm_head_bwd reads dlogits as a GEMM operand of row pitch C and needs whole 16-byte
+ * rows, C % 8 == 0 in the 16-bit modes and C % 4 == 0 in fp32 -- any other C returns RGBNM_EINVAL before anything is launched
+ * (callers pad the head: plainvit.py _ncls_pad). */
+/* Workspace that lets rgbnm_head_bwd keep its three sets of split partial sums side by side (REQUIRED when the call sits inside
+ * a rgbnm_reduce_hold_begin / _end bracket: with less the call returns RGBNM_EWORKSPACE there and launches nothing, because the
+ * held reductions would read a region the later producers have overwritten; outside a bracket any workspace that holds the
+ * largest of the three regions -- rgbnm_gemm_tn_workspace(B, C, E), rgbnm_gemm_tn_workspace(B, E, E), B 2 E floats; also
+ * rgbnm_vit_workspace_ex where that is the smaller one -- is re-used by the three producers one after the other). */
 size_t rgbnm_head_bwd_workspace(const rgbnm_vit_cfg* cfg, int n_classes);
 int rgbnm_head_bwd(const rgbnm_vit_cfg* cfg, const rgbnm_head_params* p, const rgbnm_head_acts* a,
                    const rgbnm_head_grads* g, const void* dlogits, void* da, void* dpooled, void* dx, void* ws,

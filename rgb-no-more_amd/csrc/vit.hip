@@ -232,9 +232,13 @@ int rgbnm_vit_block_fwd(const rgbnm_vit_cfg* c, const rgbnm_block_params* p, con
   return rgbnm_vit_block_fwd_chain(c, p, a, 0, nullptr, nullptr, st);
 }
 
+// what every mask kernel of the block would refuse (philox.h drop_host_args), asked once in front of the first launch
+static bool drop_args_ok(const rgbnm_dropout* d) { return d->seed && d->p >= 0.f && d->p < 1.f && d->block >= 0; }
+
 int rgbnm_vit_block_fwd_drop(const rgbnm_vit_cfg* c, const rgbnm_block_params* p, const rgbnm_block_acts* a, const rgbnm_dropout* d,
                              void* st) {
   if (!c || !p || !a || !d) return RGBNM_EINVAL;
+  if (!drop_args_ok(d)) return RGBNM_EINVAL;      // before LN1 / qkv / attention are enqueued: a refusal launches nothing
   const int dt = c->dtype, M = c->B * c->N, E = c->E, I = c->heads * 64;
   TRY(rgbnm_layernorm_fwd(dt, a->x_in, p->ln1_g, p->ln1_b, a->xn1, a->mean1, a->rstd1, M, E, c->ln_eps, st));
   TRY(rgbnm_gemm_nt(dt, RGBNM_EPI_NONE, a->xn1, E, p->wqkv, E, a->qkv, 3 * I, p->bqkv_perm, 0, 0, 0, 0, 0, 0, M,
@@ -256,7 +260,7 @@ int rgbnm_vit_block_fwd_drop(const rgbnm_vit_cfg* c, const rgbnm_block_params* p
 static int block_bwd(const rgbnm_vit_cfg* c, const rgbnm_block_params* p, const rgbnm_block_acts* a, const rgbnm_block_grads* g,
                      const rgbnm_block_scratch* s, const rgbnm_dropout* d, const void* dy, void* dx, void* st) {
   if (!c || !p || !a || !g || !s || !dy || !dx) return RGBNM_EINVAL;
-  if (d && (!d->dy_m || !d->dxmid_m || d->dy_m == d->dxmid_m)) return RGBNM_EINVAL;
+  if (d && (!d->dy_m || !d->dxmid_m || d->dy_m == d->dxmid_m || !drop_args_ok(d))) return RGBNM_EINVAL;
   const int dt = c->dtype, M = c->B * c->N, E = c->E, I = c->heads * 64;
   size_t off[7];
   if (s->ws_bytes < block_ws_offsets(M, E, I, off)) return RGBNM_EWORKSPACE;
@@ -452,11 +456,16 @@ int rgbnm_head_bwd(const rgbnm_vit_cfg* c, const rgbnm_head_params* p, const rgb
                    size_t ws_bytes, void* st) {
   if (!c || !p || !a || !g || !dlogits || !da || !dpooled || !dx) return RGBNM_EINVAL;
   const int dt = c->dtype, E = c->E, C = p->n_classes, B = c->B;
+  // dlogits is a GEMM operand with C as its row pitch and, for da, its reduction length: whole 16-byte vectors (rgbnm.h)
+  if (C <= 0 || C % (dt == RGBNM_DT_F32 ? 4 : 8)) return RGBNM_EINVAL;
   // three split-sum producers: side by side when the workspace has room for all of them (rgbnm_head_bwd_workspace: required
   // inside a held-reduction bracket, where the partial sums live until rgbnm_reduce_hold_end), else one after the other in place
   const size_t s1 = (rgbnm_gemm_tn_workspace(B, C, E) + 255) & ~(size_t)255, s2 = (rgbnm_gemm_tn_workspace(B, E, E) + 255) & ~(size_t)255;
   const size_t s3 = (size_t)B * 2 * E * sizeof(float);
   const bool apart = ws_bytes >= s1 + s2 + s3;
+  // held reductions read the partial sums at rgbnm_reduce_hold_end: in a shared region the second and third producer would have
+  // overwritten the first one's by then
+  if (!apart && rgbnm_reduce_hold_active()) return RGBNM_EWORKSPACE;
   char* w1 = (char*)ws;
   char* w2 = apart ? w1 + s1 : w1;
   char* w3 = apart ? w2 + s2 : w1;

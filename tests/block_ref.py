@@ -279,20 +279,37 @@ def check_ln_fwd(worst, key, where, x, g, b, y, mean, rstd, B=None):
     return r
 
 
-def check_res(worst, key, where, a, w, b, res, got, inter, B=None):
-    """got = res + a w^T + b.  inter: the staged 16-bit epilogues round a w^T + b to the element type first."""
+def check_res(worst, key, where, a, w, b, res, got, inter, B=None, f=None):
+    """got = res + a w^T + b.  inter: the staged 16-bit epilogues round a w^T + b to the element type first.
+    f (fp64 [M, N], keep . scale of the dropout site, or None): got = res + f (a w^T + b), the terms of
+    tests/test_dropout_kernels.py nt_drop_case -- the mask multiplies the staged value (f inter) and the product is rounded to fp32
+    once more (gemm.hip epilogue, `drop_one`: v * d.scale in fp32): + 2 fp32 ulps of f pre."""
     pre, mag = linear(d64(a), d64(w), d64(b))
     extra = ulp(pre, got.dtype) if inter and got.dtype != F32 else None
+    if f is not None:
+        extra = 2 * ulp(f * pre, F32) + (f * extra if extra is not None else 0.0)
+        pre, mag = f * pre, f * mag
     _chk(worst, key, got, pre + d64(res), mag + d64(res).abs(), a.shape[1] * U, where, extra=extra, B=B, tile=(32, got.shape[1]))
 
 
-def check_gelu(worst, where, xn2, w1, b1, gl, u, B=None):
+def check_gelu(worst, where, xn2, w1, b1, gl, u, B=None, f=None):
+    """f (fp64 [M, 4 E], keep . scale of site 1, or None): gl = f gelu(pre), u = f gelu'(pre) with nt_drop_case's terms: every
+    term of the unmasked bound times f, and 2 more fp32 ulps of the result for the product with the scale."""
     pre, mag = linear(d64(xn2), d64(w1), d64(b1))
     tiny = float(pre.abs().min())
     assert tiny >= DENORMAL_FREE, f"{where}: a pre-activation of magnitude {tiny:.3g} (the table's documented exception)"
     up = ulp(pre, gl.dtype)
     K = xn2.shape[1]
     ref, ref2 = gelu64(pre), dgelu64(pre)
+    if f is not None:
+        if gl.dtype == F32:
+            up = 0.0                      # (nt_drop_case: the pre-activation is rounded to T in the 16-bit modes only)
+        ref, ref2 = f * ref, f * ref2
+        _chk(worst, "gl", gl, ref, 1.13 * f * mag, K * U, where, extra=f * (1.13 * up + 2.0 ** -22 * pre.abs()) + 4 * ulp(ref, F32),
+             B=B, tile=(32, 64))
+        _chk(worst, "u", u, ref2, 0.8 * f * mag, K * U, where, extra=f * (0.8 * up + 2.0 ** -21) + 4 * ulp(ref2, F32), B=B,
+             tile=(32, 64))
+        return pre
     _chk(worst, "gl", gl, ref, 1.13 * mag, K * U, where, extra=1.13 * up + 2.0 ** -22 * pre.abs() + 2 * ulp(ref, F32), B=B,
          tile=(32, 64))
     _chk(worst, "u", u, ref2, 0.8 * mag, K * U, where, extra=0.8 * up + 2.0 ** -21 + 2 * ulp(ref2, F32), B=B, tile=(32, 64))
@@ -307,9 +324,11 @@ def check_attn_fwd(worst, where, qkv, attn, lse, B, scale=SCALE):
     return r
 
 
-def check_block_fwd(worst, where, P, A, B, inter=False, nxt=None):
+def check_block_fwd(worst, where, P, A, B, inter=False, nxt=None, f=None):
     """Stages 1 - 7 (8 with nxt = (next block's parameters, its xn1 / mean1 / rstd1 dict)) of one block, each from the tensors
-    the run itself stored.  P, A: dicts of tensors on one device.  Returns what the regime assertions need."""
+    the run itself stored.  P, A: dicts of tensors on one device.  Returns what the regime assertions need.
+    f: None, or the dropout factors {0: [M, E], 1: [M, 4 E], 2: [M, E]} (fp64, keep . scale) of rgbnm_vit_block_fwd_drop."""
+    f = f or {}
     info = {}
     r = check_ln_fwd(worst, "xn1", where, A["x_in"], P["ln1_g"], P["ln1_b"], A["xn1"], A["mean1"], A["rstd1"], B)
     info["rstd1_max"] = float(r["rstd"].max())
@@ -319,10 +338,10 @@ def check_block_fwd(worst, where, P, A, B, inter=False, nxt=None):
     r = check_attn_fwd(worst, where, A["qkv"], A["attn"], A["lse"], B, 1.0 / math.sqrt(e))
     info["onehot_rows"] = int((r["pmax"] > 0.9).sum())
     del r, ref, mag
-    check_res(worst, "x_mid", where, A["attn"], P["wproj"], P["bproj"], A["x_in"], A["x_mid"], inter, B)
+    check_res(worst, "x_mid", where, A["attn"], P["wproj"], P["bproj"], A["x_in"], A["x_mid"], inter, B, f.get(0))
     check_ln_fwd(worst, "xn2", where, A["x_mid"], P["ln2_g"], P["ln2_b"], A["xn2"], A["mean2"], A["rstd2"], B)
-    info["pre"] = check_gelu(worst, where, A["xn2"], P["w1"], P["b1"], A["gl"], A["u"], B)
-    check_res(worst, "x_out", where, A["gl"], P["w2"], P["b2"], A["x_mid"], A["x_out"], inter, B)
+    info["pre"] = check_gelu(worst, where, A["xn2"], P["w1"], P["b1"], A["gl"], A["u"], B, f.get(1))
+    check_res(worst, "x_out", where, A["gl"], P["w2"], P["b2"], A["x_mid"], A["x_out"], inter, B, f.get(2))
     if nxt is not None:
         check_ln_fwd(worst, "next-xn1", where, A["x_out"], nxt[0]["ln1_g"], nxt[0]["ln1_b"], nxt[1]["xn1"], nxt[1]["mean1"],
                      nxt[1]["rstd1"], B)
@@ -352,8 +371,10 @@ def check_lnbwd_fused(worst, key, where, a, wt, x, mean, rstd, g, res, dx, part,
 
 def check_block_bwd(worst, where, P, A, G, B):
     """Backward stages 1 - 6a of one block on the fused forms (one-launch backward / per-operation fused path): G holds dy, du,
-    dx_mid, dattn (None: its scratch was reused), dqkv, dx and part2 / part1 ([B, 2, E], None: not checked here)."""
-    dy = d64(G["dy"])
+    dx_mid, dattn (None: its scratch was reused), dqkv, dx and part2 / part1 ([B, 2, E], None: not checked here).
+    The dropout backward (vit.hip block_bwd with d) adds dy_m and dxmid_m: the GEMM operands of du and dattn; the two residuals
+    stay G["dy"] and G["dx_mid"]."""
+    dy = d64(G["dy_m"] if G.get("dy_m") is not None else G["dy"])
     pre, mag = dy @ d64(P["w2"]), dy.abs() @ d64(P["w2"]).abs()
     uu = d64(A["u"])
     dt, e, inner = G["du"].dtype, dy.shape[1], A["attn"].shape[1]
@@ -363,7 +384,9 @@ def check_block_bwd(worst, where, P, A, G, B):
     r2 = check_lnbwd_fused(worst, "dx_mid", where, G["du"], P["w1"], A["x_mid"], A["mean2"], A["rstd2"], P["ln2_g"], G["dy"],
                            G["dx_mid"], G.get("part2"), B)
     r2 = {k: v for k, v in r2.items() if k.startswith(("dg", "db"))}
-    ref, mag = d64(G["dx_mid"]) @ d64(P["wproj"]), d64(G["dx_mid"]).abs() @ d64(P["wproj"]).abs()
+    dxm = d64(G["dxmid_m"] if G.get("dxmid_m") is not None else G["dx_mid"])
+    ref, mag = dxm @ d64(P["wproj"]), dxm.abs() @ d64(P["wproj"]).abs()
+    del dxm
     delta = None
     if G.get("dattn") is not None:
         _chk(worst, "dattn", G["dattn"], ref, mag, e * U, where, B=B, tile=(32, 64))
@@ -399,8 +422,10 @@ def check_block_dw(worst, where, A, G, W, B):
     parameter gradients are the sums over images of the STORED part2 / part1."""
     M = B * NTOK
     cu = (M + 2) * U
-    for key, dyk, xk, perm in (("dw2", G["dy"], A["gl"], False), ("dw1", G["du"], A["xn2"], False),
-                               ("dwproj", G["dx_mid"], A["attn"], False), ("dwqkv", G["dqkv"], A["xn1"], True)):
+    dyg = G["dy_m"] if G.get("dy_m") is not None else G["dy"]                    # (the dropout backward's masked operands)
+    dxmg = G["dxmid_m"] if G.get("dxmid_m") is not None else G["dx_mid"]
+    for key, dyk, xk, perm in (("dw2", dyg, A["gl"], False), ("dw1", G["du"], A["xn2"], False),
+                               ("dwproj", dxmg, A["attn"], False), ("dwqkv", G["dqkv"], A["xn1"], True)):
         ref, mag, rb, mb = tn(d64(dyk), d64(xk))
         if perm:
             dst = qkv_rows(ref.shape[0] // 192).to(ref.device)
@@ -488,21 +513,25 @@ def emu_lnbwd(a, wt, x, mean, rstd, g, res, B, rounded=True):
     return _b(dx), part
 
 
+def emu_attn_bwd(A, dattn, B, e):
+    """d(qkv) from the stored qkv / attention output / lse and d(attention output): P and dS rounded to bf16 before the second products."""
+    q, k, v = _heads(_f(A["qkv"]), B, 3)
+    dO, O = _heads(_f(dattn), B)[0], _heads(_f(A["attn"]), B)[0]
+    scale = 1.0 / math.sqrt(e)
+    Pm = torch.exp((q @ k.transpose(-1, -2)) * scale - A["lse"].reshape(B, -1, NTOK)[..., None])
+    D = (dO * O).sum(-1, keepdim=True)
+    dS = _f(_b(Pm * (dO @ v.transpose(-1, -2) - D)))
+    Pb = _f(_b(Pm))
+    return _b(torch.cat([_flat(scale * (dS @ k)), _flat(scale * (dS.transpose(-1, -2) @ q)), _flat(Pb.transpose(-1, -2) @ dO)], 1))
+
+
 def emu_block_bwd(P, A, dy, B, rounded=True):
     G = dict(dy=dy)
     pre = _f(dy) @ _f(P["w2"])
     G["du"] = _b(_f(_b(pre)) * _f(A["u"]))                         # every path: vit_chain_bwd.hip:506 is mlp_bwd_kernel's body
     G["dx_mid"], G["part2"] = emu_lnbwd(G["du"], P["w1"], A["x_mid"], A["mean2"], A["rstd2"], P["ln2_g"], dy, B, rounded)
     G["dattn"] = _b(_f(G["dx_mid"]) @ _f(P["wproj"]))
-    q, k, v = _heads(_f(A["qkv"]), B, 3)
-    dO, O = _heads(_f(G["dattn"]), B)[0], _heads(_f(A["attn"]), B)[0]
-    scale = 1.0 / math.sqrt(dy.shape[1])
-    Pm = torch.exp((q @ k.transpose(-1, -2)) * scale - A["lse"].reshape(B, -1, NTOK)[..., None])
-    D = (dO * O).sum(-1, keepdim=True)
-    dS = _f(_b(Pm * (dO @ v.transpose(-1, -2) - D)))
-    Pb = _f(_b(Pm))
-    G["dqkv"] = _b(torch.cat([_flat(scale * (dS @ k)), _flat(scale * (dS.transpose(-1, -2) @ q)),
-                              _flat(Pb.transpose(-1, -2) @ dO)], 1))
+    G["dqkv"] = emu_attn_bwd(A, G["dattn"], B, dy.shape[1])
     G["dx"], G["part1"] = emu_lnbwd(G["dqkv"], P["wqkv"], A["x_in"], A["mean1"], A["rstd1"], P["ln1_g"], G["dx_mid"], B, rounded)
     return G
 

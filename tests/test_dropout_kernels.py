@@ -1,12 +1,14 @@
 """The dropout kernels (rgbnm.h, dropout mask contract) against the numpy restatement of tests/dropout_ref.py:
-rgbnm_dropout_apply bit for bit, rgbnm_gemm_nt_drop's RES / GELU epilogues element-wise (tests/kernel_check.py bounds, guarded
-outputs) in the staged and the direct form, p = 0 against rgbnm_gemm_nt bit for bit, and the statistics of the masks."""
+rgbnm_dropout_apply bit for bit (also past its grid cap: composite_ref.APPLY_BIG), rgbnm_gemm_nt_drop's RES / GELU epilogues
+element-wise (tests/kernel_check.py bounds, guarded outputs) in the staged and the direct form, p = 0 against rgbnm_gemm_nt
+bit for bit, and the statistics of the masks."""
 import math
 
 import numpy as np
 import pytest
 import torch
 
+import composite_ref as CR
 import dropout_ref as D
 from kernel_check import U, guarded, nan_padded, check_bound, launched, ran, ulp
 from rgb_no_more_amd import lib as L
@@ -55,6 +57,30 @@ def test_apply_on_ones_is_keep_times_scale_bit_for_bit(dt):
         want = torch.where(ref != 0, (z.float() * float(D.threshold(p)[1])).to(dt), torch.zeros_like(z))
         apply(dt, st, p, site, block, z, N, z, N, M, N)
         assert torch.equal(z, want)
+
+
+@pytest.mark.parametrize("dtn,M,N", CR.APPLY_BIG)
+def test_apply_past_the_grid_cap_is_keep_times_scale_bit_for_bit(dtn, M, N):
+    """launch_apply caps the grid at 8192 workgroups of 256 eight-column groups; JPEG-S's own [50176, 384] gradient is past it.
+    These shapes turn dropout_apply_kernel's grid-stride loop twice, the second turn ragged, on the 16-byte path (16-bit and fp32)
+    and on the element path (N % 8 != 0); tests/test_composite_edges_cpu.py asserts those regimes from launch_apply's arithmetic."""
+    dt = CR.DT[dtn]
+    i = [c[0] for c in CR.APPLY_BIG].index(dtn)
+    seed, site, block, p = SEEDS[(i + 1) % 4], (2, 0, 1)[i], (0, 11, 5)[i], (0.1, 0.5, 0.25)[i]
+    st = seed_tensor(seed)
+    x = nan_padded(torch.ones(M, N, device=DEV, dtype=dt), N, 2)
+    y = guarded(M, N, dt)
+    _, names = launched(lambda: apply(dt, st, p, site, block, x, N, y.t, N, M, N))
+    assert len(names) == 1 and "dropout_apply_kernel" in names[0], names
+    y.check(f"apply {dtn} M={M} N={N}")
+    ref = factor_t(seed, p, site, block, M, N).to(dt)
+    assert torch.equal(y.t, ref), (M, N, site, block)
+    del y, ref
+    # on data, in place: y = T(x * scale) or 0
+    z = rnd((M, N), 60 + i, 1.0, dt)
+    want = CR.masked_copy(z, factor_t(seed, p, site, block, M, N), p)
+    apply(dt, st, p, site, block, z, N, z, N, M, N)
+    assert torch.equal(z, want)
 
 
 def nt_drop_case(dt, epi, M, N, K, seed, p, site, block, *, c_f32=False, pad=False):
