@@ -278,12 +278,21 @@ size_t rgbnm_dct_augment_workspace(int B);
 /* Yq [B,1,Hy,Wy,8,8], CbCrq [B,2,Hc,Wc,8,8] (NULL: grayscale -> zero chroma), quant [B,3,8,8]: int16 as returned by
  * read_coefficients.  crop_w must be 56, 28 or 14 (resize /2, identity, x2 -> 28x28 luma / 14x14 chroma blocks).
  * params are needed twice: on the device (kernels) and on the host (validated before launch).
- * conv16: A(8,2) 16x16 fp32; filters: [n][64] fp32 multipliers for MIDFREQAUG/SHARPNESS (may be NULL if unused).
+ * conv16: A(8,2) 16x16 fp32; filters: [n][64] fp32 multipliers for MIDFREQAUG/SHARPNESS.  filters may be NULL only if none of
+ * the first nops ops of any image is MIDFREQAUG or SHARPNESS: otherwise the call returns RGBNM_EINVAL.  iarg0 of those two ops
+ * must index a table of the bank (not checked: the bank's length is not an argument).
  * outY [B,1,28,28,8,8], outC [B,2,14,14,8,8] in out_dtype, after ToRange(-1,1; -1024,1016); out_dtype 2 (RGBNM_DT_I16)
  * stores the int16 coefficients themselves, WITHOUT ToRange (the per-transform classes of custom_transforms.py chain on it).
  * entry_clamp bit 0: clamp before the first op (RandAugment_dct.forward, :1106-1108); bit 1: the input is already
  * de-quantised (unit tables) and must NOT be clamped in front of the crop / resize / flip stage (the reference's per-transform
- * classes pass out-of-range coefficients of a preceding resize through unchanged).  nops in {0,1,2}. */
+ * classes pass out-of-range coefficients of a preceding resize through unchanged).  nops in {0,1,2}.
+ * Flat images (every DC of the op's plane set equal), as the reference's CPU kernels leave them (tests/golden/g24_flat.npz):
+ * AUTOCONTRAST / AUTOSATURATION keep the DCs when min = max = 0 and otherwise set every DC to 0 (0 / 0 = NaN, which the int16
+ * cast turns into 0); EQUALIZE sets every luma DC to -1024 (the same NaN, shifted back by the range minimum).
+ * Every argument is validated on the host before anything is launched: a NULL pointer (CbCrq and filters excepted, see above),
+ * B <= 0, nops or size or out_dtype outside their sets, a crop box that is odd, negative, outside the luma or chroma grid, not
+ * square or of a side other than size/2, size, 2 size, or an op id outside 0..19 return RGBNM_EINVAL, a short workspace
+ * RGBNM_EWORKSPACE; no kernel has then run and no buffer has been touched. */
 int rgbnm_dct_augment(const int16_t* Yq, const int16_t* CbCrq, const int16_t* quant, const rgbnm_aug_params* params_dev,
                       const rgbnm_aug_params* params_host, const float* conv16, const float* filters, void* outY,
                       void* outC, int out_dtype, int B, int Hy, int Wy, int Hc, int Wc, int entry_clamp, int nops,

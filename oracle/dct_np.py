@@ -202,6 +202,11 @@ def autocontrast(coeff):
     mn, mx = dc.min(), dc.max()
     if mn == mx and mx == 0:
         return out
+    if mn == mx:
+        # a flat non-zero image: 0 / 0 = NaN in the reference, and its int16 cast makes 0 of it (tests/golden/g24_flat.npz);
+        # stated here because numpy leaves the cast of a NaN undefined
+        out[:, :, :, 0, 0] = 0
+        return out
     dc = (dc - mn) / (mx - mn)
     dc = np.float32(CMIN) + dc * np.float32(CMAX - CMIN)
     out[:, :, :, 0, 0] = _round_i16(dc)
@@ -306,8 +311,8 @@ def magnitude_table(num_bins=11, image_size=(28, 28)):
 def equalize(coeff):
     """dct_ops.py:916-955 (CPU branch: bincount over the 2041 shifted DC values): per channel
     new = round((cdf[dc] - cdf_min) / (N - cdf_min) * 2039) + CMIN, division and product in fp32, round half to even.
-    cdf_min = number of blocks holding the smallest DC.  All-equal DCs divide by zero in the reference (undefined
-    int16 cast); here they are left unchanged."""
+    cdf_min = number of blocks holding the smallest DC.  All-equal DCs divide 0 by 0 in the reference: its int16 cast makes 0
+    of the NaN and the shift back gives CMIN for every DC (tests/golden/g24_flat.npz)."""
     out = coeff.copy()
     for c in range(coeff.shape[0]):
         dc = coeff[c, :, :, 0, 0].astype(np.int64) - CMIN
@@ -315,6 +320,7 @@ def equalize(coeff):
         nz = hist[hist != 0]
         denom = nz[1:].sum()
         if denom == 0:
+            out[c, :, :, 0, 0] = CMIN
             continue
         cdf = np.cumsum(hist)
         eq = np.rint((cdf - nz[0]).astype(np.float32) / np.float32(denom) * np.float32(CMAX - CMIN - 1))

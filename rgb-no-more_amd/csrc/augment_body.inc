@@ -660,8 +660,10 @@ __global__ __launch_bounds__(AUG_THREADS) void dct_randaug_kernel(short* inter, 
       int cmin = 0;
       for (int i = 0; i < N; ++i) cmin += img[i * 64] == mn ? 1 : 0;
       __syncthreads();                      // every thread has read the original DCs
-      if (tid < N && N - cmin > 0) {
-        const float eq = rintf((float)(le - cmin) / (float)(N - cmin) * (float)(CMAX - CMIN - 1));
+      if (tid < N) {
+        // a flat image (every DC equal, N - cmin == 0) divides 0 by 0 in the reference; its int16 cast makes 0 of the NaN and the
+        // shift back gives CMIN for every DC, whatever the DC was (tests/golden/g24_flat.npz)
+        const float eq = N - cmin > 0 ? rintf((float)(le - cmin) / (float)(N - cmin) * (float)(CMAX - CMIN - 1)) : 0.f;
         img[tid * 64] = clamp_s((int)eq + CMIN);
       }
     } else if (op == RGBNM_OP_INVERT || op == RGBNM_OP_SOLARIZE || op == RGBNM_OP_FREQENHANCE) {
@@ -681,7 +683,7 @@ __global__ __launch_bounds__(AUG_THREADS) void dct_randaug_kernel(short* inter, 
         for (int e = 0; e < 8; ++e) {
           int x = v[e];
           if (op == RGBNM_OP_FREQENHANCE) { if (e != 0 || (i & 7) != 0) x = __float2int_rn((float)x * fm); }
-          else if (neg) x = -x;
+          else if (neg) x = (int)(short)-x;                       // int16 negation (wraps like the reference's tensors: only -32768, on an unclamped image)
           v[e] = clamp_s(x);
         }
         rows[i] = v;
@@ -826,6 +828,7 @@ inline int launch(const int16_t* Yq, const int16_t* CbCrq, const int16_t* quant,
                   size_t ws_bytes, hipStream_t st, const long long* yoff = nullptr, const long long* coff = nullptr) {
   if (ws_bytes < workspace_bytes(B)) return RGBNM_EWORKSPACE;
   if ((yoff != nullptr) != (coff != nullptr)) return RGBNM_EINVAL;
+  if (out_dtype != DT_F32 && out_dtype != DT_BF16 && out_dtype != 2) return RGBNM_EINVAL;      // before kernel 1 goes out, not after it
   // host-side validation of every crop box (the HIP path implements the x2 / identity / /2 resize cases)
   for (int b = 0; b < B; ++b) {
     const rgbnm_aug_params& p = params_host[b];
@@ -834,8 +837,11 @@ inline int launch(const int16_t* Yq, const int16_t* CbCrq, const int16_t* quant,
     if ((p.crop_i & 1) || (p.crop_j & 1) || p.crop_i < 0 || p.crop_j < 0) return RGBNM_EINVAL;
     if (p.crop_i + p.crop_h > Hy || p.crop_j + p.crop_w > Wy) return RGBNM_EINVAL;
     if (CbCrq && (p.crop_i / 2 + p.crop_h / 2 > Hc || p.crop_j / 2 + p.crop_w / 2 > Wc)) return RGBNM_EINVAL;
-    for (int s = 0; s < nops; ++s)
+    for (int s = 0; s < nops; ++s) {
       if (p.op[s] < 0 || p.op[s] > RGBNM_OP_EQUALIZE) return RGBNM_EINVAL;
+      // the only readers of `filters`: without a bank kernel 2 would read through the null pointer
+      if (!filters && (p.op[s] == RGBNM_OP_MIDFREQAUG || p.op[s] == RGBNM_OP_SHARPNESS)) return RGBNM_EINVAL;
+    }
   }
   // algorithmic bytes of the stage (SURVEY.md 8d): the crop box in (192 w^2 B for side w: luma w^2 blocks + 2 chroma planes of
   // (w/2)^2, 128 B each) + the quantisation tables, the S x S image out in out_dtype -- the int16 intermediate is not counted
