@@ -17,10 +17,14 @@
  *     (out_dtype; in_dtype fp32 / bf16 / fp16 with an fp16 output), rgbnm_softxent / _grad / _grad_mix (dl_dtype) and,
  *     through rgbnm_vit_cfg.dtype, the ViT composites (patch embedding, blocks, head); and SwinV2's own entries:
  *     rgbnm_window_attention_fwd / _bwd, rgbnm_swin_embed (out_dtype fp16 from any in_dtype; in_dtype fp16 to any
- *     out_dtype), rgbnm_ln_generic_fwd / _bwd, rgbnm_merge_gather and rgbnm_token_mean.  They run the generic kernels;
- *     the bf16-tuned ones (one-launch chains, k-pipelined / weight-resident / small-M GEMMs, fused MLP, attention v2,
- *     pipelined and grouped weight-gradient kernels, LayerNorm-chained epilogues, held reductions) are bf16 only and are
- *     skipped for fp16.  Everything else (the augment stage, rgbnm_mixup) takes fp32 / bf16 only.
+ *     out_dtype), rgbnm_ln_generic_fwd / _bwd, rgbnm_merge_gather and rgbnm_token_mean.  By default they run the generic
+ *     kernels.  With the option "f16_tuned" set, rgbnm_gemm_nt and rgbnm_gemm_tn (and every composite that calls them) take
+ *     fp16 through the plain GEMM kernels tuned for 16-bit operands, at the shapes where bf16 takes them: the small-M kernel
+ *     (none / tanh / dtanh), the weight-resident and the k-pipelined row-panel kernels (none / residual / GELU with the erf
+ *     arithmetic / dGELU), the pipelined and wide weight-gradient kernels, and the rgbnm_gemm_tn_group_* brackets (a queue holds
+ *     jobs of one dtype: a job of another dtype runs what is queued first).  The other bf16-tuned kernels (one-launch chains,
+ *     fused MLP, attention v2, LayerNorm-chained row-panel epilogues, the bf16 GELU table) are bf16 only and are skipped for
+ *     fp16 whatever the option says.  Everything else (the augment stage, rgbnm_mixup) takes fp32 / bf16 only.
  *   - tensors are dense row-major; "ld*" are row strides in elements.
  */
 #ifndef RGBNM_H
@@ -63,6 +67,8 @@ int rgbnm_abi_version(void);
  *   "kp8"          1  ... its 8-wave / 256-row geometry for row counts that are multiples of 256 (the SwinV2 stages)
  *   "kp_persist"   1  ... its persistent form for several column tiles (JPEG-S: E = 384)
  *   "nt_small"     1  at most 512 rows (the classification head) on 32 x 32 tiles with an in-workgroup split of K
+ *   "f16_tuned"    0  fp16 on the kernels of nt_small / nt_wres / nt_kpipe / tn_pipe / tn_wide and in the grouped dW launches, as bf16
+ *                     (0: fp16 runs the generic tile kernels only, as it did before the option existed: same launches, same bits)
  *   "ln_fuse"      1  LayerNorm forward / backward in the row-panel kernel's epilogues (E = 192)
  *   GEMM  dW = dY^T . X (weight gradients)
  *   "tn_pipe"      1  pipelined kernel (csrc/gemm_tn_pipe.hip; 0: the generic one)     "tn_tr"  1  its ds_read_b64_tr_b16 fragments

@@ -317,6 +317,17 @@ int launch_nt_epi(const GemmNT& p, int epi, hipStream_t st) {
   return RGBNM_OK;
 }
 
+template <typename T> constexpr int dtype_of() {
+  return std::is_same<T, bf16>::value ? DT_BF16 : (std::is_same<T, f16>::value ? DT_F16 : DT_F32);
+}
+// the kernels tuned for 16-bit operands (gemm_nt_small / _kpipe / _wres, gemm_tn_pipe) take this call: bf16 always, fp16 when the
+// f16_tuned option is set
+template <typename T> bool tuned16() {
+  if constexpr (std::is_same<T, bf16>::value) return true;
+  else if constexpr (std::is_same<T, f16>::value) return rgbnm_get_option("f16_tuned") != 0;
+  else return false;
+}
+
 // the staged (16-byte row) epilogue of a 16-bit gemm_nt_kernel: every output row a whole number of 16-byte vectors
 bool nt_staged_ok(const GemmNT& p) {
   return !p.c_f32 && (p.N % 8 == 0) && (p.ldc % 8 == 0) && (!p.R || p.ldr % 8 == 0) && (!p.C2 || p.ldc2 % 8 == 0) &&
@@ -326,12 +337,14 @@ bool nt_staged_ok(const GemmNT& p) {
 template <typename T, int NB>
 int launch_nt_sel(const GemmNT& p, int epi, hipStream_t st) {
   if constexpr (sizeof(T) == 2) {
-    // the small-M, k-pipelined and weight-resident kernels are bf16 only: fp16 takes the generic staged kernel
-    constexpr bool fast = std::is_same<T, bf16>::value;
+    // the small-M, k-pipelined and weight-resident kernels: bf16 always, fp16 behind the f16_tuned option (default: fp16 takes
+    // the generic staged kernel)
+    constexpr int dt = dtype_of<T>();
+    const bool fast = tuned16<T>();
     if (fast && p.M <= 512 && !p.pos && !p.C2 && rgbnm_get_option("nt_small")) {
       // few rows (the classification head: M = batch): 32 x 32 tiles, the reduction split over a workgroup's four waves
       // (gemm_nt_small.hip); 1 = shape / epilogue not eligible
-      const int rc = rgbnm_launch_nt_small(epi, p.A, p.lda, p.W, p.ldw, p.C, p.ldc, p.bias, p.R, p.ldr, p.c_f32, p.M, p.N,
+      const int rc = rgbnm_launch_nt_small(dt, epi, p.A, p.lda, p.W, p.ldw, p.C, p.ldc, p.bias, p.R, p.ldr, p.c_f32, p.M, p.N,
                                            p.K, st);
       if (rc != 1) return rc;
     }
@@ -339,13 +352,13 @@ int launch_nt_sel(const GemmNT& p, int epi, hipStream_t st) {
     if (fast && ok && !p.pos && rgbnm_get_option("nt_kpipe")) {
       // N % 192 == 0 with a long reduction (K >= 256): 224-row panels x 192-column tiles, k-tiles through an LDS-DMA ring
       // (gemm_nt_kpipe.hip); N = 192: one row panel per CU
-      const int rc = rgbnm_launch_nt_kpipe(epi, p.A, p.lda, p.W, p.ldw, p.C, p.ldc, p.bias, p.R, p.ldr, p.C2, p.ldc2, p.M,
+      const int rc = rgbnm_launch_nt_kpipe(dt, epi, p.A, p.lda, p.W, p.ldw, p.C, p.ldc, p.bias, p.R, p.ldr, p.C2, p.ldc2, p.M,
                                            p.N, p.K, st);
       if (rc != 1) return rc;
     }
     if (fast && ok && !p.pos && rgbnm_get_option("nt_wres")) {
       // K = 192 layers: persistent weight-resident kernel (gemm_nt_wres.hip); 1 = shape not eligible
-      const int rc = rgbnm_launch_nt_wres(epi, p.A, p.lda, p.W, p.ldw, p.C, p.ldc, p.bias, p.R, p.ldr, p.C2, p.ldc2,
+      const int rc = rgbnm_launch_nt_wres(dt, epi, p.A, p.lda, p.W, p.ldw, p.C, p.ldc, p.bias, p.R, p.ldr, p.C2, p.ldc2,
                                           p.M, p.N, p.K, st);
       if (rc != 1) return rc;
     }
@@ -615,7 +628,7 @@ int submit_tn_reduce(const GemmTN& p, float* dW, float* db, int S, int perm_head
 }
 
 // deferred (grouped) weight-gradient launches
-struct TnPending { GemmTN p; float* dW; float* db; int perm_heads, accumulate; };
+struct TnPending { GemmTN p; float* dW; float* db; int perm_heads, accumulate, dtype; };
 thread_local bool g_tn_defer = false;     // per host thread, like the reduction queue (reduce.hip)
 constexpr int TN_QMAX = 52;      // = TN_MAXJOBS of gemm_tn_pipe.hip
 thread_local TnPending g_tn_q[TN_QMAX];
@@ -658,7 +671,7 @@ int tn_flush(hipStream_t st) {
     jobs[i].smax = p.S;
   }
   int S = 0, direct = 0;
-  const int rc = rgbnm_launch_tn_pipe_group(jobs, n, &S, st, rgbnm_get_option("tn_direct") ? &direct : nullptr);
+  const int rc = rgbnm_launch_tn_pipe_group(g_tn_q[0].dtype, jobs, n, &S, st, rgbnm_get_option("tn_direct") ? &direct : nullptr);
   if (rc != RGBNM_OK) return rc < 0 ? rc : RGBNM_EINVAL;     // eligibility was checked when the jobs were queued
   if (direct) return RGBNM_OK;                               // no token split: the kernel wrote dW / db itself
   const bool own = !rgbnm_reduce_defer_active();             // the reductions of one grouped launch: one launch (also when the
@@ -687,21 +700,22 @@ int launch_tn(GemmTN p, float* dW, float* db, int perm_heads, int accumulate, hi
   const bool nb3 = (p.Ki % 192 == 0);
   p.ctiles = nb3 ? p.Ki / 192 : cdiv(p.Ki, 128);
   const int tiles = p.rtiles * p.ctiles;
-  if constexpr (std::is_same<T, bf16>::value) {      // grouped / pipelined weight-gradient kernels: bf16 only
+  if (tuned16<T>()) {      // grouped / pipelined weight-gradient kernels: bf16, or fp16 with f16_tuned
+    constexpr int dt = dtype_of<T>();
     tn_check_abort();
     if (g_tn_defer && tn_groupable(p)) {
       // a grouped launch has one workgroup per output tile and at most 256 of them (rgbnm_launch_tn_pipe_group): what is queued
-      // runs before a job that would take the queue past that, or that has another row count (the queue used to fail
-      // with RGBNM_EINVAL for widths whose blocks have more than 256 / n tiles)
+      // runs before a job that would take the queue past that, or that has another row count or element type (the
+      // queue used to fail with RGBNM_EINVAL for widths whose blocks have more than 256 / n tiles)
       const int jt = cdiv(p.No, 128) * (p.Ki / 192);
-      if (g_tn_n && (g_tn_q[0].p.M != p.M || g_tn_tiles + jt > 256)) { const int rf = tn_flush(st); if (rf != RGBNM_OK) return rf; }
-      g_tn_q[g_tn_n++] = TnPending{p, dW, db, perm_heads, accumulate};
+      if (g_tn_n && (g_tn_q[0].p.M != p.M || g_tn_q[0].dtype != dt || g_tn_tiles + jt > 256)) { const int rf = tn_flush(st); if (rf != RGBNM_OK) return rf; }
+      g_tn_q[g_tn_n++] = TnPending{p, dW, db, perm_heads, accumulate, dt};
       g_tn_tiles += jt;
       return g_tn_n == g_tn_cap ? tn_flush(st) : RGBNM_OK;
     }
     if (rgbnm_get_option("tn_pipe")) {
       int Sp = 0;
-      const int rc = rgbnm_launch_tn_pipe(p.dY, p.ldy, p.X, p.ldx, p.part, db ? p.bpart : nullptr, p.M, p.No, p.Ki,
+      const int rc = rgbnm_launch_tn_pipe(dt, p.dY, p.ldy, p.X, p.ldx, p.part, db ? p.bpart : nullptr, p.M, p.No, p.Ki,
                                           &Sp, st, p.S);
       if (rc < 0) return rc;
       if (rc == 0) {

@@ -1,5 +1,5 @@
 // Row-panel NT GEMM for the N = 192 Linear layers with a long reduction (fc2: K = 768 + bias + residual; the dX
-// GEMMs of fc1 and qkv: K = 768 / 576), bf16:   C[M,192] = epi(A[M,K] . W[192,K]^T).
+// GEMMs of fc1 and qkv: K = 768 / 576), bf16 -- and, for the plain epilogues, fp16 --:   C[M,192] = epi(A[M,K] . W[192,K]^T).
 // These read 58-77 MB of activations to produce 19 MB: HBM-read bound.  One 448-thread workgroup per CU owns ONE
 // contiguous panel of rows (M / 256 = 196 tokens at B = 256: exactly one workgroup per CU, a single balanced round;
 // 7 waves x 32 rows, the last 28 rows are padding) and all 192 output columns, and streams the reduction through a
@@ -9,6 +9,7 @@
 // Epilogue: accumulators (MFMA issued with swapped operands: a lane owns one token) -> bf16 staging tile in the ring
 // memory -> coalesced 16-byte row pieces, bias and the residual (prefetched into registers before the loop) fused.
 #include "common.h"
+#include <type_traits>
 #include "internal.h"
 #include "lds_common.h"
 #include "ln_bwd_rows.h"
@@ -68,10 +69,15 @@ int rgbnm_launch_nt_kpipe_lnbwd(const void* A, int lda, const void* W, int ldw, 
 }
 
 // returns 1 when the shape is not eligible (caller falls back to the tile-per-workgroup kernel)
-int rgbnm_launch_nt_kpipe(int epi, const void* A, int lda, const void* W, int ldw, void* C, int ldc, const float* bias,
+int rgbnm_launch_nt_kpipe(int dtype, int epi, const void* A, int lda, const void* W, int ldw, void* C, int ldc, const float* bias,
                           const void* R, int ldr, void* C2, int ldc2, int M, int N, int K, hipStream_t st) {
-  if (use_kp8(M, N, epi)) return kp8::launch_plain(epi, A, lda, W, ldw, C, ldc, bias, R, ldr, C2, ldc2, M, N, K, st);
-  return kp7::launch_plain(epi, A, lda, W, ldw, C, ldc, bias, R, ldr, C2, ldc2, M, N, K, st);
+  if (dtype == DT_F16) {
+    if (use_kp8(M, N, epi)) return kp8::launch_plain<f16>(epi, A, lda, W, ldw, C, ldc, bias, R, ldr, C2, ldc2, M, N, K, st);
+    return kp7::launch_plain<f16>(epi, A, lda, W, ldw, C, ldc, bias, R, ldr, C2, ldc2, M, N, K, st);
+  }
+  if (dtype != DT_BF16) return 1;
+  if (use_kp8(M, N, epi)) return kp8::launch_plain<bf16>(epi, A, lda, W, ldw, C, ldc, bias, R, ldr, C2, ldc2, M, N, K, st);
+  return kp7::launch_plain<bf16>(epi, A, lda, W, ldw, C, ldc, bias, R, ldr, C2, ldc2, M, N, K, st);
 }
 
 #ifdef KP_PROF

@@ -43,6 +43,8 @@ constexpr int RED_OFF = (BM * CP * 2 + 1023) / 1024 * 1024;   // column-reductio
 typedef rgbnm::LnBwdRows<NTHREADS, BM> LnBwd;                  // EPI_LNBWD: 8 lanes per row, shared with mlp_bwd_kernel (ln_bwd_rows.h)
 constexpr bool LN_OK = BM * CP * 2 <= RED_OFF && RED_OFF + LnBwd::RED_BYTES <= NSTAGE * STAGE;   // LN scratch fits the ring (not kp8)
 
+// (the 16-bit operand pointers are typed bf16 for their 2-byte address arithmetic; the plain epilogues read and write them as the
+// kernel's element type E, bf16 or fp16 -- the LayerNorm epilogues are bf16 only)
 struct KpArgs {
   const bf16* A; const bf16* W; bf16* C; const float* bias; const bf16* R;
   int lda, ldw, ldc, ldr;
@@ -80,10 +82,10 @@ constexpr bool TAB_RESIDENT_OK = (SMEM + TAB_RESERVE) * (NWAVES <= 4 ? 2 : 1) <=
 #ifndef KP_DMA_BURST
 #define KP_DMA_BURST 0
 #endif
-template <bool W2D, int ND, class DmaFn>
+template <typename E, bool W2D, int ND, class DmaFn>
 __device__ __forceinline__ void ktile_mma(const unsigned char* sA, const unsigned char* sW, const int (&foff)[4], int wn,
                                           f32x16 (&acc)[6], bool do_dma, DmaFn dma) {
-#define KP_LD(ptr) (*reinterpret_cast<const bf16x8*>(ptr))
+#define KP_LD(ptr) (*reinterpret_cast<const typename Vec8<E>::type*>(ptr))
 #define KP_SB __builtin_amdgcn_sched_barrier(0)
   if constexpr (KP_PIPE && !W2D) {
     KP_SB;
@@ -94,7 +96,7 @@ __device__ __forceinline__ void ktile_mma(const unsigned char* sA, const unsigne
     }
     KP_SB;
 #endif
-    Frag<bf16> fa[4], fb[4][6];
+    Frag<E> fa[4], fb[4][6];
     fa[0].v = KP_LD(sA + foff[0]);
 #pragma unroll
     for (int b = 0; b < 6; ++b) fb[0][b].v = KP_LD(sW + 32 * b * TKB + foff[0]);
@@ -126,7 +128,7 @@ __device__ __forceinline__ void ktile_mma(const unsigned char* sA, const unsigne
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     if constexpr (W2D) {
-      Frag<bf16> fa[2], fb[3];
+      Frag<E> fa[2], fb[3];
       fa[0].v = KP_LD(sA + foff[c]);
       fa[1].v = KP_LD(sA + 32 * TKB + foff[c]);
 #pragma unroll
@@ -136,7 +138,7 @@ __device__ __forceinline__ void ktile_mma(const unsigned char* sA, const unsigne
 #pragma unroll
         for (int j = 0; j < 3; ++j) mma(acc[3 * rg + j], fb[j], fa[rg]);
     } else {
-      Frag<bf16> fa, fb[6];
+      Frag<E> fa, fb[6];
       fa.v = KP_LD(sA + foff[c]);
 #pragma unroll
       for (int b = 0; b < 6; ++b) fb[b].v = KP_LD(sW + 32 * b * TKB + foff[c]);
@@ -148,12 +150,16 @@ __device__ __forceinline__ void ktile_mma(const unsigned char* sA, const unsigne
 #undef KP_SB
 }
 
-template <int EPI>
+template <typename E, int EPI>
 __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
+  static_assert(std::is_same<E, bf16>::value || (EPI != EPI_RES_LN && EPI != EPI_LNBWD), "LayerNorm epilogues: bf16 only");
+  constexpr bool IS_BF16 = std::is_same<E, bf16>::value;      // the GELU table is a bf16 image: other types take the arithmetic GELU
+  using V8 = typename Vec8<E>::type;
+  using V4 = typename Vec4<E>::type;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem0[];
   // EPI_GELU with the table (8-wave geometry: 14 KB to spare): the image stays at LDS offset 0 for the workgroup's life, ring,
   // staging tile and bias live TAB_RESERVE higher
-  const bool tabr = EPI == EPI_GELU && TAB_RESIDENT_OK && p.tab.img != nullptr;
+  const bool tabr = IS_BF16 && EPI == EPI_GELU && TAB_RESIDENT_OK && p.tab.img != nullptr;
   unsigned char* const smem = smem0 + (tabr ? TAB_RESERVE : 0);
   float* Bs = reinterpret_cast<float*>(smem + BIAS_OFF);
   // blocks that share an A row panel (its column tiles) are neighbours on one XCD (block b runs on XCD b % 8): the
@@ -174,13 +180,13 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
 
 
   // ---- residual rows of this panel, straight into registers (oldest loads: they never delay a k-tile wait)
-  bf16x8 rv[NVEC];
+  V8 rv[NVEC];
   if (EPI == EPI_RES || EPI == EPI_DGELU) {
 #pragma unroll
     for (int i = 0; i < NVEC; ++i) {
       const int idx = tid + NTHREADS * i, row = idx / (BN / 8), vec = idx % (BN / 8);
       const int rr = row < rows ? row : rows - 1;
-      rv[i] = *reinterpret_cast<const bf16x8*>(p.R + (size_t)(m0 + rr) * p.ldr + n0 + vec * 8);
+      rv[i] = *reinterpret_cast<const V8*>(p.R + (size_t)(m0 + rr) * p.ldr + n0 + vec * 8);
     }
   }
   // EPI_RES_LN: residual rows in the 8-lanes-per-row layout of its LayerNorm pass (gamma / beta: after the loop)
@@ -280,7 +286,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
     const unsigned char* sA = smem + st_comp * STAGE + a_row;
     const unsigned char* sW = smem + st_comp * STAGE + A_STAGE;
     st_comp = st_comp == NSTAGE - 1 ? 0 : st_comp + 1;
-    ktile_mma<W2D, NDMA>(sA, sW, foff, wn, acc, do_dma, [&](int j) { issue1(stD, j); });
+    ktile_mma<E, W2D, NDMA>(sA, sW, foff, wn, acc, do_dma, [&](int j) { issue1(stD, j); });
     if (do_dma) {
       k0 += 64;
       st_issue = st_issue == NSTAGE - 1 ? 0 : st_issue + 1;
@@ -291,7 +297,8 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
   KPROF(2);
 
   // ---- pass 1: lane = token (32 w + l31), register quad = 4 consecutive features (+ bias) -> bf16 staging tile
-  bf16* Cs = reinterpret_cast<bf16*>(smem);
+  E* Cs = reinterpret_cast<E*>(smem);
+  bf16* Cs16 = reinterpret_cast<bf16*>(smem);      // the same tile for the (bf16 only) LayerNorm epilogues
 #pragma unroll
   for (int b = 0; b < 6; ++b)
 #pragma unroll
@@ -301,7 +308,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
       f32x4 v = {acc[b][4 * q + 0], acc[b][4 * q + 1], acc[b][4 * q + 2], acc[b][4 * q + 3]};
       if (BIAS_LDS) v += *reinterpret_cast<const f32x4*>(Bs + nl);
       else if (p.bias) v += *reinterpret_cast<const f32x4*>(p.bias + n0 + nl);
-      store4<bf16>(Cs + ml * CP + nl, v);
+      store4<E>(Cs + ml * CP + nl, v);
     }
   f32x4 gm[3][2], bt[3][2];        // EPI_RES_LN: gamma / beta of this lane's 24 elements, requested now (accumulators dead)
   if (EPI == EPI_RES_LN) {
@@ -328,7 +335,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
         float s0 = 0.f, s1 = 0.f;
 #pragma unroll
         for (int v = 0; v < 3; ++v) {
-          const bf16* cp = Cs + row * CP + v * 64 + l8 * 8;            // 8-byte aligned (CP * 2 = 392)
+          const bf16* cp = Cs16 + row * CP + v * 64 + l8 * 8;           // 8-byte aligned (CP * 2 = 392)
           const bf16x4 c0 = *reinterpret_cast<const bf16x4*>(cp), c1 = *reinterpret_cast<const bf16x4*>(cp + 4);
           bf16x8 xb;
 #pragma unroll
@@ -369,24 +376,25 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
   }
   if (EPI == EPI_LNBWD) {
     // ---- LayerNorm backward on the staged rows + panel sums of dgamma / dbeta (ln_bwd_rows.h)
-    lnb.run(Cs, CP, p.C, p.ldc, p.gamma, p.R != nullptr, p.part, panel, reinterpret_cast<float*>(smem + RED_OFF), m0, rows, tid);
+    lnb.run(Cs16, CP, p.C, p.ldc, p.gamma, p.R != nullptr, p.part, panel, reinterpret_cast<float*>(smem + RED_OFF), m0, rows, tid);
     return;
   }
   // ---- pass 2: valid rows x 24 vectors of 8 features, coalesced 384-byte rows
+  E* C2 = reinterpret_cast<E*>(p.C2);
 #pragma unroll
   for (int i = 0; i < NVEC; ++i) {
     const int idx = tid + NTHREADS * i, row = idx / (BN / 8), vec = idx % (BN / 8);
     if (row >= rows) continue;
-    const bf16x4 c0 = *reinterpret_cast<const bf16x4*>(Cs + row * CP + vec * 8);
-    const bf16x4 c1 = *reinterpret_cast<const bf16x4*>(Cs + row * CP + vec * 8 + 4);
-    bf16x8 cv = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
+    const V4 c0 = *reinterpret_cast<const V4*>(Cs + row * CP + vec * 8);
+    const V4 c1 = *reinterpret_cast<const V4*>(Cs + row * CP + vec * 8 + 4);
+    V8 cv = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
     if (EPI == EPI_RES) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) cv[e] = (bf16)((float)cv[e] + (float)rv[i][e]);
+      for (int e = 0; e < 8; ++e) cv[e] = from_f32<E>((float)cv[e] + (float)rv[i][e]);
     }
     if (EPI == EPI_DGELU) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) cv[e] = (bf16)((float)cv[e] * (float)rv[i][e]);
+      for (int e = 0; e < 8; ++e) cv[e] = from_f32<E>((float)cv[e] * (float)rv[i][e]);
     }
     if (EPI == EPI_GELU && tabr) {
       unsigned pb[4], gq[4], dq[4];
@@ -395,10 +403,10 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
       for (int jj = 0; jj < 4; ++jj) pb[jj] = raw[jj];
       rgbnm::gelu_table_pairs4(pb, gq, dq, p.tab, k4v);
       const rgbnm::tab_u32x4 gr = {gq[0], gq[1], gq[2], gq[3]}, dr = {dq[0], dq[1], dq[2], dq[3]};
-      cv = __builtin_bit_cast(bf16x8, gr);
-      store_c2(p.C2 + (size_t)(m0 + row) * p.ldc2 + n0 + vec * 8, __builtin_bit_cast(bf16x8, dr));
+      cv = __builtin_bit_cast(V8, gr);
+      store_c2(C2 + (size_t)(m0 + row) * p.ldc2 + n0 + vec * 8, __builtin_bit_cast(V8, dr));
     } else if (EPI == EPI_GELU) {     // one erfc / exp2 evaluation yields gelu(u) (-> C) and gelu'(u) (-> C2), as in gemm.hip
-      bf16x8 dv;
+      V8 dv;
 #pragma unroll
       for (int e = 0; e < 8; e += 2) {
         const f32x2 u = {(float)cv[e], (float)cv[e + 1]};
@@ -408,14 +416,14 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
 #else
         gelu_pair_fast(u, gv, dgv);
 #endif
-        dv[e] = (bf16)dgv[0];
-        dv[e + 1] = (bf16)dgv[1];
-        cv[e] = (bf16)gv[0];
-        cv[e + 1] = (bf16)gv[1];
+        dv[e] = from_f32<E>(dgv[0]);
+        dv[e + 1] = from_f32<E>(dgv[1]);
+        cv[e] = from_f32<E>(gv[0]);
+        cv[e + 1] = from_f32<E>(gv[1]);
       }
-      store_c2(p.C2 + (size_t)(m0 + row) * p.ldc2 + n0 + vec * 8, dv);
+      store_c2(C2 + (size_t)(m0 + row) * p.ldc2 + n0 + vec * 8, dv);
     }
-    *reinterpret_cast<bf16x8*>(p.C + (size_t)(m0 + row) * p.ldc + n0 + vec * 8) = cv;
+    *reinterpret_cast<V8*>(p.C + (size_t)(m0 + row) * p.ldc + n0 + vec * 8) = cv;
   }
   KPROF(3);
 }
@@ -426,15 +434,19 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
 // the NEXT unit's first k-tile -- into the LAST ring stage (NSTAGE - 1), which neither the 88 KB staging tile nor the GELU table image
 // below it (TAB_PERSIST_OK) ever touches -- before it starts the epilogue of
 // the current one: from the second unit on the prologue is gone.  Same MFMA order per output as the kernel above (same bits).
-template <int EPI>
+template <typename E, int EPI>
 __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_persist_kernel(KpArgs p) {
   static_assert(EPI == EPI_NONE || EPI == EPI_RES || EPI == EPI_GELU || EPI == EPI_DGELU, "plain epilogues");
+  constexpr bool IS_BF16 = std::is_same<E, bf16>::value;      // the GELU table is a bf16 image
+  using V8 = typename Vec8<E>::type;
+  using V4 = typename Vec4<E>::type;
+  E* C2 = reinterpret_cast<E*>(p.C2);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* Bs = reinterpret_cast<float*>(smem + BIAS_OFF);
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, g = lane >> 5;
-  const bool tab = EPI == EPI_GELU && TAB_PERSIST_OK && p.tab.img != nullptr;
+  const bool tab = IS_BF16 && EPI == EPI_GELU && TAB_PERSIST_OK && p.tab.img != nullptr;
   unsigned k4v = 0x00040004u;                 // (table GELU: a VGPR operand of the packed key arithmetic)
   asm volatile("" : "+v"(k4v));
   // Unit order.  Workgroup b runs on XCD b % 8 and is slot b / 8 of it; the XCD's units are numbered jj = (its panel index) *
@@ -523,7 +535,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_persist_kernel(KpArgs 
 #ifndef KP_REARLY
 #define KP_REARLY 1
 #endif
-    bf16x8 rv[NVEC];
+    V8 rv[NVEC];
     const int tl = 64 * w + lane_id_here();        // (opaque thread id: see set_unit)
     auto request_rows = [&]() {
       if (EPI == EPI_RES || EPI == EPI_DGELU) {
@@ -531,7 +543,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_persist_kernel(KpArgs 
         for (int i = 0; i < NVEC; ++i) {
           const int idx = tl + NTHREADS * i, row = idx / (BN / 8), vec = idx % (BN / 8);
           const int rr = row < rows ? row : rows - 1;
-          rv[i] = *reinterpret_cast<const bf16x8*>(p.R + (size_t)(m0 + rr) * p.ldr + n0 + vec * 8);
+          rv[i] = *reinterpret_cast<const V8*>(p.R + (size_t)(m0 + rr) * p.ldr + n0 + vec * 8);
         }
       }
     };
@@ -546,7 +558,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_persist_kernel(KpArgs 
       const unsigned char* sA = smem + st_comp * STAGE + a_row;
       const unsigned char* sW = smem + st_comp * STAGE + A_STAGE;
       st_comp = st_comp == NSTAGE - 1 ? 0 : st_comp + 1;
-      ktile_mma<false, NDMA>(sA, sW, foff, 0, acc, do_dma, [&](int j) {
+      ktile_mma<E, false, NDMA>(sA, sW, foff, 0, acc, do_dma, [&](int j) {
         int i = w + NWAVES * j;
         i = i < NSLOT ? i : i - NSLOT;
         const bf16* base = i < ASLOT ? p.A : p.W;
@@ -579,7 +591,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_persist_kernel(KpArgs 
     }
 
     // ---- pass 1: lane = token, register quad = 4 consecutive features (+ bias) -> bf16 staging tile
-    bf16* Cs = reinterpret_cast<bf16*>(smem + (tab ? TAB_RESERVE : 0));
+    E* Cs = reinterpret_cast<E*>(smem + (tab ? TAB_RESERVE : 0));
     const int ml = 32 * w + l31;
 #pragma unroll
     for (int b = 0; b < 6; ++b)
@@ -588,7 +600,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_persist_kernel(KpArgs 
         const int nl = 32 * b + 8 * q + 4 * g;
         f32x4 v = {acc[b][4 * q + 0], acc[b][4 * q + 1], acc[b][4 * q + 2], acc[b][4 * q + 3]};
         v += *reinterpret_cast<const f32x4*>(Bs + nl);
-        store4<bf16>(Cs + ml * CP + nl, v);
+        store4<E>(Cs + ml * CP + nl, v);
       }
     if (tab) {                               // this wave's pieces of the table image (older than the prefetched k-tile) have landed
       if (landed0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");
@@ -602,16 +614,16 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_persist_kernel(KpArgs 
     for (int i = 0; i < NVEC; ++i) {
       const int idx = tl + NTHREADS * i, row = idx / (BN / 8), vec = idx % (BN / 8);
       if (row >= crows) continue;
-      const bf16x4 c0 = *reinterpret_cast<const bf16x4*>(Cs + row * CP + vec * 8);
-      const bf16x4 c1 = *reinterpret_cast<const bf16x4*>(Cs + row * CP + vec * 8 + 4);
-      bf16x8 cv = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
+      const V4 c0 = *reinterpret_cast<const V4*>(Cs + row * CP + vec * 8);
+      const V4 c1 = *reinterpret_cast<const V4*>(Cs + row * CP + vec * 8 + 4);
+      V8 cv = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
       if (EPI == EPI_RES) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) cv[e] = (bf16)((float)cv[e] + (float)rv[i][e]);
+        for (int e = 0; e < 8; ++e) cv[e] = from_f32<E>((float)cv[e] + (float)rv[i][e]);
       }
       if (EPI == EPI_DGELU) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) cv[e] = (bf16)((float)cv[e] * (float)rv[i][e]);
+        for (int e = 0; e < 8; ++e) cv[e] = from_f32<E>((float)cv[e] * (float)rv[i][e]);
       }
       if (EPI == EPI_GELU && tab) {
         unsigned pb[4], gq[4], dq[4];
@@ -620,10 +632,10 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_persist_kernel(KpArgs 
         for (int jj = 0; jj < 4; ++jj) pb[jj] = raw[jj];
         rgbnm::gelu_table_pairs4(pb, gq, dq, p.tab, k4v);
         const rgbnm::tab_u32x4 gr = {gq[0], gq[1], gq[2], gq[3]}, dr = {dq[0], dq[1], dq[2], dq[3]};
-        cv = __builtin_bit_cast(bf16x8, gr);
-        store_c2(p.C2 + (size_t)(cm0 + row) * p.ldc2 + cn0 + vec * 8, __builtin_bit_cast(bf16x8, dr));
+        cv = __builtin_bit_cast(V8, gr);
+        store_c2(C2 + (size_t)(cm0 + row) * p.ldc2 + cn0 + vec * 8, __builtin_bit_cast(V8, dr));
       } else if (EPI == EPI_GELU) {
-        bf16x8 dv;
+        V8 dv;
 #pragma unroll
         for (int e = 0; e < 8; e += 2) {
           const f32x2 uu = {(float)cv[e], (float)cv[e + 1]};
@@ -633,21 +645,21 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_persist_kernel(KpArgs 
 #else
           gelu_pair_fast(uu, gv, dgv);
 #endif
-          dv[e] = (bf16)dgv[0];
-          dv[e + 1] = (bf16)dgv[1];
-          cv[e] = (bf16)gv[0];
-          cv[e + 1] = (bf16)gv[1];
+          dv[e] = from_f32<E>(dgv[0]);
+          dv[e + 1] = from_f32<E>(dgv[1]);
+          cv[e] = from_f32<E>(gv[0]);
+          cv[e + 1] = from_f32<E>(gv[1]);
         }
 #ifndef KPX_NOC2
-        store_c2(p.C2 + (size_t)(cm0 + row) * p.ldc2 + cn0 + vec * 8, dv);
+        store_c2(C2 + (size_t)(cm0 + row) * p.ldc2 + cn0 + vec * 8, dv);
 #else
-        if (dv[0] == (bf16)123.f && dv[3] == (bf16)-7.f) store_c2(p.C2 + (size_t)(cm0 + row) * p.ldc2 + cn0 + vec * 8, dv);
+        if (dv[0] == (E)123.f && dv[3] == (E)-7.f) store_c2(C2 + (size_t)(cm0 + row) * p.ldc2 + cn0 + vec * 8, dv);
 #endif
       }
 #ifdef KPX_NOSTORE
-      if (cv[0] == (bf16)123.f && cv[3] == (bf16)-7.f)
+      if (cv[0] == (E)123.f && cv[3] == (E)-7.f)
 #endif
-      *reinterpret_cast<bf16x8*>(p.C + (size_t)(cm0 + row) * p.ldc + cn0 + vec * 8) = cv;
+      *reinterpret_cast<V8*>(p.C + (size_t)(cm0 + row) * p.ldc + cn0 + vec * 8) = cv;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();          // the staging tile and the bias are read: the next unit may overwrite stages 0 / 1 and Bs
@@ -659,32 +671,32 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_persist_kernel(KpArgs 
   }
 }
 
-template <int EPI>
+template <typename E, int EPI>
 int launch_persist(const KpArgs& p, hipStream_t st) {
   static DevOnce attr;
   if (attr.need()) {
-    if (hipFuncSetAttribute((const void*)gemm_nt_kpipe_persist_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)gemm_nt_kpipe_persist_kernel<E, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess)
       return RGBNM_ELAUNCH;
     attr.done();
   }
   const int J = ((p.npanels + 7) / 8) * p.ntiles;             // units per XCD
   const int slots = J < 32 ? J : 32;                          // 32 CUs per XCD, one workgroup each
-  hipLaunchKernelGGL((gemm_nt_kpipe_persist_kernel<EPI>), dim3(8 * slots), dim3(NTHREADS), SMEM, st, p);
+  hipLaunchKernelGGL((gemm_nt_kpipe_persist_kernel<E, EPI>), dim3(8 * slots), dim3(NTHREADS), SMEM, st, p);
   LAUNCH_CHECK();
   return RGBNM_OK;
 }
 
-template <int EPI>
+template <typename E, int EPI>
 int launch(const KpArgs& p, hipStream_t st) {
   static DevOnce attr;
   if (attr.need()) {
-    if (hipFuncSetAttribute((const void*)gemm_nt_kpipe_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute((const void*)gemm_nt_kpipe_kernel<E, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             SMEM + (TAB_RESIDENT_OK ? TAB_RESERVE : 0)) != hipSuccess)
       return RGBNM_ELAUNCH;
     attr.done();
   }
-  const bool tabr = EPI == EPI_GELU && TAB_RESIDENT_OK && p.tab.img != nullptr;
-  hipLaunchKernelGGL((gemm_nt_kpipe_kernel<EPI>), dim3(cdiv(p.npanels, 8) * 8 * p.ntiles), dim3(NTHREADS),
+  const bool tabr = std::is_same<E, bf16>::value && EPI == EPI_GELU && TAB_RESIDENT_OK && p.tab.img != nullptr;
+  hipLaunchKernelGGL((gemm_nt_kpipe_kernel<E, EPI>), dim3(cdiv(p.npanels, 8) * 8 * p.ntiles), dim3(NTHREADS),
                      SMEM + (tabr ? TAB_RESERVE : 0), st, p);
   LAUNCH_CHECK();
   return RGBNM_OK;
@@ -710,7 +722,7 @@ int launch_res_ln(const void* A, int lda, const void* W, int ldw, const float* b
   p.npanels = cdiv(M, rows);
   const double mn = (double)M * N;
   const int slot = rgbnm_trace_begin(TR_NT, 2.0 * mn * K, ((double)M * K + (double)N * K) * 2.0 + mn * 2.0 * 3.0, st);
-  const int rc = launch<EPI_RES_LN>(p, st);
+  const int rc = launch<bf16, EPI_RES_LN>(p, st);
   rgbnm_trace_end(slot, st);
   return rc;
 }
@@ -736,12 +748,13 @@ int launch_lnbwd(const void* A, int lda, const void* W, int ldw, const void* X, 
   *npanels_out = p.npanels;
   const double mn = (double)M * N;
   const int slot = rgbnm_trace_begin(TR_NT, 2.0 * mn * K, ((double)M * K + (double)N * K) * 2.0 + mn * 2.0 * (dres ? 3.0 : 2.0), st);
-  const int rc = launch<EPI_LNBWD>(p, st);
+  const int rc = launch<bf16, EPI_LNBWD>(p, st);
   rgbnm_trace_end(slot, st);
   return rc;
 }
 
 // returns 1 when the shape is not eligible (caller falls back to the tile-per-workgroup kernel)
+template <typename E>
 int launch_plain(int epi, const void* A, int lda, const void* W, int ldw, void* C, int ldc, const float* bias,
                           const void* R, int ldr, void* C2, int ldc2, int M, int N, int K, hipStream_t st) {
   // epi uses the numbering of gemm.hip: 0 none, 1 residual, 2 GELU (+ GELU' into C2), 4 dGELU product
@@ -755,7 +768,7 @@ int launch_plain(int epi, const void* A, int lda, const void* W, int ldw, void* 
   p.X = nullptr; p.gamma = p.mean = p.rstd = nullptr; p.part = nullptr; p.ldx = 0;
   p.beta = nullptr; p.Y2 = nullptr; p.mean_o = p.rstd_o = nullptr; p.eps = 0.f; p.ldy2 = 0;
   p.C2 = (bf16*)C2; p.ldc2 = ldc2;
-  if (epi == 2) rgbnm::gelu_table_keys(p.tab);
+  if (epi == 2 && std::is_same<E, bf16>::value) rgbnm::gelu_table_keys(p.tab);      // fp16: tab keeps KpArgs' initialiser (img == nullptr): the arithmetic GELU runs
   p.ntiles = N / BN;
   // N = 192: one panel per CU when it fits (M / 256 rows, at most 224: one balanced round).  Several column tiles: full
   // 224-row panels (the workgroup's arithmetic intensity against the L2 -> CU fabric is what bounds these shapes)
@@ -768,11 +781,11 @@ int launch_plain(int epi, const void* A, int lda, const void* W, int ldw, void* 
                                                               (epi != 0 ? mn * 2.0 : 0.0), st);
   int rc;
   if (NSTAGE == 3 && BIAS_LDS && p.ntiles > 1 && rgbnm_get_option("kp_persist"))
-    rc = epi == 1 ? launch_persist<EPI_RES>(p, st) : epi == 2 ? launch_persist<EPI_GELU>(p, st)
-       : epi == 4 ? launch_persist<EPI_DGELU>(p, st) : launch_persist<EPI_NONE>(p, st);
+    rc = epi == 1 ? launch_persist<E, EPI_RES>(p, st) : epi == 2 ? launch_persist<E, EPI_GELU>(p, st)
+       : epi == 4 ? launch_persist<E, EPI_DGELU>(p, st) : launch_persist<E, EPI_NONE>(p, st);
   else
-    rc = epi == 1 ? launch<EPI_RES>(p, st) : epi == 2 ? launch<EPI_GELU>(p, st)
-       : epi == 4 ? launch<EPI_DGELU>(p, st) : launch<EPI_NONE>(p, st);
+    rc = epi == 1 ? launch<E, EPI_RES>(p, st) : epi == 2 ? launch<E, EPI_GELU>(p, st)
+       : epi == 4 ? launch<E, EPI_DGELU>(p, st) : launch<E, EPI_NONE>(p, st);
   rgbnm_trace_end(slot, st);
   return rc;
 }

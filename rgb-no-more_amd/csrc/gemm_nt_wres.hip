@@ -1,5 +1,6 @@
 // Weight-resident NT GEMM for the K = 192 Linear layers of JPEG-Ti (qkv, fc1, the dGELU product, attention dX):
-//   C[M, N] = epi(A[M,192] . W[N,192]^T), bf16.
+//   C[M, N] = epi(A[M,192] . W[N,192]^T), 16-bit elements T = bf16 or fp16 (same bytes, same LDS layout; the MFMA and the
+//   conversions differ).
 // These GEMMs read 19 MB and write 58-154 MB at B = 256: HBM bound, and with a tile-per-workgroup kernel also
 // latency bound (every workgroup re-fetches its 72 KB weight tile from L2 and has one 16 KB activation tile in
 // flight).  Here one persistent 448-thread workgroup per CU keeps a 192-column weight tile (72 KB, LDS-DMA'd once,
@@ -36,8 +37,9 @@ static_assert(SMEM <= 160 * 1024, "LDS");
 
 enum { EPI_NONE = 0, EPI_RES = 1, EPI_GELU = 2, EPI_DGELU = 4 };
 
+template <typename T>
 struct WresArgs {
-  const bf16* A; const bf16* W; bf16* C; const float* bias; const bf16* R; bf16* C2;
+  const T* A; const T* W; T* C; const float* bias; const T* R; T* C2;
   int lda, ldw, ldc, ldr, ldc2;
   int M, N, ntiles, msplit, tiles_per_split;
 };
@@ -49,8 +51,10 @@ __device__ unsigned long long g_wres_prof[320 * 8 * 32];
 #define PROF(i) do {} while (0)
 #endif
 
-template <int EPI>
-__global__ __launch_bounds__(NTHREADS) void gemm_nt_wres_kernel(WresArgs p) {
+template <typename T, int EPI>
+__global__ __launch_bounds__(NTHREADS) void gemm_nt_wres_kernel(WresArgs<T> p) {
+  using V8 = typename Vec8<T>::type;
+  using V4 = typename Vec4<T>::type;
   constexpr bool HASR = (EPI == EPI_RES || EPI == EPI_DGELU);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* Ws = smem;
@@ -70,7 +74,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_wres_kernel(WresArgs p) {
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, g = lane >> 5;
   unsigned char* Aw = smem + W_BYTES + BIAS_BYTES + 16 + w * A_WAVE;
-  bf16* Cs = reinterpret_cast<bf16*>(Aw);
+  T* Cs = reinterpret_cast<T*>(Aw);
 
   PROF(0);
   // ---- start-up: bias and the resident weight tile by LDS-DMA; tiles t0 .. t0+6 are pre-assigned to the 7 waves
@@ -110,9 +114,9 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_wres_kernel(WresArgs p) {
   // phase behind an s_waitcnt that drained the next tile's prefetch)
   const int woff0 = l31 * ROWB + ((g ^ fl) << 4);
 
-  bf16x8 a[NCH];                                       // the NEXT tile, in flight while the current one is computed
+  V8 a[NCH];                                          // the NEXT tile, in flight while the current one is computed
   auto load_tile = [&](int tt) {
-    const bf16* ab = p.A + (size_t)tt * BMT * p.lda;
+    const T* ab = p.A + (size_t)tt * BMT * p.lda;
     // the three source offsets are recomputed from lane_id_here(): as loop invariants they get hoisted, and in the
     // register-heavy epilogue variants SPILLED -- the reload then sits in front of these loads behind an s_waitcnt
     // vmcnt(0) that drains the wave's in-flight stores and R loads on every tile
@@ -124,7 +128,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_wres_kernel(WresArgs p) {
       src[j] = (pidx / 24) * p.lda + (pidx % 24) * 8;
     }
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) a[j] = *reinterpret_cast<const bf16x8*>(ab + src[j % 3] + (j / 3) * 8 * p.lda);
+    for (int j = 0; j < NCH; ++j) a[j] = *reinterpret_cast<const V8*>(ab + src[j % 3] + (j / 3) * 8 * p.lda);
   };
   auto grab = [&]() -> int {                           // next unclaimed tile of this workgroup (wave-uniform)
     int v = 0;
@@ -135,11 +139,11 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_wres_kernel(WresArgs p) {
   // the first 96-column half of the NEXT tile is requested at the end of a step (behind that tile's A loads, which
   // are needed first anyway); the second half right after the MFMA phase (registers are free then; by the time it is
   // consumed the prefetch issued before it has long landed).
-  bf16x8 r_cur[2][NVEC];
-  auto load_r = [&](int tt, int h, bf16x8 (&r)[NVEC]) {
-    const bf16* rb = p.R + (size_t)tt * BMT * p.ldr + n0 + BNH * h;
+  V8 r_cur[2][NVEC];
+  auto load_r = [&](int tt, int h, V8 (&r)[NVEC]) {
+    const T* rb = p.R + (size_t)tt * BMT * p.ldr + n0 + BNH * h;
 #pragma unroll
-    for (int i = 0; i < NVEC; ++i) r[i] = *reinterpret_cast<const bf16x8*>(rb + r_lane[i % 3] + (i / 3) * 16 * p.ldr);
+    for (int i = 0; i < NVEC; ++i) r[i] = *reinterpret_cast<const V8*>(rb + r_lane[i % 3] + (i / 3) * 16 * p.ldr);
   };
   int t = t0 + w;
   if (t < tend) {
@@ -160,7 +164,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_wres_kernel(WresArgs p) {
     // park the tile in the private buffer (previous tile's staging reads are older LDS instructions of this wave:
     // LDS executes a wave in order), then immediately refill the registers with the tile after it
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) *reinterpret_cast<bf16x8*>(Aw + a_dst[j % 6] + (j / 6) * 16 * ROWB) = a[j];
+    for (int j = 0; j < NCH; ++j) *reinterpret_cast<V8*>(Aw + a_dst[j % 6] + (j / 6) * 16 * ROWB) = a[j];
     const int tn = grab();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (tn < tend) load_tile(tn);
@@ -175,11 +179,11 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_wres_kernel(WresArgs p) {
     asm volatile("" : "+v"(wbase));
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-      Frag<bf16> fa, fb[6];
+      Frag<T> fa, fb[6];
       const int wo = (wbase ^ ((c % 4) << 5)) + 128 * (c / 4);
-      fa.v = *reinterpret_cast<const bf16x8*>(Aw + wo);
+      fa.v = *reinterpret_cast<const V8*>(Aw + wo);
 #pragma unroll
-      for (int b = 0; b < 6; ++b) fb[b].v = *reinterpret_cast<const bf16x8*>(Ws + 32 * b * ROWB + wo);
+      for (int b = 0; b < 6; ++b) fb[b].v = *reinterpret_cast<const V8*>(Ws + 32 * b * ROWB + wo);
 #pragma unroll
       for (int b = 0; b < 6; ++b) mma(acc[b], fb[b], fa);     // swapped: D rows <-> features, D cols <-> tokens
     }
@@ -199,20 +203,20 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_wres_kernel(WresArgs p) {
           const f32x16& ac = acc[3 * h + b];
           f32x4 v = {ac[4 * q + 0], ac[4 * q + 1], ac[4 * q + 2], ac[4 * q + 3]};
           v += *reinterpret_cast<const f32x4*>(Bs + BNH * h + nl);
-          store4<bf16>(Cs + l31 * CP + nl, v);
+          store4<T>(Cs + l31 * CP + nl, v);
         }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       // ---- pass 2: 32 rows x 12 vectors of 8 features, 6 per lane, coalesced 192-byte row pieces
-      bf16* cbase = p.C + (size_t)t * BMT * p.ldc + nh;
-      bf16* c2base = EPI == EPI_GELU ? p.C2 + (size_t)t * BMT * p.ldc2 + nh : nullptr;
+      T* cbase = p.C + (size_t)t * BMT * p.ldc + nh;
+      T* c2base = EPI == EPI_GELU ? p.C2 + (size_t)t * BMT * p.ldc2 + nh : nullptr;
 #pragma unroll
       for (int i = 0; i < NVEC; ++i) {
         const int so = s_lane[i % 3] + (i / 3) * 16 * CP;
-        const bf16x4 c0 = *reinterpret_cast<const bf16x4*>(Cs + so);
-        const bf16x4 c1 = *reinterpret_cast<const bf16x4*>(Cs + so + 4);
-        bf16x8 cv = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
+        const V4 c0 = *reinterpret_cast<const V4*>(Cs + so);
+        const V4 c1 = *reinterpret_cast<const V4*>(Cs + so + 4);
+        V8 cv = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
         if (EPI == EPI_GELU) {
-          bf16x8 dv;
+          V8 dv;
 #pragma unroll
           for (int e = 0; e < 8; e += 2) {
             const f32x2 u = {(float)cv[e], (float)cv[e + 1]};
@@ -222,10 +226,10 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_wres_kernel(WresArgs p) {
 #else
             gelu_pair_fast(u, gv, dgv);
 #endif
-            dv[e] = (bf16)dgv[0];
-            dv[e + 1] = (bf16)dgv[1];
-            cv[e] = (bf16)gv[0];
-            cv[e + 1] = (bf16)gv[1];
+            dv[e] = from_f32<T>(dgv[0]);
+            dv[e + 1] = from_f32<T>(dgv[1]);
+            cv[e] = from_f32<T>(gv[0]);
+            cv[e + 1] = from_f32<T>(gv[1]);
           }
           store_c2(c2base + c2_lane[i % 3] + (i / 3) * 16 * p.ldc2, dv);
         }
@@ -235,10 +239,10 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_wres_kernel(WresArgs p) {
             float v = (float)cv[e];
             if (EPI == EPI_RES) v += (float)r_cur[h][i][e];
             else v *= (float)r_cur[h][i][e];
-            cv[e] = (bf16)v;
+            cv[e] = from_f32<T>(v);
           }
         }
-        *reinterpret_cast<bf16x8*>(cbase + c_lane[i % 3] + (i / 3) * 16 * p.ldc) = cv;
+        *reinterpret_cast<V8*>(cbase + c_lane[i % 3] + (i / 3) * 16 * p.ldc) = cv;
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // staging reads done before the buffer is rewritten
     }
@@ -253,31 +257,25 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_wres_kernel(WresArgs p) {
   }
 }
 
-template <int EPI>
-int launch(const WresArgs& p, int grid, hipStream_t st) {
+template <typename T, int EPI>
+int launch(const WresArgs<T>& p, int grid, hipStream_t st) {
   static DevOnce attr;
   if (attr.need()) {
-    if (hipFuncSetAttribute((const void*)gemm_nt_wres_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) !=
+    if (hipFuncSetAttribute((const void*)gemm_nt_wres_kernel<T, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) !=
         hipSuccess)
       return RGBNM_ELAUNCH;
     attr.done();
   }
-  hipLaunchKernelGGL((gemm_nt_wres_kernel<EPI>), dim3(grid), dim3(NTHREADS), SMEM, st, p);
+  hipLaunchKernelGGL((gemm_nt_wres_kernel<T, EPI>), dim3(grid), dim3(NTHREADS), SMEM, st, p);
   LAUNCH_CHECK();
   return RGBNM_OK;
 }
 
-}  // namespace
-
-// returns 1 when the shape is not eligible (caller falls back to the tile-per-workgroup kernel)
-int rgbnm_launch_nt_wres(int epi, const void* A, int lda, const void* W, int ldw, void* C, int ldc, const float* bias,
-                         const void* R, int ldr, void* C2, int ldc2, int M, int N, int Kdim, hipStream_t st) {
-  if (Kdim != K || N % BN || M % BMT || lda % 8 || ldw % 8 || ldc % 8 || M < 4096) return 1;
-  if (epi != EPI_NONE && epi != EPI_RES && epi != EPI_GELU && epi != EPI_DGELU) return 1;
-  if ((epi == EPI_RES || epi == EPI_DGELU) && (!R || ldr % 8)) return 1;
-  if (epi == EPI_GELU && (!C2 || ldc2 % 8)) return 1;
-  WresArgs p;
-  p.A = (const bf16*)A; p.W = (const bf16*)W; p.C = (bf16*)C; p.bias = bias; p.R = (const bf16*)R; p.C2 = (bf16*)C2;
+template <typename T>
+int launch_t(int epi, const void* A, int lda, const void* W, int ldw, void* C, int ldc, const float* bias, const void* R, int ldr,
+             void* C2, int ldc2, int M, int N, hipStream_t st) {
+  WresArgs<T> p;
+  p.A = (const T*)A; p.W = (const T*)W; p.C = (T*)C; p.bias = bias; p.R = (const T*)R; p.C2 = (T*)C2;
   p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr; p.ldc2 = ldc2; p.M = M; p.N = N;
   p.ntiles = N / BN;
   const int mtiles = M / BMT;
@@ -294,13 +292,27 @@ int rgbnm_launch_nt_wres(int epi, const void* A, int lda, const void* W, int ldw
                                                               (epi != EPI_NONE ? mn * 2.0 : 0.0), st);
   int rc;
   switch (epi) {
-    case EPI_NONE: rc = launch<EPI_NONE>(p, grid, st); break;
-    case EPI_RES: rc = launch<EPI_RES>(p, grid, st); break;
-    case EPI_GELU: rc = launch<EPI_GELU>(p, grid, st); break;
-    default: rc = launch<EPI_DGELU>(p, grid, st); break;
+    case EPI_NONE: rc = launch<T, EPI_NONE>(p, grid, st); break;
+    case EPI_RES: rc = launch<T, EPI_RES>(p, grid, st); break;
+    case EPI_GELU: rc = launch<T, EPI_GELU>(p, grid, st); break;
+    default: rc = launch<T, EPI_DGELU>(p, grid, st); break;
   }
   rgbnm_trace_end(slot, st);
   return rc;
+}
+
+}  // namespace
+
+// returns 1 when the shape is not eligible (caller falls back to the tile-per-workgroup kernel)
+int rgbnm_launch_nt_wres(int dtype, int epi, const void* A, int lda, const void* W, int ldw, void* C, int ldc, const float* bias,
+                         const void* R, int ldr, void* C2, int ldc2, int M, int N, int Kdim, hipStream_t st) {
+  if (dtype != DT_BF16 && dtype != DT_F16) return 1;
+  if (Kdim != K || N % BN || M % BMT || lda % 8 || ldw % 8 || ldc % 8 || M < 4096) return 1;
+  if (epi != EPI_NONE && epi != EPI_RES && epi != EPI_GELU && epi != EPI_DGELU) return 1;
+  if ((epi == EPI_RES || epi == EPI_DGELU) && (!R || ldr % 8)) return 1;
+  if (epi == EPI_GELU && (!C2 || ldc2 % 8)) return 1;
+  if (dtype == DT_F16) return launch_t<f16>(epi, A, lda, W, ldw, C, ldc, bias, R, ldr, C2, ldc2, M, N, st);
+  return launch_t<bf16>(epi, A, lda, W, ldw, C, ldc, bias, R, ldr, C2, ldc2, M, N, st);
 }
 
 #ifdef WRES_PROF

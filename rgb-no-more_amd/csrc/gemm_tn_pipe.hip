@@ -1,4 +1,4 @@
-// Weight-gradient GEMM, pipelined (bf16): part[s][No,Ki] = dY[tok range s, No]^T . X[tok range s, Ki]
+// Weight-gradient GEMM, pipelined (16-bit operands E = bf16 or fp16: same bytes in LDS, another MFMA): part[s][No,Ki] = dY[tok range s, No]^T . X[tok range s, Ki]
 // (reference: the dW of every nn.Linear backward, models/plainvit.py:195,441,443,487,490).
 //
 // HBM-bound op (reads every activation once, output is tiny), so the design is a memory pipeline:
@@ -35,6 +35,8 @@ constexpr int STAGE = A_STAGE + B_STAGE;       // 40 KB
 constexpr int NSTAGE = TN_NSTAGE;              // 3: two tiles (80 KB) in flight; 4: three (120 KB), all 160 KB of LDS
 constexpr int SMEM = NSTAGE * STAGE;           // 120 KB
 
+// (operand pointers below are typed bf16 for their 2-byte address arithmetic only: the kernels read them through LDS-DMA as bytes
+// and form Frag<E>)
 struct TnPipe {
   const bf16* dY; const bf16* X; float* part; float* bpart;
   int ldy, ldx, M, No, Ki, S, kt_per_split, rtiles, ctiles;
@@ -62,9 +64,14 @@ struct TnGroup {
 };
 
 // all 8 transpose reads of chunk C (16 tokens) for this wave: 1 A fragment + 3 B fragments
-template <int C>
-__device__ __forceinline__ void tr_chunk(unsigned aA, unsigned aB0, unsigned aB1, unsigned aB2, Frag<bf16>& fa,
-                                         Frag<bf16> (&fb)[3]) {
+template <typename E> __device__ __forceinline__ typename Vec8<E>::type pack8t(u32x2 lo, u32x2 hi) {
+  u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
+  return __builtin_bit_cast(typename Vec8<E>::type, v);
+}
+
+template <int C, typename E>
+__device__ __forceinline__ void tr_chunk(unsigned aA, unsigned aB0, unsigned aB1, unsigned aB2, Frag<E>& fa,
+                                         Frag<E> (&fb)[3]) {
   u32x2 al, ah, b0l, b0h, b1l, b1h, b2l, b2h;
   asm volatile(
       "ds_read_b64_tr_b16 %0, %8 offset:%12\n\t"
@@ -81,23 +88,23 @@ __device__ __forceinline__ void tr_chunk(unsigned aA, unsigned aB0, unsigned aB1
         "i"(C * 16 * B_ROW), "i"(C * 16 * B_ROW + 4 * B_ROW)
       : "memory");
   __builtin_amdgcn_sched_barrier(0);
-  fa.v = pack8(al, ah);
-  fb[0].v = pack8(b0l, b0h);
-  fb[1].v = pack8(b1l, b1h);
-  fb[2].v = pack8(b2l, b2h);
+  fa.v = pack8t<E>(al, ah);
+  fb[0].v = pack8t<E>(b0l, b0h);
+  fb[1].v = pack8t<E>(b1l, b1h);
+  fb[2].v = pack8t<E>(b2l, b2h);
 }
 
 // Experiments (round 5, TN_FPIPE; default 0 = the loop above's read - wait - MFMA per 16 tokens, two waves per SIMD covering each
 // other): 1 = the same eight reads through the builtin with the next chunk's reads under the current MFMAs -- MEASURED +50 % on the
 // launch: the compiler drains vmcnt in front of every builtin LDS read that follows an LDS-DMA, which empties the ring;
 // 2 = asm reads without the wait, lgkmcnt counted by hand: +-0.5 % (the kernel waits for its operand stream, not for LDS).
-template <int C>
+template <int C, typename E>
 __device__ __forceinline__ void tr_chunk_b(const unsigned char* sp, unsigned oA, unsigned oB0, unsigned oB1, unsigned oB2,
-                                           Frag<bf16>& fa, Frag<bf16> (&fb)[3]) {
-  fa.v = pack8(tr_read(sp, oA + C * 16 * A_ROW), tr_read(sp, oA + C * 16 * A_ROW + 4 * A_ROW));
-  fb[0].v = pack8(tr_read(sp, oB0 + C * 16 * B_ROW), tr_read(sp, oB0 + C * 16 * B_ROW + 4 * B_ROW));
-  fb[1].v = pack8(tr_read(sp, oB1 + C * 16 * B_ROW), tr_read(sp, oB1 + C * 16 * B_ROW + 4 * B_ROW));
-  fb[2].v = pack8(tr_read(sp, oB2 + C * 16 * B_ROW), tr_read(sp, oB2 + C * 16 * B_ROW + 4 * B_ROW));
+                                           Frag<E>& fa, Frag<E> (&fb)[3]) {
+  fa.v = pack8t<E>(tr_read(sp, oA + C * 16 * A_ROW), tr_read(sp, oA + C * 16 * A_ROW + 4 * A_ROW));
+  fb[0].v = pack8t<E>(tr_read(sp, oB0 + C * 16 * B_ROW), tr_read(sp, oB0 + C * 16 * B_ROW + 4 * B_ROW));
+  fb[1].v = pack8t<E>(tr_read(sp, oB1 + C * 16 * B_ROW), tr_read(sp, oB1 + C * 16 * B_ROW + 4 * B_ROW));
+  fb[2].v = pack8t<E>(tr_read(sp, oB2 + C * 16 * B_ROW), tr_read(sp, oB2 + C * 16 * B_ROW + 4 * B_ROW));
 }
 
 #ifndef TN_FPIPE
@@ -124,6 +131,7 @@ __device__ __forceinline__ void tr_chunk_nw(unsigned aA, unsigned aB0, unsigned 
 }
 template <bool V> struct BoolTag { static constexpr bool value = V; };
 
+template <typename E>
 __global__ __launch_bounds__(512) void gemm_tn_pipe_kernel(TnGroup grp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // 256 workgroups, block b runs on XCD b % 8: unit u = (b % 8) * 32 + b / 8 keeps consecutive units -- the tiles of one
@@ -210,9 +218,9 @@ __global__ __launch_bounds__(512) void gemm_tn_pipe_kernel(TnGroup grp) {
     acc[0][r] = 0.f; acc[1][r] = 0.f; acc[2][r] = 0.f; accb[r] = 0.f;
   }
   const bool do_bias = (p.bpart != nullptr) && (ct == 0) && (wn == 0);
-  Frag<bf16> ones;
+  Frag<E> ones;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) ones.v[e] = (bf16)1.0f;
+  for (int e = 0; e < 8; ++e) ones.v[e] = (E)1.0f;
 
   int st_issue = 0, st_comp = 0;
 #pragma unroll
@@ -250,11 +258,11 @@ __global__ __launch_bounds__(512) void gemm_tn_pipe_kernel(TnGroup grp) {
       }                                                                              \
       __builtin_amdgcn_sched_barrier(0);                                             \
       {                                                                              \
-        Frag<bf16> fa, fb0, fb1, fb2;                                                \
-        fa.v = pack8(r[C & 1][0], r[C & 1][1]);                                      \
-        fb0.v = pack8(r[C & 1][2], r[C & 1][3]);                                     \
-        fb1.v = pack8(r[C & 1][4], r[C & 1][5]);                                     \
-        fb2.v = pack8(r[C & 1][6], r[C & 1][7]);                                     \
+        Frag<E> fa, fb0, fb1, fb2;                                                   \
+        fa.v = pack8t<E>(r[C & 1][0], r[C & 1][1]);                                  \
+        fb0.v = pack8t<E>(r[C & 1][2], r[C & 1][3]);                                 \
+        fb1.v = pack8t<E>(r[C & 1][4], r[C & 1][5]);                                 \
+        fb2.v = pack8t<E>(r[C & 1][6], r[C & 1][7]);                                 \
         mma(acc[0], fa, fb0);                                                        \
         mma(acc[1], fa, fb1);                                                        \
         mma(acc[2], fa, fb2);                                                        \
@@ -268,7 +276,7 @@ __global__ __launch_bounds__(512) void gemm_tn_pipe_kernel(TnGroup grp) {
       // counted lgkmcnt waits let the next chunk's eight reads stay in flight)
       const unsigned char* sp = smem + st_comp * STAGE;
       st_comp = st_comp == NSTAGE - 1 ? 0 : st_comp + 1;
-      Frag<bf16> fa[2], fb[2][3];
+      Frag<E> fa[2], fb[2][3];
       tr_chunk_b<0>(sp, oA, oB0, oB1, oB2, fa[0], fb[0]);
       __builtin_amdgcn_sched_barrier(0);
 #define CHUNK(C)                                                                     \
@@ -292,7 +300,7 @@ __global__ __launch_bounds__(512) void gemm_tn_pipe_kernel(TnGroup grp) {
       const unsigned sb = lds0 + st_comp * STAGE;
       st_comp = st_comp == NSTAGE - 1 ? 0 : st_comp + 1;
       const unsigned aA = sb + oA, aB0 = sb + oB0, aB1 = sb + oB1, aB2 = sb + oB2;
-      Frag<bf16> fa, fb[3];
+      Frag<E> fa, fb[3];
   #define CHUNK(C)                                   \
       tr_chunk<C>(aA, aB0, aB1, aB2, fa, fb);        \
       mma(acc[0], fa, fb[0]);                        \
@@ -379,6 +387,7 @@ __device__ __forceinline__ void trw_chunk(unsigned aA0, unsigned aA1, unsigned a
   __builtin_amdgcn_sched_barrier(0);
 }
 
+template <typename E>
 __global__ __launch_bounds__(512) void gemm_tn_wide_kernel(TnGroup grp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int u = (blockIdx.x & 7) * 32 + (blockIdx.x >> 3);        // XCD-contiguous unit numbering (see the narrow kernel)
@@ -471,9 +480,9 @@ __global__ __launch_bounds__(512) void gemm_tn_wide_kernel(TnGroup grp) {
     }
   }
   const bool do_bias = (bpart != nullptr) && (ct == 0) && (wn == 0);
-  Frag<bf16> ones;
+  Frag<E> ones;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) ones.v[e] = (bf16)1.0f;
+  for (int e = 0; e < 8; ++e) ones.v[e] = (E)1.0f;
 
   int st_issue = 0, st_comp = 0;
 #pragma unroll
@@ -501,9 +510,9 @@ __global__ __launch_bounds__(512) void gemm_tn_wide_kernel(TnGroup grp) {
 #define WCHUNK(C)                                                                                     \
       trw_chunk<C>(sb + oA[0], sb + oA[1], sb + oA[2], sb + oB[0], sb + oB[1], sb + oB[2], r);        \
       {                                                                                               \
-        Frag<bf16> fa[3], fb[3];                                                                      \
-        fa[0].v = pack8(r[0], r[1]); fa[1].v = pack8(r[2], r[3]); fa[2].v = pack8(r[4], r[5]);        \
-        fb[0].v = pack8(r[6], r[7]); fb[1].v = pack8(r[8], r[9]); fb[2].v = pack8(r[10], r[11]);      \
+        Frag<E> fa[3], fb[3];                                                                         \
+        fa[0].v = pack8t<E>(r[0], r[1]); fa[1].v = pack8t<E>(r[2], r[3]); fa[2].v = pack8t<E>(r[4], r[5]);     \
+        fb[0].v = pack8t<E>(r[6], r[7]); fb[1].v = pack8t<E>(r[8], r[9]); fb[2].v = pack8t<E>(r[10], r[11]);   \
         _Pragma("unroll") for (int i = 0; i < 3; ++i) {                                               \
           _Pragma("unroll") for (int b = 0; b < 3; ++b) mma(acc[i][b], fa[i], fb[b]);                 \
           if constexpr (BIAS) mma(accb[i], fa[i], ones);                                              \
@@ -561,12 +570,15 @@ int tn_fill(TnPipe& p, const void* dY, int ldy, const void* X, int ldx, float* p
 }  // namespace
 
 // jobs[0..n): same M; returns 1 when a job is not eligible (nothing launched), S (common split count) through S_out
-int rgbnm_launch_tn_pipe_group(const RgbnmTnJob* jobs, int n, int* S_out, hipStream_t st, int* direct_out) {
+namespace {
+
+template <typename E>
+int tn_pipe_group(const RgbnmTnJob* jobs, int n, int* S_out, hipStream_t st, int* direct_out) {
   if (direct_out) *direct_out = 0;
   if (n < 1 || n > TN_MAXJOBS) return RGBNM_EINVAL;
   static DevOnce attr_set;
   if (attr_set.need()) {
-    if (hipFuncSetAttribute((const void*)gemm_tn_pipe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)gemm_tn_pipe_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess)
       return RGBNM_ELAUNCH;
     attr_set.done();
   }
@@ -598,7 +610,7 @@ int rgbnm_launch_tn_pipe_group(const RgbnmTnJob* jobs, int n, int* S_out, hipStr
   if (wide) {
     static DevOnce attr_w;
     if (attr_w.need()) {
-      if (hipFuncSetAttribute((const void*)gemm_tn_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WSMEM) != hipSuccess)
+      if (hipFuncSetAttribute((const void*)gemm_tn_wide_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, WSMEM) != hipSuccess)
         return RGBNM_ELAUNCH;
       attr_w.done();
     }
@@ -671,17 +683,27 @@ int rgbnm_launch_tn_pipe_group(const RgbnmTnJob* jobs, int n, int* S_out, hipStr
     }
   }
   const int slot = rgbnm_trace_begin(TR_TN, flops, bytes, st);
-  if (wide) hipLaunchKernelGGL(gemm_tn_wide_kernel, dim3(256), dim3(512), WSMEM, st, g);
-  else hipLaunchKernelGGL(gemm_tn_pipe_kernel, dim3(256), dim3(512), SMEM, st, g);
+  if (wide) hipLaunchKernelGGL(gemm_tn_wide_kernel<E>, dim3(256), dim3(512), WSMEM, st, g);
+  else hipLaunchKernelGGL(gemm_tn_pipe_kernel<E>, dim3(256), dim3(512), SMEM, st, g);
   rgbnm_trace_end(slot, st);
   LAUNCH_CHECK();
   return RGBNM_OK;
 }
 
-int rgbnm_launch_tn_pipe(const void* dY, int ldy, const void* X, int ldx, float* part, float* bpart, int M, int No,
+}  // namespace
+
+// dtype: DT_BF16 or DT_F16, the element type of every job's operands
+int rgbnm_launch_tn_pipe_group(int dtype, const RgbnmTnJob* jobs, int n, int* S_out, hipStream_t st, int* direct_out) {
+  if (dtype == DT_F16) return tn_pipe_group<f16>(jobs, n, S_out, st, direct_out);
+  if (dtype == DT_BF16) return tn_pipe_group<bf16>(jobs, n, S_out, st, direct_out);
+  if (direct_out) *direct_out = 0;
+  return 1;
+}
+
+int rgbnm_launch_tn_pipe(int dtype, const void* dY, int ldy, const void* X, int ldx, float* part, float* bpart, int M, int No,
                          int Ki, int* S_out, hipStream_t st, int smax) {
   RgbnmTnJob j;
   j.dY = dY; j.X = X; j.part = part; j.bpart = bpart; j.ldy = ldy; j.ldx = ldx; j.M = M; j.No = No; j.Ki = Ki;
   j.dW = nullptr; j.db = nullptr; j.perm_heads = 0; j.accumulate = 0; j.smax = smax;
-  return rgbnm_launch_tn_pipe_group(&j, 1, S_out, st);
+  return rgbnm_launch_tn_pipe_group(dtype, &j, 1, S_out, st);
 }

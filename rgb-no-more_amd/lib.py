@@ -234,6 +234,16 @@ def check(rc, what=""):
         raise RgbnmError(f"{what}: rgbnm error {rc}: {msg}")
 
 
+def set_option(name, value):
+    """Set a runtime option of the library (include/rgbnm.h, rgbnm_set_option), e.g. set_option("f16_tuned", 1)."""
+    check(lib().rgbnm_set_option(name.encode(), int(value)), f"option {name}")
+
+
+def get_option(name):
+    """Current value of a runtime option (rgbnm_get_option; -1: no such option)."""
+    return lib().rgbnm_get_option(name.encode())
+
+
 def dt_of(t):
     if t == torch.float32:
         return DT_F32

@@ -260,12 +260,18 @@ def _nt(epi, x, Wsh, pair, bias=None, R=None, want_c2=False, bias_prep=None):
     return y.view(M, N2 // 2), None if c2 is None else c2.view(M, N2 // 2)
 
 
+def _tuned16(dt):
+    """Does this compute dtype run on the GEMM kernels tuned for 16-bit operands -- and with them on the grouped weight-gradient
+    launches?  bf16 always; fp16 when the library option f16_tuned is set (default 0: fp16 takes the generic kernels)."""
+    return dt == torch.bfloat16 or (dt == torch.float16 and L.get_option("f16_tuned") != 0)
+
+
 def _tn_issue(dy, x, want_bias, pair, slot=0):
     """Launch (or, inside a rgbnm_gemm_tn_group bracket, queue) one weight-gradient GEMM; _tn_finish turns what it returns into
     (dW, db) once the results exist."""
     br = _ACTIVE[0]
     if not pair:
-        queued = br is not None and br.active and dy.dtype == torch.bfloat16
+        queued = br is not None and br.active and _tuned16(dy.dtype)
         return _gemm_tn(dy, x, want_bias, slot, br.keep if queued else None) + (0, 0)
     M, N, K = dy.shape[0], dy.shape[1], x.shape[1]
     return _gemm_tn(dy.view(M // 2, 2 * N), x.view(M // 2, 2 * K), want_bias, slot) + (N, K)   # [[e.e, e.o], [o.e, o.o]] row parities
@@ -394,7 +400,7 @@ class _MlpFn(torch.autograd.Function):
         dy = dy.contiguous()
         du, _ = _nt(L.EPI_DGELU, dy, ctx.sh2[1], ctx.p2, None, R=gp)
         # both weight gradients in one launch (rgbnm.h: rgbnm_gemm_tn_group_*): half the split count, one reduction
-        grouped = dy.dtype == torch.bfloat16
+        grouped = _tuned16(dy.dtype)
         br = _ACTIVE[0]
         if br is not None and br.active and grouped and not (ctx.p1 or ctx.p2):
             # inside the backward-wide bracket (_DwBracket): both GEMMs join the queue of their stage
@@ -402,7 +408,7 @@ class _MlpFn(torch.autograd.Function):
             t1 = _tn_issue(du, x, True, False, 1)
         else:
             if br is not None and br.active:
-                br.pause()                     # row-paired (stage 1), fp32 or fp16: what is queued runs first
+                br.pause()                     # row-paired (stage 1), fp32 or untuned fp16: what is queued runs first
             if grouped:
                 L.lib().rgbnm_gemm_tn_group_begin()
             try:
@@ -826,7 +832,7 @@ class SwinTransformerV2(FlatParamModule):
         cdt = self.compute_dtype
         if cdt is None:
             cdt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else torch.float32
-        # (fp16 runs the generic GEMMs: the bf16-tuned ones, the grouped dW bracket and the held reductions are bf16 only)
+        # (fp16 runs the generic GEMMs unless the library option f16_tuned is set: then the tuned ones and the grouped dW bracket, like bf16)
         if cdt not in (torch.float32, torch.bfloat16, torch.float16):
             raise NotImplementedError(f"compute dtype {cdt}: the MI355X path implements fp32, bf16 and fp16")
         dev = y.device
@@ -846,7 +852,7 @@ class SwinTransformerV2(FlatParamModule):
         # the weight-gradient GEMMs of the whole backward in one bracket (_DwBracket): only when nobody reads a gradient before the
         # pass is over, and when its first and last nodes will both run
         br = None
-        if (self.group_dw_backward and torch.is_grad_enabled() and cdt == torch.bfloat16 and self._grad_sync is None
+        if (self.group_dw_backward and torch.is_grad_enabled() and _tuned16(cdt) and self._grad_sync is None
                 and self.head.weight.requires_grad and pe.projection[0].weight.requires_grad):
             br = self.__dict__.setdefault("_dw_bracket", _DwBracket())
             hb = self.__dict__.setdefault("_hold_bracket", _HoldBracket())

@@ -1,8 +1,10 @@
 #!/usr/bin/env python
-"""Time the training step of the ViT (JPEG-Ti / JPEG-S) or of SwinV2-T in its three compute configurations, in one process,
+"""Time the training step of the ViT (JPEG-Ti / JPEG-S) or of SwinV2-T in its four compute configurations, in one process,
 alternating:
 
-  fp16          autocast(float16): fp16 activations on the generic kernels (the bf16-tuned kernels are bf16 only)
+  fp16          autocast(float16) with the library's defaults: fp16 activations on the generic kernels
+  fp16_tuned    autocast(float16) with the option f16_tuned = 1: the plain GEMMs (small-M, weight-resident, row-panel, pipelined and
+                grouped weight gradients) on the kernels tuned for 16-bit operands; SwinV2-T: also group_dw_backward + hold_reductions
   bf16_generic  bf16 with exactly the bf16-only kernels switched off (BF16_ONLY_OPTS; SwinV2-T: also the backward-wide weight-
                 gradient bracket and the held reductions, group_dw_backward): the kernel set fp16 runs
   bf16          bf16 with every option at its default (what bench.py times; SwinV2-T: group_dw_backward + hold_reductions on,
@@ -32,14 +34,17 @@ from rgb_no_more_amd import custom_transforms as CT, detfill, lib as L  # noqa: 
 from bench import synth_coefficients  # noqa: E402
 
 ARCH = {"vitti": (192, 3), "vits": (384, 6), "swinv2t": (96, 3)}
-# every library option that selects a bf16-only kernel (rgbnm.h: the fp16 entries skip them)
+# every library option that selects a kernel fp16 does not reach under default options: bf16-only kernels, and the tuned plain GEMMs
+# (nt_kpipe, nt_wres, nt_small, tn_pipe, tn_wide) that fp16 takes only with f16_tuned = 1
 BF16_ONLY_OPTS = ("fwd_chain", "bwd_chain", "nt_kpipe", "nt_wres", "nt_small", "tn_pipe", "tn_wide", "mlp_fuse", "mlp_bwd",
                   "attn_v2", "ln_fuse")
-CONFIGS = ("fp16", "bf16_generic", "bf16")
+CONFIGS = ("fp16", "fp16_tuned", "bf16_generic", "bf16")
+F16_CONFIGS = ("fp16", "fp16_tuned")
 
 
-def set_opts(defaults, off):
+def set_opts(defaults, off, f16_tuned=0):
     lib = L.lib()
+    lib.rgbnm_set_option(b"f16_tuned", f16_tuned)
     for k, v in defaults.items():
         lib.rgbnm_set_option(k.encode(), 0 if (off and k in BF16_ONLY_OPTS) else v)
 
@@ -59,9 +64,9 @@ def swin_logit_error(cfg, defaults):
                       strict=False)
     y = torch.from_numpy(detfill.normalish((256, 1, 32, 32, 8, 8), 171)).cuda()
     c = torch.from_numpy(detfill.normalish((256, 2, 16, 16, 8, 8), 172)).cuda()
-    set_opts(defaults, cfg == "bf16_generic")
+    set_opts(defaults, cfg == "bf16_generic", int(cfg == "fp16_tuned"))
     m.train()
-    with torch.autocast("cuda", dtype=torch.float16 if cfg == "fp16" else torch.bfloat16):
+    with torch.autocast("cuda", dtype=torch.float16 if cfg in F16_CONFIGS else torch.bfloat16):
         out = m(y, c)
     torch.cuda.synchronize()
     set_opts(defaults, False)
@@ -76,9 +81,9 @@ def logit_error(cfg, defaults):
     m.load_state_dict({k: torch.from_numpy(v) for k, v in detfill.fill_state_dict(shapes, base_seed=1).items()})
     y = torch.from_numpy(detfill.normalish((256, 1, 28, 28, 8, 8), 71)).cuda()
     c = torch.from_numpy(detfill.normalish((256, 2, 14, 14, 8, 8), 72)).cuda()
-    set_opts(defaults, cfg == "bf16_generic")
+    set_opts(defaults, cfg == "bf16_generic", int(cfg == "fp16_tuned"))
     m.train()
-    with torch.autocast("cuda", dtype=torch.float16 if cfg == "fp16" else torch.bfloat16):
+    with torch.autocast("cuda", dtype=torch.float16 if cfg in F16_CONFIGS else torch.bfloat16):
         out = m(y, c)
     torch.cuda.synchronize()
     set_opts(defaults, False)
@@ -117,7 +122,7 @@ def main():
         legs = {}
         for cfg in CONFIGS:
             adt = torch.bfloat16 if cfg == "bf16" else torch.float32          # augment output (no fp16 augment output)
-            cdt = torch.float16 if cfg == "fp16" else torch.bfloat16
+            cdt = torch.float16 if cfg in F16_CONFIGS else torch.bfloat16
             aug = CT.TrainTransform_DCT(size=32 if swin else 28, out_dtype=adt)
             mix = rg.cls_transforms.RandomMixup_DCT(1000, alpha=0.2)
             mix.out_dtype = adt
@@ -125,9 +130,9 @@ def main():
             legs[cfg] = (aug, CT.FastParamSampler(aug, seed=1234), mix, cdt)
 
         def configure(cfg):
-            set_opts(defaults, cfg == "bf16_generic")
-            if swin:                            # the backward-wide bracket and the held reductions: bf16 default only
-                model.group_dw_backward = model.hold_reductions = cfg == "bf16"
+            set_opts(defaults, cfg == "bf16_generic", int(cfg == "fp16_tuned"))
+            if swin:                            # the backward-wide bracket and the held reductions: on the tuned kernel sets only
+                model.group_dw_backward = model.hold_reductions = cfg in ("bf16", "fp16_tuned")
 
         def step(cfg):
             aug, sampler, mix, cdt = legs[cfg]
@@ -172,6 +177,8 @@ def main():
                      "nonfinite_blocks": nonfinite[cfg]} for cfg, v in ms.items()}
         out["fp16_over_bf16_generic"] = out["fp16"]["step_ms_median"] / out["bf16_generic"]["step_ms_median"]
         out["fp16_over_bf16"] = out["fp16"]["step_ms_median"] / out["bf16"]["step_ms_median"]
+        out["fp16_tuned_over_fp16"] = out["fp16_tuned"]["step_ms_median"] / out["fp16"]["step_ms_median"]
+        out["fp16_tuned_over_bf16"] = out["fp16_tuned"]["step_ms_median"] / out["bf16"]["step_ms_median"]
         res[arch] = out
         print(f"{arch}: " + ", ".join(f"{k} {v['step_ms_median']:.3f} ms" for k, v in out.items() if isinstance(v, dict)), file=sys.stderr)
         del model, opt
