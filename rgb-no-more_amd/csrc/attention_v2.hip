@@ -42,12 +42,8 @@ __device__ __forceinline__ void dma_matrix(const bf16* __restrict__ src, int ld,
 // MFMA groups of one 32-row tile with their row fragments in a PINNED order (sched_barrier after every step).  Left alone the
 // compiler emits read - wait - MFMA with ONE fragment buffer: an exposed LDS latency per MFMA (36 of attn3_fwd's 80 MFMAs, 50 of
 // attn3_bwd's 196).  row_mma4: one accumulator, the four fragments requested together; row_pair_mma (tile128.h): two accumulators.
-// Same MFMA order per accumulator: same bits.  -DAV2_ROWPIPE=0: the plain loops (experiments).
-#ifndef AV2_ROWPIPE
-#define AV2_ROWPIPE 1
-#endif
+// Same MFMA order per accumulator as the plain loops: same bits.
 __device__ __forceinline__ void row_mma4(f32x16& acc, const unsigned char* arr, unsigned rb, int t, const Frag<bf16> (&x)[4]) {
-#if AV2_ROWPIPE
   Frag<bf16> f[4];
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -56,10 +52,6 @@ __device__ __forceinline__ void row_mma4(f32x16& acc, const unsigned char* arr, 
 #pragma unroll
   for (int c = 0; c < 4; ++c) mma(acc, f[c], x[c]);
   __builtin_amdgcn_sched_barrier(0);
-#else
-#pragma unroll
-  for (int c = 0; c < 4; ++c) mma(acc, rowfrag_x(arr, rb, t, c), x[c]);
-#endif
 }
 
 // MFMA operand with the head dim as reduction axis: lane <-> token row (32t + l31), 32-byte chunk c, half g.
@@ -629,7 +621,7 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __rest
           f32x16 sa, da;
 #pragma unroll
           for (int r = 0; r < 16; ++r) { sa[r] = 0.f; da[r] = 0.f; }
-          row_pair_mma<AV2_ROWPIPE != 0>(sa, da, Ks, Vs, rb, t, qf, gf);
+          row_pair_mma(sa, da, Ks, Vs, rb, t, qf, gf);
           float ds[16];
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
@@ -680,7 +672,7 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __rest
           f32x16 sa, da;
 #pragma unroll
           for (int r = 0; r < 16; ++r) { sa[r] = 0.f; da[r] = 0.f; }
-          row_pair_mma<AV2_ROWPIPE != 0>(sa, da, Qs, Gs, rb, t, kf, vf);
+          row_pair_mma(sa, da, Qs, Gs, rb, t, kf, vf);
           float pp[16], ds[16];
 #pragma unroll
           for (int q4 = 0; q4 < 4; ++q4) {   // accumulator rows 4 q4 .. 4 q4 + 3 = queries t*32 + 8 q4 + 4 g + 0..3

@@ -23,15 +23,10 @@ __device__ __forceinline__ short clamp_s(int v) { return (short)(v < CMIN ? CMIN
 // image (89 us) while a third of the chip idled.  Every image is a list of equal items (/2: two output blocks; identity: eight
 // blocks; x2: one input block), an image's cost is items x weight, and every wave of the grid takes the items whose start falls
 // into its equal share of the batch's total cost (prefix sums over the batch in LDS, recomputed by every workgroup: B loads).
-#ifndef AUG_K_HALF
+// cost weights per item of a /2, an identity, a x2 image (tools/aug_prof.py).  Macros, fixed: tests/augment_ref.py reads these lines
 #define AUG_K_HALF 9
-#endif
-#ifndef AUG_K_ID
 #define AUG_K_ID 8
-#endif
-#ifndef AUG_K_DBL
 #define AUG_K_DBL 12
-#endif
 constexpr int UNITS = S_Y * S_Y + 2 * S_C * S_C;          // output blocks per image: 1176 (S = 28) / 1536 (S = 32)
 constexpr int N_HALF = UNITS / 2, N_ID = UNITS / 8, N_DBL = UNITS / 4;
 static_assert(UNITS % 8 == 0 && (S_Y * S_Y) % 2 == 0 && (S_C * S_C) % 2 == 0 && S_Y % 2 == 0 && S_C % 2 == 0, "item shapes");

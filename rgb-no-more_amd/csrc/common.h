@@ -16,15 +16,6 @@ typedef f16 f16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Timing experiments that produce WRONG numbers (kernels without their stores, their GELU, their LayerNorm ...: the sensitivity
-// builds of DESIGN_NOTES.md 9) exist as -D switches in the kernel sources; a build that defines one must also say
-// -DRGBNM_EXPERIMENTS, so that no release or test build can carry one by accident.
-#if (defined(X_NOLN) || defined(X_NOGELU) || defined(X_NOEXP) || defined(X_NOSAVE) || defined(X_HALFW) || defined(X_NOATTN) || \
-     defined(X_NOMLP) || defined(X_NOPIPE) || defined(KPX_NOGELU) || defined(KPX_NOC2) || defined(KPX_NOSTORE)) &&             \
-    !defined(RGBNM_EXPERIMENTS)
-#error "a wrong-numbers timing switch (X_NO* / X_HALFW / KPX_NO*) is defined without -DRGBNM_EXPERIMENTS"
-#endif
-
 #define RGBNM_OK 0
 #define RGBNM_EINVAL (-1)
 #define RGBNM_ELAUNCH (-2)
@@ -206,24 +197,9 @@ __device__ __forceinline__ float dgelu_fast(float x) {
 }
 
 // gelu'(u), the second output of the fc1 + GELU epilogues: nobody reads it before the backward pass -- a non-temporal store keeps
-// it from pushing the rows the NEXT launch reads (gelu(u)) out of L2.  -DNT_C2=0: plain store (experiments).
-#ifndef NT_C2
-#define NT_C2 1
-#endif
-__device__ __forceinline__ void store_c2(bf16* ptr, const bf16x8& v) {
-#if NT_C2
-  __builtin_nontemporal_store(v, reinterpret_cast<bf16x8*>(ptr));
-#else
-  *reinterpret_cast<bf16x8*>(ptr) = v;
-#endif
-}
-__device__ __forceinline__ void store_c2(f16* ptr, const f16x8& v) {
-#if NT_C2
-  __builtin_nontemporal_store(v, reinterpret_cast<f16x8*>(ptr));
-#else
-  *reinterpret_cast<f16x8*>(ptr) = v;
-#endif
-}
+// it from pushing the rows the NEXT launch reads (gelu(u)) out of L2.
+__device__ __forceinline__ void store_c2(bf16* ptr, const bf16x8& v) { __builtin_nontemporal_store(v, reinterpret_cast<bf16x8*>(ptr)); }
+__device__ __forceinline__ void store_c2(f16* ptr, const f16x8& v) { __builtin_nontemporal_store(v, reinterpret_cast<f16x8*>(ptr)); }
 
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 __device__ __forceinline__ float dgelu_f(float x) {

@@ -75,27 +75,14 @@ constexpr bool TAB_RESIDENT_OK = (SMEM + TAB_RESERVE) * (NWAVES <= 4 ? 2 : 1) <=
 // every wave of the CU pushes its DMA requests into the texture addresser in one burst behind the barrier.  Same MFMA order per
 // accumulator (k ascending): same bits.  In the step (rocprofv3, JPEG-S): fc2 / proj + residual 63.6 -> 57.1 us, fc1 + GELU 139 -> 135,
 // dGELU 122 -> 116.  The 8-wave geometry (2 A + 3 W fragments per 6 MFMAs, 150 registers: the compiler already keeps a chunk of
-// fragments ahead there) measured 6 % SLOWER pinned the same way and keeps the plain loops.  -DKP_PIPE=0: plain loops everywhere.
-#ifndef KP_PIPE
-#define KP_PIPE 1
-#endif
-#ifndef KP_DMA_BURST
-#define KP_DMA_BURST 0
-#endif
+// fragments ahead there) measured 6 % SLOWER pinned the same way and keeps the plain loop.
 template <typename E, bool W2D, int ND, class DmaFn>
 __device__ __forceinline__ void ktile_mma(const unsigned char* sA, const unsigned char* sW, const int (&foff)[4], int wn,
                                           f32x16 (&acc)[6], bool do_dma, DmaFn dma) {
 #define KP_LD(ptr) (*reinterpret_cast<const typename Vec8<E>::type*>(ptr))
 #define KP_SB __builtin_amdgcn_sched_barrier(0)
-  if constexpr (KP_PIPE && !W2D) {
+  if constexpr (!W2D) {
     KP_SB;
-#if KP_DMA_BURST
-    if (do_dma) {
-#pragma unroll
-      for (int j = 0; j < ND; ++j) dma(j);
-    }
-    KP_SB;
-#endif
     Frag<E> fa[4], fb[4][6];
     fa[0].v = KP_LD(sA + foff[0]);
 #pragma unroll
@@ -112,22 +99,18 @@ __device__ __forceinline__ void ktile_mma(const unsigned char* sA, const unsigne
           if (b == 0) fa[c + 1].v = KP_LD(sA + foff[c + 1]);
           fb[c + 1][b].v = KP_LD(sW + 32 * b * TKB + foff[c + 1]);
         }
-#if !KP_DMA_BURST
         if ((m * ND) / 24 != ((m + 1) * ND) / 24) {
           if (do_dma) dma((m * ND) / 24);
         }
-#endif
         KP_SB;
       }
-    return;
-  }
-  if (do_dma) {
+  } else {
+    if (do_dma) {
 #pragma unroll
-    for (int j = 0; j < ND; ++j) dma(j);
-  }
+      for (int j = 0; j < ND; ++j) dma(j);
+    }
 #pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    if constexpr (W2D) {
+    for (int c = 0; c < 4; ++c) {
       Frag<E> fa[2], fb[3];
       fa[0].v = KP_LD(sA + foff[c]);
       fa[1].v = KP_LD(sA + 32 * TKB + foff[c]);
@@ -137,13 +120,6 @@ __device__ __forceinline__ void ktile_mma(const unsigned char* sA, const unsigne
       for (int rg = 0; rg < 2; ++rg)
 #pragma unroll
         for (int j = 0; j < 3; ++j) mma(acc[3 * rg + j], fb[j], fa[rg]);
-    } else {
-      Frag<E> fa, fb[6];
-      fa.v = KP_LD(sA + foff[c]);
-#pragma unroll
-      for (int b = 0; b < 6; ++b) fb[b].v = KP_LD(sW + 32 * b * TKB + foff[c]);
-#pragma unroll
-      for (int b = 0; b < 6; ++b) mma(acc[b], fb[b], fa);
     }
   }
 #undef KP_LD
@@ -232,15 +208,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
     unsigned char* st = smem + stage * STAGE;
 #pragma unroll
     for (int j = 0; j < NDMA; ++j) {
-#ifdef KP_NOW      // timing experiment only: weight k-tiles beyond the first keep re-reading k-tile 0 (an L1/L2-hot line set)
-      const int i = (w + NWAVES * j) < NSLOT ? (w + NWAVES * j) : (w + NWAVES * j) - NSLOT;
-      __builtin_amdgcn_global_load_lds((glb_ptr)(src[j] + (i < ASLOT ? k0 : 0)), (lds_ptr)(st + dst[j]), 16, 0, 0);
-#elif defined(KP_NOA)    // timing experiment only: activation k-tiles keep re-reading k-tile 0
-      const int i = (w + NWAVES * j) < NSLOT ? (w + NWAVES * j) : (w + NWAVES * j) - NSLOT;
-      __builtin_amdgcn_global_load_lds((glb_ptr)(src[j] + (i < ASLOT ? 0 : k0)), (lds_ptr)(st + dst[j]), 16, 0, 0);
-#else
       __builtin_amdgcn_global_load_lds((glb_ptr)(src[j] + k0), (lds_ptr)(st + dst[j]), 16, 0, 0);
-#endif
     }
     k0 += 64;
   };
@@ -411,11 +379,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
       for (int e = 0; e < 8; e += 2) {
         const f32x2 u = {(float)cv[e], (float)cv[e + 1]};
         f32x2 gv, dgv;
-#ifdef KP_NOGELU   // timing experiment only: what the erf arithmetic costs in this epilogue
-        gv = u; dgv = u * 0.5f;
-#else
         gelu_pair_fast(u, gv, dgv);
-#endif
         dv[e] = from_f32<E>(dgv[0]);
         dv[e + 1] = from_f32<E>(dgv[1]);
         cv[e] = from_f32<E>(gv[0]);
@@ -528,13 +492,9 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_persist_kernel(KpArgs 
     for (int b = 0; b < 6; ++b)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-    // residual rows of this unit: requested behind the barrier of the LAST k-tile (KP_REARLY; they fly under its 24 MFMAs, the
-    // end-of-loop barrier and pass 1; in front of the whole k-loop, as in the kernel above, their 48 registers do not fit this
-    // kernel's loop): dGELU 117.7 -> 115.2 us, fc2 / proj + residual 56.6 -> 56.2 in the JPEG-S step.  -DKP_REARLY=0: behind the
-    // k-loop, as before.
-#ifndef KP_REARLY
-#define KP_REARLY 1
-#endif
+    // residual rows of this unit: requested behind the barrier of the LAST k-tile (they fly under its 24 MFMAs, the end-of-loop
+    // barrier and pass 1; in front of the whole k-loop, as in the kernel above, their 48 registers do not fit this kernel's loop;
+    // behind the k-loop they were slower): dGELU 117.7 -> 115.2 us, fc2 / proj + residual 56.6 -> 56.2 in the JPEG-S step.
     V8 rv[NVEC];
     const int tl = 64 * w + lane_id_here();        // (opaque thread id: see set_unit)
     auto request_rows = [&]() {
@@ -551,7 +511,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_persist_kernel(KpArgs 
       if (!last) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");    // everything but the youngest k-tile's DMAs
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
-      if (last && KP_REARLY && (EPI == EPI_RES || EPI == EPI_DGELU)) request_rows();
+      if (last) request_rows();
       const bool do_dma = t + 2 < T;
       unsigned char* stD = smem + st_issue * STAGE;
       const int kD = (t + 2) * 64;
@@ -567,7 +527,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_persist_kernel(KpArgs 
       });
       if (do_dma) st_issue = st_issue == NSTAGE - 1 ? 0 : st_issue + 1;
     };
-    if constexpr (KP_REARLY && (EPI == EPI_RES || EPI == EPI_DGELU)) {      // (the last k-tile peeled: rv is written in ONE place)
+    if constexpr (EPI == EPI_RES || EPI == EPI_DGELU) {      // (the last k-tile peeled: rv is written in ONE place)
 #pragma unroll 1
       for (int t = 0; t + 1 < T; ++t) ktile(t, false);
       ktile(T - 1, true);
@@ -578,7 +538,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_persist_kernel(KpArgs 
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();          // every wave is done reading the ring: it becomes the staging tile
     KPROFU(1);
-    if (!KP_REARLY) request_rows();
     if (tab) rgbnm::gelu_table_dma(p.tab.img, smem, w, NWAVES, lane_id_here());     // (ring stage 0 is free: the k-loop is over)
     // ---- the next unit's first k-tile, into the stage the staging tile leaves alone
     const int cm0 = m0, cn0 = n0, crows = rows;
@@ -640,25 +599,14 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_persist_kernel(KpArgs 
         for (int e = 0; e < 8; e += 2) {
           const f32x2 uu = {(float)cv[e], (float)cv[e + 1]};
           f32x2 gv, dgv;
-#ifdef KPX_NOGELU        // (sensitivity builds, wrong numbers)
-          gv = uu; dgv = uu;
-#else
           gelu_pair_fast(uu, gv, dgv);
-#endif
           dv[e] = from_f32<E>(dgv[0]);
           dv[e + 1] = from_f32<E>(dgv[1]);
           cv[e] = from_f32<E>(gv[0]);
           cv[e + 1] = from_f32<E>(gv[1]);
         }
-#ifndef KPX_NOC2
         store_c2(C2 + (size_t)(cm0 + row) * p.ldc2 + cn0 + vec * 8, dv);
-#else
-        if (dv[0] == (E)123.f && dv[3] == (E)-7.f) store_c2(C2 + (size_t)(cm0 + row) * p.ldc2 + cn0 + vec * 8, dv);
-#endif
       }
-#ifdef KPX_NOSTORE
-      if (cv[0] == (E)123.f && cv[3] == (E)-7.f)
-#endif
       *reinterpret_cast<V8*>(p.C + (size_t)(cm0 + row) * p.ldc + cn0 + vec * 8) = cv;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -157,9 +157,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_wres_kernel(WresArgs<T> p) {
   int pstep = 0;
 #endif
 
-#ifdef WRES_SIXWAVES
-  if (w == 6) return;
-#endif
   while (t < tend) {
     // park the tile in the private buffer (previous tile's staging reads are older LDS instructions of this wave:
     // LDS executes a wave in order), then immediately refill the registers with the tile after it
@@ -221,11 +218,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_wres_kernel(WresArgs<T> p) {
           for (int e = 0; e < 8; e += 2) {
             const f32x2 u = {(float)cv[e], (float)cv[e + 1]};
             f32x2 gv, dgv;
-#ifdef WRES_NOGELU
-            gv = u; dgv = u * 0.5f;
-#else
             gelu_pair_fast(u, gv, dgv);
-#endif
             dv[e] = from_f32<T>(dgv[0]);
             dv[e + 1] = from_f32<T>(dgv[1]);
             cv[e] = from_f32<T>(gv[0]);

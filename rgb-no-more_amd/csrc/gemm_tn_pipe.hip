@@ -16,12 +16,6 @@
 #include "lds_common.h"
 #include "../../include/rgbnm.h"
 
-// Operand streams: TN_NT bit 0 = the dY slices (read by ONE workgroup, once) non-temporal (aux = 2 of global_load_lds), bit 1 = the
-// X tiles (shared by the tiles of a GEMM through their XCD's L2)
-#ifndef TN_NT
-#define TN_NT 0
-#endif
-
 namespace {
 
 constexpr int TK = 64;                         // tokens per stage
@@ -29,10 +23,7 @@ constexpr int A_ROW = 256, B_ROW = 384;        // bytes per token row (128 / 192
 constexpr int A_STAGE = TK * A_ROW;            // 16 KB
 constexpr int B_STAGE = TK * B_ROW;            // 24 KB
 constexpr int STAGE = A_STAGE + B_STAGE;       // 40 KB
-#ifndef TN_NSTAGE
-#define TN_NSTAGE 3
-#endif
-constexpr int NSTAGE = TN_NSTAGE;              // 3: two tiles (80 KB) in flight; 4: three (120 KB), all 160 KB of LDS
+constexpr int NSTAGE = 3;                      // 3: two tiles (80 KB) in flight; 4: three (120 KB), all 160 KB of LDS
 constexpr int SMEM = NSTAGE * STAGE;           // 120 KB
 
 // (operand pointers below are typed bf16 for their 2-byte address arithmetic only: the kernels read them through LDS-DMA as bytes
@@ -93,42 +84,11 @@ __device__ __forceinline__ void tr_chunk(unsigned aA, unsigned aB0, unsigned aB1
   fb[1].v = pack8t<E>(b1l, b1h);
   fb[2].v = pack8t<E>(b2l, b2h);
 }
+// (Round 5 tried to read chunk C + 1 under the MFMAs of chunk C instead of this read - wait - MFMA per 16 tokens, two waves per SIMD
+// covering each other.  Through the builtin: MEASURED +50 % on the launch -- the compiler drains vmcnt in front of every builtin LDS
+// read that follows an LDS-DMA (it cannot tell the ring stages apart), which empties the ring.  As asm reads without the wait,
+// lgkmcnt counted by hand: +-0.5 % -- the kernel waits for its operand stream, not for LDS.)
 
-// Experiments (round 5, TN_FPIPE; default 0 = the loop above's read - wait - MFMA per 16 tokens, two waves per SIMD covering each
-// other): 1 = the same eight reads through the builtin with the next chunk's reads under the current MFMAs -- MEASURED +50 % on the
-// launch: the compiler drains vmcnt in front of every builtin LDS read that follows an LDS-DMA, which empties the ring;
-// 2 = asm reads without the wait, lgkmcnt counted by hand: +-0.5 % (the kernel waits for its operand stream, not for LDS).
-template <int C, typename E>
-__device__ __forceinline__ void tr_chunk_b(const unsigned char* sp, unsigned oA, unsigned oB0, unsigned oB1, unsigned oB2,
-                                           Frag<E>& fa, Frag<E> (&fb)[3]) {
-  fa.v = pack8t<E>(tr_read(sp, oA + C * 16 * A_ROW), tr_read(sp, oA + C * 16 * A_ROW + 4 * A_ROW));
-  fb[0].v = pack8t<E>(tr_read(sp, oB0 + C * 16 * B_ROW), tr_read(sp, oB0 + C * 16 * B_ROW + 4 * B_ROW));
-  fb[1].v = pack8t<E>(tr_read(sp, oB1 + C * 16 * B_ROW), tr_read(sp, oB1 + C * 16 * B_ROW + 4 * B_ROW));
-  fb[2].v = pack8t<E>(tr_read(sp, oB2 + C * 16 * B_ROW), tr_read(sp, oB2 + C * 16 * B_ROW + 4 * B_ROW));
-}
-
-#ifndef TN_FPIPE
-#define TN_FPIPE 0
-#endif
-// ... and as one asm block WITHOUT the wait (TN_FPIPE == 2): the compiler drains vmcnt before a builtin LDS read that follows
-// LDS-DMA (it cannot tell the ring stages apart), which empties the DMA pipeline; asm reads are invisible to that rule, so the waits
-// (lgkmcnt counted by hand: LDS returns in order) are written out next to them
-template <int C>
-__device__ __forceinline__ void tr_chunk_nw(unsigned aA, unsigned aB0, unsigned aB1, unsigned aB2, u32x2 (&r)[8]) {
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %8 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %1, %8 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %2, %9 offset:%14\n\t"
-      "ds_read_b64_tr_b16 %3, %9 offset:%15\n\t"
-      "ds_read_b64_tr_b16 %4, %10 offset:%14\n\t"
-      "ds_read_b64_tr_b16 %5, %10 offset:%15\n\t"
-      "ds_read_b64_tr_b16 %6, %11 offset:%14\n\t"
-      "ds_read_b64_tr_b16 %7, %11 offset:%15"
-      : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(r[4]), "=&v"(r[5]), "=&v"(r[6]), "=&v"(r[7])
-      : "v"(aA), "v"(aB0), "v"(aB1), "v"(aB2), "i"(C * 16 * A_ROW), "i"(C * 16 * A_ROW + 4 * A_ROW),
-        "i"(C * 16 * B_ROW), "i"(C * 16 * B_ROW + 4 * B_ROW)
-      : "memory");
-}
 template <bool V> struct BoolTag { static constexpr bool value = V; };
 
 template <typename E>
@@ -194,10 +154,10 @@ __global__ __launch_bounds__(512) void gemm_tn_pipe_kernel(TnGroup grp) {
     unsigned char* st = smem + stage * STAGE + w * 1024;
 #pragma unroll
     for (int j = 0; j < 2; ++j)
-      __builtin_amdgcn_global_load_lds((glb_ptr)(gA + offA[j]), (lds_ptr)(st + j * 8192), 16, 0, (TN_NT & 1) ? 2 : 0);
+      __builtin_amdgcn_global_load_lds((glb_ptr)(gA + offA[j]), (lds_ptr)(st + j * 8192), 16, 0, 0);
 #pragma unroll
     for (int j = 0; j < 3; ++j)
-      __builtin_amdgcn_global_load_lds((glb_ptr)(gB + offB[j]), (lds_ptr)(st + A_STAGE + j * 8192), 16, 0, (TN_NT & 2) ? 2 : 0);
+      __builtin_amdgcn_global_load_lds((glb_ptr)(gB + offB[j]), (lds_ptr)(st + A_STAGE + j * 8192), 16, 0, 0);
     gA += stepA;
     gB += stepB;
   };
@@ -243,73 +203,18 @@ __global__ __launch_bounds__(512) void gemm_tn_pipe_kernel(TnGroup grp) {
         issue(st_issue);
         st_issue = st_issue == NSTAGE - 1 ? 0 : st_issue + 1;
       }
-  #if TN_FPIPE == 2
-      const unsigned sb = lds0 + st_comp * STAGE;
-      st_comp = st_comp == NSTAGE - 1 ? 0 : st_comp + 1;
-      const unsigned aA = sb + oA, aB0 = sb + oB0, aB1 = sb + oB1, aB2 = sb + oB2;
-      u32x2 r[2][8];
-      tr_chunk_nw<0>(aA, aB0, aB1, aB2, r[0]);
-#define CHUNK(C)                                                                     \
-      if (C < 3) {                                                                   \
-        tr_chunk_nw<C + 1>(aA, aB0, aB1, aB2, r[(C + 1) & 1]);                       \
-        asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");                           \
-      } else {                                                                       \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                           \
-      }                                                                              \
-      __builtin_amdgcn_sched_barrier(0);                                             \
-      {                                                                              \
-        Frag<E> fa, fb0, fb1, fb2;                                                   \
-        fa.v = pack8t<E>(r[C & 1][0], r[C & 1][1]);                                  \
-        fb0.v = pack8t<E>(r[C & 1][2], r[C & 1][3]);                                 \
-        fb1.v = pack8t<E>(r[C & 1][4], r[C & 1][5]);                                 \
-        fb2.v = pack8t<E>(r[C & 1][6], r[C & 1][7]);                                 \
-        mma(acc[0], fa, fb0);                                                        \
-        mma(acc[1], fa, fb1);                                                        \
-        mma(acc[2], fa, fb2);                                                        \
-        if constexpr (BIAS) mma(accb, fa, ones);                                     \
-      }                                                                              \
-      __builtin_amdgcn_sched_barrier(0);
-      CHUNK(0) CHUNK(1) CHUNK(2) CHUNK(3)
-#undef CHUNK
-#elif TN_FPIPE
-      // fragments of chunk C + 1 are read while the MFMAs of chunk C run (two register sets; LDS returns in order, so the compiler's
-      // counted lgkmcnt waits let the next chunk's eight reads stay in flight)
-      const unsigned char* sp = smem + st_comp * STAGE;
-      st_comp = st_comp == NSTAGE - 1 ? 0 : st_comp + 1;
-      Frag<E> fa[2], fb[2][3];
-      tr_chunk_b<0>(sp, oA, oB0, oB1, oB2, fa[0], fb[0]);
-      __builtin_amdgcn_sched_barrier(0);
-#define CHUNK(C)                                                                     \
-      if (C < 3) tr_chunk_b<C + 1>(sp, oA, oB0, oB1, oB2, fa[(C + 1) & 1], fb[(C + 1) & 1]);  \
-      mma(acc[0], fa[C & 1], fb[C & 1][0]);                                            \
-      mma(acc[1], fa[C & 1], fb[C & 1][1]);                                            \
-      mma(acc[2], fa[C & 1], fb[C & 1][2]);                                            \
-      if constexpr (BIAS) mma(accb, fa[C & 1], ones);                                  \
-      if (C < 3) {            /* the next chunk's reads trickle out between this chunk's MFMAs */ \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                             \
-        __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);                             \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                             \
-        __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);                             \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                             \
-        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                             \
-        if constexpr (BIAS) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);         \
-      }
-      CHUNK(0) CHUNK(1) CHUNK(2) CHUNK(3)
-#undef CHUNK
-#else
       const unsigned sb = lds0 + st_comp * STAGE;
       st_comp = st_comp == NSTAGE - 1 ? 0 : st_comp + 1;
       const unsigned aA = sb + oA, aB0 = sb + oB0, aB1 = sb + oB1, aB2 = sb + oB2;
       Frag<E> fa, fb[3];
-  #define CHUNK(C)                                   \
+#define CHUNK(C)                                     \
       tr_chunk<C>(aA, aB0, aB1, aB2, fa, fb);        \
       mma(acc[0], fa, fb[0]);                        \
       mma(acc[1], fa, fb[1]);                        \
       mma(acc[2], fa, fb[2]);                        \
       if constexpr (BIAS) mma(accb, fa, ones);
       CHUNK(0) CHUNK(1) CHUNK(2) CHUNK(3)
-  #undef CHUNK
-  #endif
+#undef CHUNK
     }
   };
   if (do_bias) tiles(BoolTag<true>());
@@ -445,13 +350,13 @@ __global__ __launch_bounds__(512) void gemm_tn_wide_kernel(TnGroup grp) {
   auto issue = [&](int stage, int t) {
     unsigned char* st = smem + stage * WSTAGE;
     // instruction w: A tile for every wave (w < 12); w + 8: A for waves 0 - 3, B for the others; the rest: B
-    __builtin_amdgcn_global_load_lds((glb_ptr)(gA + off[0]), (lds_ptr)(st + w * 1024), 16, 0, (TN_NT & 1) ? 2 : 0);
-    if (w < 4) __builtin_amdgcn_global_load_lds((glb_ptr)(gA + off[1]), (lds_ptr)(st + (w + 8) * 1024), 16, 0, (TN_NT & 1) ? 2 : 0);
-    else __builtin_amdgcn_global_load_lds((glb_ptr)(gB + off[1]), (lds_ptr)(st + (w + 8) * 1024), 16, 0, (TN_NT & 2) ? 2 : 0);
-    __builtin_amdgcn_global_load_lds((glb_ptr)(gB + off[2]), (lds_ptr)(st + (w + 16) * 1024), 16, 0, (TN_NT & 2) ? 2 : 0);
-    __builtin_amdgcn_global_load_lds((glb_ptr)(gB + off[3]), (lds_ptr)(st + (w + 24) * 1024), 16, 0, (TN_NT & 2) ? 2 : 0);
+    __builtin_amdgcn_global_load_lds((glb_ptr)(gA + off[0]), (lds_ptr)(st + w * 1024), 16, 0, 0);
+    if (w < 4) __builtin_amdgcn_global_load_lds((glb_ptr)(gA + off[1]), (lds_ptr)(st + (w + 8) * 1024), 16, 0, 0);
+    else __builtin_amdgcn_global_load_lds((glb_ptr)(gB + off[1]), (lds_ptr)(st + (w + 8) * 1024), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((glb_ptr)(gB + off[2]), (lds_ptr)(st + (w + 16) * 1024), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((glb_ptr)(gB + off[3]), (lds_ptr)(st + (w + 24) * 1024), 16, 0, 0);
     if (((t ^ (w >> 2)) & 1) == 0)
-      __builtin_amdgcn_global_load_lds((glb_ptr)(gB + off[4]), (lds_ptr)(st + (32 + (w & 3)) * 1024), 16, 0, (TN_NT & 2) ? 2 : 0);
+      __builtin_amdgcn_global_load_lds((glb_ptr)(gB + off[4]), (lds_ptr)(st + (32 + (w & 3)) * 1024), 16, 0, 0);
     gA += stepA;
     gB += stepB;
   };

@@ -63,41 +63,31 @@ __device__ __forceinline__ Frag<bf16> rowfrag_x(const unsigned char* arr, unsign
 // with their eight row fragments in a PINNED order: four fragments ahead, every MFMA followed by the read of the fragment two steps
 // on (into registers an earlier MFMA has read -- the sixteen the transposed fragments of the tile's second half take afterwards).
 // Left alone the compiler emits read - wait - MFMA eight times with ONE fragment buffer: an exposed LDS latency per MFMA (50 of
-// attn3_bwd's 196; 336 per block and wave of the chain backward).  ROWPIPE = false: the plain loop (experiments: each file passes
-// its own switch, AV2_ROWPIPE / XB_ROWPIPE).  Same MFMA order per accumulator: same bits.
-template <bool ROWPIPE>
+// attn3_bwd's 196; 336 per block and wave of the chain backward).  Same MFMA order per accumulator as the plain loop: same bits.
 __device__ __forceinline__ void row_pair_mma(f32x16& sa, f32x16& da, const unsigned char* arrS, const unsigned char* arrD, unsigned rb,
                                              int t, const Frag<bf16> (&xs)[4], const Frag<bf16> (&xd)[4]) {
-  if constexpr (ROWPIPE) {
 #define T128_SB __builtin_amdgcn_sched_barrier(0)
-    Frag<bf16> fs[4], fd[4];
-    T128_SB;
-    fs[0] = rowfrag_x(arrS, rb, t, 0);
-    fd[0] = rowfrag_x(arrD, rb, t, 0);
-    fs[1] = rowfrag_x(arrS, rb, t, 1);
-    fd[1] = rowfrag_x(arrD, rb, t, 1);
-    T128_SB;
-    mma(sa, fs[0], xs[0]); T128_SB;
-    fs[2] = rowfrag_x(arrS, rb, t, 2); T128_SB;
-    mma(da, fd[0], xd[0]); T128_SB;
-    fd[2] = rowfrag_x(arrD, rb, t, 2); T128_SB;
-    mma(sa, fs[1], xs[1]); T128_SB;
-    fs[3] = rowfrag_x(arrS, rb, t, 3); T128_SB;
-    mma(da, fd[1], xd[1]); T128_SB;
-    fd[3] = rowfrag_x(arrD, rb, t, 3); T128_SB;
-    mma(sa, fs[2], xs[2]);
-    mma(da, fd[2], xd[2]);
-    mma(sa, fs[3], xs[3]);
-    mma(da, fd[3], xd[3]);
-    T128_SB;
+  Frag<bf16> fs[4], fd[4];
+  T128_SB;
+  fs[0] = rowfrag_x(arrS, rb, t, 0);
+  fd[0] = rowfrag_x(arrD, rb, t, 0);
+  fs[1] = rowfrag_x(arrS, rb, t, 1);
+  fd[1] = rowfrag_x(arrD, rb, t, 1);
+  T128_SB;
+  mma(sa, fs[0], xs[0]); T128_SB;
+  fs[2] = rowfrag_x(arrS, rb, t, 2); T128_SB;
+  mma(da, fd[0], xd[0]); T128_SB;
+  fd[2] = rowfrag_x(arrD, rb, t, 2); T128_SB;
+  mma(sa, fs[1], xs[1]); T128_SB;
+  fs[3] = rowfrag_x(arrS, rb, t, 3); T128_SB;
+  mma(da, fd[1], xd[1]); T128_SB;
+  fd[3] = rowfrag_x(arrD, rb, t, 3); T128_SB;
+  mma(sa, fs[2], xs[2]);
+  mma(da, fd[2], xd[2]);
+  mma(sa, fs[3], xs[3]);
+  mma(da, fd[3], xd[3]);
+  T128_SB;
 #undef T128_SB
-  } else {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      mma(sa, rowfrag_x(arrS, rb, t, c), xs[c]);
-      mma(da, rowfrag_x(arrD, rb, t, c), xd[c]);
-    }
-  }
 }
 
 // Transposed operands (tokens as reduction axis) of tile T of ONE array, both fragments (FI = 0, 1) x both 32-wide d tiles:
@@ -140,24 +130,18 @@ __device__ __forceinline__ void tfrag4_b(const unsigned char* smem, unsigned a0,
 // Between a wave's accesses to ITS OWN LDS tile (write the fragment layout, read row pieces back, overwrite with the next tile) no
 // wait is needed: the LDS executes one wave's DS instructions in order, and the compiler counts lgkmcnt for the registers that are
 // used.  What must not happen is the compiler reordering the accesses (differently typed pointers): a compiler-only fence.  The
-// drains that stood here cost two LDS round trips per stored tile (~50 tiles per block and wave).  -DX_LDSWAIT restores them.
-#ifdef X_LDSWAIT
-__device__ __forceinline__ void own_tile_fence() { wait_lds(); }
-#else
+// drains that stood here cost two LDS round trips per stored tile (~50 tiles per block and wave).
 __device__ __forceinline__ void own_tile_fence() { asm volatile("" ::: "memory"); }
-#endif
 
 // LDS-DMA of one [N][64] bf16 matrix (row stride ld elements) into an array by ONE wave: 28 instructions of 1 KB (8 rows).
-// Rows >= N replicate row N - 1 (finite data; their probabilities are masked to zero).  AUX: the cache policy of the loads
-// (2 = non-temporal)
-template <int AUX = 0>
+// Rows >= N replicate row N - 1 (finite data; their probabilities are masked to zero).
 __device__ __forceinline__ void dma_matrix_all(const bf16* __restrict__ src, int ld, int N, unsigned char* dst, int lane) {
 #pragma unroll 4
   for (int i = 0; i < 28; ++i) {
     const int row = 8 * i + (lane >> 3), pc = lane & 7;
     const int lc = pc ^ fswz(row);
     const int srow = row < N ? row : N - 1;
-    __builtin_amdgcn_global_load_lds((glb_ptr)(src + (size_t)srow * ld + lc * 8), (lds_ptr)(dst + i * 1024), 16, 0, AUX);
+    __builtin_amdgcn_global_load_lds((glb_ptr)(src + (size_t)srow * ld + lc * 8), (lds_ptr)(dst + i * 1024), 16, 0, 0);
   }
 }
 

@@ -32,7 +32,7 @@
 #include <string.h>
 #include <type_traits>
 #include "internal.h"
-#include "tile128.h"
+#include "chain_common.h"
 #include "../../include/rgbnm.h"
 
 namespace {
@@ -63,18 +63,7 @@ constexpr int FLAG_OFF = B2_OFF + E * 4;           // 73088: the last hidden chu
 constexpr int ST0_OFF = K_OFF;                    // even hidden chunks (over K, V: dead by then)
 constexpr int TB_OFF = ST0_OFF + STAGE;           // 122880: gelu | gelu' tiles of waves 0..4
 constexpr int SMEM = 163840;
-#ifndef PIPE_QKV
-#define PIPE_QKV 6
-#endif
-#ifndef PIPE_P
-#define PIPE_P 6
-#endif
-#ifndef PIPE_M1
-#define PIPE_M1 5
-#endif
-#ifndef PIPE_M2
-#define PIPE_M2 6
-#endif
+constexpr int PIPE_QKV = 6, PIPE_P = 6, PIPE_M1 = 5;    // weight fragments requested ahead of the MFMAs: q / k / v steps, projection, fc1
 static_assert(BQKV_OFF + 3 * INNER * 4 <= SMEM, "LDS");
 static_assert(TB_OFF + 10 * STG_TILE <= SMEM, "LDS");
 static_assert(FLAG_OFF + 16 <= ST0_OFF, "LDS");
@@ -101,21 +90,10 @@ struct ChainArgs {            // passed BY VALUE (kernel argument segment): noth
 // Global stores of the saved tensors: NON-TEMPORAL (`global_store_dwordx4 ... nt`).  Nobody reads them for a millisecond (the
 // backward), so they should not push the weight images and the next phases' lines out of L2: -3 % on this launch and -1.3 % on
 // the backward launch behind it (interleaved A/B; the same hint did nothing for the per-operation kernels of
-// round 2, whose outputs the next launch reads at once).  -DX_STORE=0 plain, =2 write-through (sc1), =3 sc0 sc1 (experiments).
-#ifndef X_STORE
-#define X_STORE 1
-#endif
+// round 2, whose outputs the next launch reads at once).
 template <typename V, typename P>
 __device__ __forceinline__ void gstore(P* ptr, const V& v) {
-#if X_STORE == 1
   __builtin_nontemporal_store(v, reinterpret_cast<V*>(ptr));
-#elif X_STORE == 2
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 2" ::"v"(reinterpret_cast<V*>(ptr)), "v"(v) : "memory");   // (store-data hazard: the compiler cannot see this store)
-#elif X_STORE == 3
-  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 2" ::"v"(reinterpret_cast<V*>(ptr)), "v"(v) : "memory");
-#else
-  *reinterpret_cast<V*>(ptr) = v;
-#endif
 }
 
 // ---- DMA wave helpers (linear 1 KB pieces: lds_common.h dma_linear)
@@ -125,10 +103,7 @@ __device__ __forceinline__ void dma_f32x192(const float* src, unsigned char* dst
     __builtin_amdgcn_global_load_lds((glb_ptr)(src + 64 * i + lane), (lds_ptr)(dst + 256 * i), 4, 0, 0);
 }
 
-// ---- D-layout rows: 12 pieces (index c = 2 b + hs) of 8 bf16 = features 16 c + 8 g + (0..7) of the lane's token, held as PACKED
-// dwords (element j of a piece = half j & 1 of dword j >> 1): as bf16 vectors built element by element the compiler kept the
-// 96 values of a row set in 96 registers and spilled them
-struct Rows { u32x4 v[12]; };
+// ---- D-layout rows (chain_common.h Rows)
 __device__ __forceinline__ float bf_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
 __device__ __forceinline__ float bf_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
 
@@ -161,11 +136,6 @@ __device__ __forceinline__ void ln_stats(const Rows& x, float& mu, float& rs, fl
 }
 // y = (x - mu) * rs * gamma + beta, gamma | beta = 2 x 192 floats in LDS
 __device__ __forceinline__ void ln_apply(const Rows& x, float mu, float rs, const float* gb, int g, Rows& y) {
-#ifdef X_NOLN        // (experiments only, wrong numbers: what the five LayerNorm applications per block cost -- y = x)
-#pragma unroll
-  for (int c = 0; c < 12; ++c) y.v[c] = x.v[c];
-  return;
-#endif
 #pragma unroll
   for (int c = 0; c < 12; ++c) {
     const float* gp = gb + 16 * c + 8 * g;
@@ -206,7 +176,6 @@ __device__ __forceinline__ void tile_out(unsigned char* smem, unsigned stg, cons
   u32x4 v[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const u32x4*>(smem + ro + i * 8 * ROWB);
-#ifndef X_NOSAVE      // (experiments only: the kernel without its global stores -- what the saved tensors cost)
   if (live == 32) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) gstore(gp + (size_t)i * 8 * ld, v[i]);
@@ -215,7 +184,6 @@ __device__ __forceinline__ void tile_out(unsigned char* smem, unsigned stg, cons
     for (int i = 0; i < 4; ++i)
       if (i * 8 + rl < live) gstore(gp + (size_t)i * 8 * ld, v[i]);
   }
-#endif
   own_tile_fence();
 }
 __device__ __forceinline__ void rows_out(unsigned char* smem, unsigned stg, const Rows& x, bf16* dst, int live) {
@@ -224,56 +192,6 @@ __device__ __forceinline__ void rows_out(unsigned char* smem, unsigned stg, cons
     tile_out(smem, stg, x.v[4 * t], x.v[4 * t + 1], x.v[4 * t + 2], x.v[4 * t + 3], dst + 64 * t, E, live);
     __builtin_amdgcn_sched_barrier(0);
   }
-}
-
-// acc (32 output features x 32 tokens, swapped) += W chunk rows [32 ht .. +31] . x : 12 k-steps; chunk rows are 384 B, 16-byte
-// chunks swizzled by pchunk (as the W1 stage of mlp_fused.hip)
-__device__ __forceinline__ void gemm_k192(f32x16& acc, const unsigned char* sW, int ht, const Rows& x, const Geo& L) {
-  int wbase = L.l31 * (E * 2) + ((L.g ^ L.fl) << 4) + ht * 32 * (E * 2);
-  asm volatile("" : "+v"(wbase));
-  Frag<bf16> fb;
-#pragma unroll
-  for (int c = 0; c < 12; ++c) {
-    Frag<bf16> fx;
-#ifdef X_HALFW      // (experiments only, wrong numbers: every weight fragment read from LDS serves two MFMAs -- what a wave that owned
-                    // 64 rows would save on the LDS port)
-    if ((c & 1) == 0)
-#endif
-    fb.v = *reinterpret_cast<const bf16x8*>(sW + ((wbase ^ ((c % 4) << 5)) + 128 * (c / 4)));
-    fx.v = as_bf16x8(x.v[c]);
-    mma(acc, fb, fx);
-  }
-}
-
-// Both 32-row halves (ht = 0, 1) of a 64 x 192 chunk times x as ONE stream of 24 MFMAs with the weight fragments requested
-// DEPTH MFMAs ahead.  Left to itself the scheduler (256 registers: "minimum pressure" everywhere) emits read -> wait -> MFMA with a
-// single fragment buffer, i.e. one exposed LDS latency (100+ cycles under load) per 32-cycle MFMA; two waves per SIMD hide half
-// of it at best.  The order is pinned with sched_group_barrier, the compiler counts the lgkmcnt values.
-template <int DEPTH>
-__device__ __forceinline__ void gemm_k192x2(f32x16& a0, f32x16& a1, const unsigned char* sW, const Rows& x, const Geo& L) {
-  int wb0 = L.l31 * (E * 2) + ((L.g ^ L.fl) << 4);
-  asm volatile("" : "+v"(wb0));
-  const int wb1 = wb0 + 32 * (E * 2);
-  Frag<bf16> fb[24];
-#pragma unroll
-  for (int i = 0; i < 24; ++i) {
-    const int c = i >> 1;
-    fb[i].v = *reinterpret_cast<const bf16x8*>(sW + ((((i & 1) ? wb1 : wb0) ^ ((c % 4) << 5)) + 128 * (c / 4)));
-  }
-#pragma unroll
-  for (int i = 0; i < 24; ++i) {
-    Frag<bf16> fx;
-    fx.v = as_bf16x8(x.v[i >> 1]);
-    mma((i & 1) ? a1 : a0, fb[i], fx);
-  }
-  __builtin_amdgcn_sched_group_barrier(0x100, DEPTH, 0);
-#pragma unroll
-  for (int i = 0; i < 24 - DEPTH; ++i) {
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-  }
-#pragma unroll
-  for (int i = 0; i < DEPTH; ++i) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
 }
 
 #ifdef CHAIN_PROF
@@ -311,9 +229,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
   CP_RT(126);
 
   if (w == NCW) {
-#ifdef X_DMAPRIO
-    __builtin_amdgcn_s_setprio(X_DMAPRIO);
-#endif
     // ================================================================ DMA wave: the static weight schedule
     const int lane = L.lane;
     auto chunkA = [&](const ChainBlk& b, int idx, int slot) {
@@ -406,10 +321,8 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
             const int row = trow + 8 * i;
             if (row < lr) {
               const size_t go = ((size_t)img * NTOK + 32 * (4 + q) + row) * HID + chunk * 64 + tvec * 8;
-#ifndef X_NOSAVE
               gstore(b.gl + go, tv[q][0][i]);
               gstore(b.gp + go, tv[q][1][i]);
-#endif
             }
           }
         }
@@ -444,11 +357,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
   }
 
   // ==================================================================== compute waves
-#if defined(X_PRIO) && X_PRIO == 1      // experiments: static issue priority for the younger wave of every SIMD pair
-  if (w >= 4) __builtin_amdgcn_s_setprio(1);
-#elif defined(X_PRIO) && X_PRIO == 2    // ... for the older one
-  if (w < 4) __builtin_amdgcn_s_setprio(1);
-#endif
   const int row0 = 32 * w;
   const int live = NTOK - row0 < 32 ? NTOK - row0 : 32;          // 32, or 4 for the seventh wave
   const int tok = row0 + L.l31 < NTOK ? row0 + L.l31 : NTOK - 1; // this lane's token (clamped: finite data in the pad rows)
@@ -502,12 +410,7 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
         for (int ht = 0; ht < 2; ++ht)
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[ht][r] = 0.f;
-#ifdef X_NOPIPE
-        gemm_k192(acc[0], sW, 0, xn, L);
-        gemm_k192(acc[1], sW, 1, xn, L);
-#else
         gemm_k192x2<PIPE_QKV>(acc[0], acc[1], sW, xn, L);
-#endif
         u32x4 pc[4];
 #pragma unroll
         for (int ht = 0; ht < 2; ++ht)
@@ -542,30 +445,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
         unsigned rb = (unsigned)(L.l31 * ROWB + ((L.g ^ L.fl) << 4)), tr = L.tr0;
         asm volatile("" : "+v"(rb), "+v"(tr));
         float mx = -INFINITY;
-#if defined(X_NOPIPE) || defined(X_NOATTN)
-#ifdef X_NOATTN
-        TileLoop<0>::run([&](auto tc) {
-#else
-        TileLoop<NTILE>::run([&](auto tc) {
-#endif
-          constexpr int t = decltype(tc)::value;
-          f32x16 acc;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            Frag<bf16> kf;
-            kf.v = *reinterpret_cast<const bf16x8*>(Ks + (rb ^ (unsigned)(c << 5)) + t * 32 * ROWB);
-            mma(acc, kf, qf[c]);
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            float v = acc[r];
-            if (t * 32 + 32 > NTOK && t * 32 + acc_row(r, L.lane) >= NTOK) v = -INFINITY;
-            mx = fmaxf(mx, v);
-          }
-        });
-#else
         // software-pipelined by hand, one fence per key tile: the K fragments of tile t + 1 are requested, then the 4 MFMAs of tile t
         // are issued and the maxima of tile t - 1 run under them (two score tiles live)
         {
@@ -601,7 +480,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
             for (int c = 0; c < 4; ++c) kc[c] = kn[c];
           });
         }
-#endif
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
         const float mc2 = mx * c2;
         float sum = 0.f;
@@ -611,39 +489,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
         const unsigned vt = (unsigned)V_OFF + tr;
-#if defined(X_NOPIPE) || defined(X_NOATTN)
-#ifdef X_NOATTN
-        TileLoop<0>::run([&](auto tc) {
-#else
-        TileLoop<NTILE>::run([&](auto tc) {
-#endif
-          constexpr int t = decltype(tc)::value;
-          f32x16 acc;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            Frag<bf16> kf;
-            kf.v = *reinterpret_cast<const bf16x8*>(Ks + (rb ^ (unsigned)(c << 5)) + t * 32 * ROWB);
-            mma(acc, kf, qf[c]);
-          }
-          float pr[16];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            pr[r] = __builtin_amdgcn_exp2f(fmaf(acc[r], c2, -mc2));
-            if (t * 32 + 32 > NTOK && t * 32 + acc_row(r, L.lane) >= NTOK) pr[r] = 0.f;
-            sum += pr[r];
-          }
-          Frag<bf16> vv[4];
-          tfrag4<t>(vt, vv);
-          Frag<bf16> pf = pfrag<bf16>(pr, 0);
-          mma(o[0], vv[0], pf);
-          mma(o[1], vv[1], pf);
-          pf = pfrag<bf16>(pr, 1);
-          mma(o[0], vv[2], pf);
-          mma(o[1], vv[3], pf);
-        });
-#else
         // one fenced region per key tile: S_t (K fragments requested in the previous region), then the V fragments of this tile and
         // the K fragments of the next one are requested and travel under the exponentials, P.V_t
         {
@@ -668,11 +513,7 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
             float pr[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-#ifdef X_NOEXP      // (experiments only, wrong numbers: what the exponentials cost)
-              pr[r] = fmaf(acc[r], c2, -mc2);
-#else
               pr[r] = __builtin_amdgcn_exp2f(fmaf(acc[r], c2, -mc2));
-#endif
               if (t * 32 + 32 > NTOK && t * 32 + acc_row(r, L.lane) >= NTOK) pr[r] = 0.f;
               sum += pr[r];
             }
@@ -691,7 +532,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
             for (int c = 0; c < 4; ++c) kc[c] = kn[c];
           });
         }
-#endif
         sum += __shfl_xor(sum, 32, 64);
         const float inv = 1.f / sum;
         if (L.g == 0 && L.l31 < live) b.lse[((size_t)img * HEADS + h) * NTOK + row0 + L.l31] = mx * p.scale + __logf(sum);
@@ -726,7 +566,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
           u32x4 v[4];
 #pragma unroll
           for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const u32x4*>(smem + ro + i * 8 * ROWB);
-#ifndef X_NOSAVE
           if (live == 32) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) gstore(dst + (size_t)i * 8 * INNER, v[i]);
@@ -735,7 +574,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
             for (int i = 0; i < 4; ++i)
               if (i * 8 + rl < live) gstore(dst + (size_t)i * 8 * INNER, v[i]);
           }
-#endif
           own_tile_fence();
         }
       }
@@ -757,14 +595,10 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
         Frag<bf16> fw[6];
 #pragma unroll
         for (int bt = 0; bt < 6; ++bt)
-#ifdef X_HALFW
-          if (bt & 1) fw[bt].v = fw[bt - 1].v; else
-#endif
           fw[bt].v = *reinterpret_cast<const bf16x8*>(smem + (wo ^ (unsigned)(s << 5)) + bt * 32 * ROWB);
 #pragma unroll
         for (int bt = 0; bt < 6; ++bt) mma(accp[bt], fw[bt], of[h][s]);
       }
-#ifndef X_NOPIPE
       // the 24 weight fragments of the step PIPE_P MFMAs ahead of their use
       __builtin_amdgcn_sched_group_barrier(0x100, PIPE_P, 0);
 #pragma unroll
@@ -775,7 +609,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
 #pragma unroll
       for (int i = 0; i < PIPE_P; ++i) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       __builtin_amdgcn_sched_barrier(0);
-#endif
     }
     BAR(15);                                                      // step 14b: the chunk slots are free (fc1-bias ring lives there)
     float mu2, rs2;
@@ -830,12 +663,7 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
     unsigned k4v = 0x00040004u;
     asm volatile("" : "+v"(k4v));
     const int woff0 = L.l31 * (E * 2) + ((L.g ^ L.fl) << 4);
-#ifdef X_NOMLP
-    for (int chunk = 0; chunk < HID / 64; ++chunk) BAR(16 + chunk);
-    for (int chunk = 0; chunk < 0; ++chunk) {
-#else
     for (int chunk = 0; chunk < HID / 64; ++chunk) {
-#endif
       BAR(16 + chunk);                            // steps 15 .. 26
       const unsigned st_off = (unsigned)((chunk & 1) ? ST1_OFF : ST0_OFF);
       const unsigned char* sW1 = smem + st_off;
@@ -850,19 +678,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
         for (int r = 0; r < 16; ++r) a1[r] = 0.f;
         int wbase = woff0 + ht * 32 * (E * 2);
         asm volatile("" : "+v"(wbase));
-#ifdef X_NOPIPE
-        Frag<bf16> fb;
-#pragma unroll
-        for (int c = 0; c < 12; ++c) {
-          Frag<bf16> fx;
-#ifdef X_HALFW
-          if ((c & 1) == 0)
-#endif
-          fb.v = *reinterpret_cast<const bf16x8*>(sW1 + ((wbase ^ ((c % 4) << 5)) + 128 * (c / 4)));
-          fx.v = as_bf16x8(fa.v[c]);
-          mma(a1, fb, fx);
-        }
-#else
         {
           Frag<bf16> fb[12];
 #pragma unroll
@@ -890,7 +705,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
         for (int bt = 0; bt < 6; ++bt)
           fw2[bt].v = *reinterpret_cast<const bf16x8*>(smem + (w2o ^ (unsigned)((2 * ht) << 5)) + bt * 32 * ROWB);
         __builtin_amdgcn_sched_barrier(0);
-#endif
         Frag<bf16> pg[2];
         if (handed && ht == 0 && chunk > 0) {                      // the DMA wave has taken the previous chunk's tiles (normally long ago)
           while (__builtin_amdgcn_readfirstlane(*flag) < chunk) __builtin_amdgcn_s_sleep(1);
@@ -908,10 +722,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
             const f32x2 uu = f32x2{a1[8 * hs + j], a1[8 * hs + j + 1]} + (j < 4 ? f32x2{bl[j], bl[j + 1]} : f32x2{bh[j - 4], bh[j - 3]});
             const bf16x2v pbv = {(bf16)uu[0], (bf16)uu[1]};
             pb[jj] = __builtin_bit_cast(unsigned, pbv);
-#ifdef X_NOGELU      // (experiments only, wrong numbers: what the table GELU's index arithmetic and lookups cost -- gelu = gelu' = u)
-            agv[jj] = alo[jj] = ahi[jj] = 0;
-            continue;
-#endif
             unsigned p1, p2, ak, i4, sg;
             asm("v_pk_min_u16 %0, %1, %2" : "=v"(p1) : "v"(pb[jj]), "s"(kneg));
             asm("v_pk_min_i16 %0, %1, %2" : "=v"(p2) : "v"(p1), "s"(kpos));
@@ -925,7 +735,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
             alo[jj] = i4 & 0xffffu;
             ahi[jj] = i4 >> 16;
           }
-#ifndef X_NOGELU
           asm volatile(
               "ds_read_b32 %0, %8\n\tds_read_b32 %1, %9\n\tds_read_b32 %2, %10\n\tds_read_b32 %3, %11\n\t"
               "ds_read_b32 %4, %12\n\tds_read_b32 %5, %13\n\tds_read_b32 %6, %14\n\tds_read_b32 %7, %15\n\t"
@@ -933,19 +742,14 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
               : "=&v"(e0[0]), "=&v"(e1[0]), "=&v"(e0[1]), "=&v"(e1[1]), "=&v"(e0[2]), "=&v"(e1[2]), "=&v"(e0[3]), "=&v"(e1[3])
               : "v"(alo[0]), "v"(ahi[0]), "v"(alo[1]), "v"(ahi[1]), "v"(alo[2]), "v"(ahi[2]), "v"(alo[3]), "v"(ahi[3])
               : "memory");
-#endif
           u32x4 gq, dq;
 #pragma unroll
           for (int jj = 0; jj < 4; ++jj) {
-#ifdef X_NOGELU
-            gq[jj] = dq[jj] = pb[jj];
-#else
             const unsigned dpair = __builtin_amdgcn_perm(e1[jj], e0[jj], 0x05040100u);
             unsigned gm;
             asm("v_pk_sub_u16 %0, %1, %2" : "=v"(gm) : "v"(agv[jj]), "v"(dpair));
             gq[jj] = (pb[jj] & 0x80008000u) | gm;
             dq[jj] = __builtin_amdgcn_perm(e1[jj], e0[jj], 0x07060302u);
-#endif
           }
           gv = __builtin_bit_cast(bf16x8, gq);
           dv = __builtin_bit_cast(bf16x8, dq);
@@ -956,21 +760,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
             *reinterpret_cast<bf16x8*>(smem + to + tpoff) = dv;
           }
         }
-#ifdef X_NOPIPE
-#pragma unroll
-        for (int hs = 0; hs < 2; ++hs) {
-          const int s = 2 * ht + hs;
-          Frag<bf16> fw[6];
-#pragma unroll
-          for (int bt = 0; bt < 6; ++bt)
-#ifdef X_HALFW
-            if (bt & 1) fw[bt].v = fw[bt - 1].v; else
-#endif
-            fw[bt].v = *reinterpret_cast<const bf16x8*>(smem + (w2o ^ (unsigned)(s << 5)) + bt * 32 * ROWB);
-#pragma unroll
-          for (int bt = 0; bt < 6; ++bt) mma(acc2[bt], fw[bt], pg[hs]);
-        }
-#else
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int bt = 0; bt < 6; ++bt)
@@ -987,7 +776,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
         }
         __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
         __builtin_amdgcn_sched_barrier(0);
-#endif
       }
       // the chunk's gelu / gelu' tiles out as whole 128-byte row pieces (handed tiles: written out before the barrier behind which
       // the DMA wave takes them)
@@ -1004,7 +792,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
             v0[i] = *reinterpret_cast<const bf16x8*>(smem + so);
             v1[i] = *reinterpret_cast<const bf16x8*>(smem + so + tpoff);
           }
-#ifndef X_NOSAVE
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const int idx = ln + 64 * i, row = idx >> 3, vec = idx & 7;
@@ -1012,7 +799,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
             gstore(b.gl + go, v0[i]);
             gstore(b.gp + go, v1[i]);
           }
-#endif
         } else {
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
@@ -1022,10 +808,8 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_fwd_kernel(ChainArgs p) {
               const bf16x8 v0 = *reinterpret_cast<const bf16x8*>(smem + so);
               const bf16x8 v1 = *reinterpret_cast<const bf16x8*>(smem + so + tpoff);
               const size_t go = (grow0 + row) * HID + chunk * 64 + vec * 8;
-#ifndef X_NOSAVE
               gstore(b.gl + go, v0);
               gstore(b.gp + go, v1);
-#endif
             }
           }
         }

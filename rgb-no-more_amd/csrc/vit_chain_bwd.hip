@@ -25,7 +25,7 @@
 #include <type_traits>
 #include "internal.h"
 #include "ln_bwd_rows.h"
-#include "tile128.h"
+#include "chain_common.h"
 #include "../../include/rgbnm.h"
 
 namespace {
@@ -35,15 +35,7 @@ constexpr int NCW = 7, NTHREADS = 64 * (NCW + 1), CTHREADS = 64 * NCW, BM = 32 *
 constexpr int ARR = NPAD * ROWB, SLOT = 24576, STAGE = 2 * SLOT, CH = 64, NCHUNK = HID / CH;
 constexpr int CP = E + 4;                           // pitch (elements) of the LayerNorm-backward staging tile
 constexpr int SMEM = 163840;
-#ifndef PIPE_P
-#define PIPE_P 6
-#endif
-#ifndef PIPE_M1
-#define PIPE_M1 5
-#endif
-#ifndef PIPE_X
-#define PIPE_X 7
-#endif
+constexpr int PIPE_P = 6, PIPE_M1 = 5, PIPE_X = 7;     // fragment reads requested ahead of the MFMAs in phases P, M (first GEMM), X
 // ---- M: two weight stages | per wave: gelu' tile, du tile
 constexpr int M_STG = 2 * STAGE;                    // 98304
 constexpr int TILE = 32 * ROWB;                     // 4096
@@ -80,31 +72,9 @@ struct BwdArgs {              // passed BY VALUE (kernel argument segment): noth
   float scale;
 };
 
-// the attention phases' row_pair_mma (tile128.h) in its pinned order; XB_ROWPIPE=0: the plain loop (experiments)
-#ifndef XB_ROWPIPE
-#define XB_ROWPIPE 1
-#endif
-// Global stores: XB_NT bit 0 = du (read again only by the weight-gradient launch) non-temporal, bit 1 = the gradient tiles the DMA
-// wave writes (d(q, k, v): read back by phase X of the same workgroup), bit 2 = d(attention output) tiles (read back by phase A)
-#ifndef XB_NT
-#define XB_NT 1
-#endif
-// Loads: XB_NTLD bit 0 = the gelu' rows of phase M (read once) non-temporal, bit 1 = the K / V / Q / dO arrays of phase A (LDS-DMA aux = 2)
-#ifndef XB_NTLD
-#define XB_NTLD 0
-#endif
-constexpr int A_AUX = (XB_NTLD & 2) ? 2 : 0;
-template <bool NT, typename V, typename P>
-__device__ __forceinline__ void gstore(P* ptr, const V& v) {
-#ifdef XB_NOSTORE     // (experiments only, wrong gradients downstream: the kernel without the stores this helper issues)
-  if ((XB_NOSTORE & 1) && NT) return;          // bit 0: du (the only non-temporal stream)
-  if ((XB_NOSTORE & 2) && !NT) return;         // bit 1: the d(q, k, v) / d(attention output) tiles
-#endif
-  if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<V*>(ptr));
-  else *reinterpret_cast<V*>(ptr) = v;
-}
-
-struct Rows { u32x4 v[12]; };      // 12 operand fragments: features 16 c + 8 g + (0..7) of the lane's token (vit_chain.hip)
+// du is read again only by the weight-gradient launch: a NON-TEMPORAL store.  The gradient tiles the DMA wave writes (d(q, k, v):
+// read back by phase X of the same workgroup) and the d(attention output) tiles (read back by phase A) are plain stores.
+__device__ __forceinline__ void store_du(bf16* ptr, const bf16x8& v) { __builtin_nontemporal_store(v, reinterpret_cast<bf16x8*>(ptr)); }
 
 // the seven waves' own 32 x 64 pieces of a [N][ld] matrix (columns c0 .. c0 + 63) -> row tiles, chunk q of row r at q ^ (r & 7)
 __device__ __forceinline__ void dma_row_tiles(const bf16* __restrict__ src, int ld, unsigned char* dst, int lane) {
@@ -135,60 +105,17 @@ __device__ __forceinline__ void tile_out(unsigned char* smem, unsigned stg, cons
   for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const u32x4*>(smem + ro + i * 8 * ROWB);
   if (live == 32) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) gstore<(XB_NT & 4) != 0>(gp + (size_t)i * 8 * ld, v[i]);
+    for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4*>(gp + (size_t)i * 8 * ld) = v[i];
   } else {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      if (i * 8 + rl < live) gstore<(XB_NT & 4) != 0>(gp + (size_t)i * 8 * ld, v[i]);
+      if (i * 8 + rl < live) *reinterpret_cast<u32x4*>(gp + (size_t)i * 8 * ld) = v[i];
   }
   own_tile_fence();
 }
 
-// acc (32 output rows x 32 tokens, swapped) += chunk rows [32 ht .. +31] (384 B rows, pchunk swizzle) . x
-__device__ __forceinline__ void gemm_k192(f32x16& acc, const unsigned char* sW, int ht, const Rows& x, const Geo& L) {
-  int wbase = L.l31 * (E * 2) + ((L.g ^ L.fl) << 4) + ht * 32 * (E * 2);
-  asm volatile("" : "+v"(wbase));
-#pragma unroll
-  for (int c = 0; c < 12; ++c) {
-    Frag<bf16> fb, fx;
-    fb.v = *reinterpret_cast<const bf16x8*>(sW + ((wbase ^ ((c % 4) << 5)) + 128 * (c / 4)));
-    fx.v = as_bf16x8(x.v[c]);
-    mma(acc, fb, fx);
-  }
-}
-
-// Both 32-row halves (ht = 0, 1) of a 64 x 192 chunk times x as ONE stream of 24 MFMAs with the weight fragments requested DEPTH
-// MFMAs ahead (vit_chain.hip gemm_k192x2: left to itself the scheduler emits read -> wait -> MFMA with one fragment buffer, i.e.
-// an exposed LDS latency per MFMA)
-template <int DEPTH>
-__device__ __forceinline__ void gemm_k192x2(f32x16& a0, f32x16& a1, const unsigned char* sW, const Rows& x, const Geo& L) {
-  int wb0 = L.l31 * (E * 2) + ((L.g ^ L.fl) << 4);
-  asm volatile("" : "+v"(wb0));
-  const int wb1 = wb0 + 32 * (E * 2);
-  Frag<bf16> fb[24];
-#pragma unroll
-  for (int i = 0; i < 24; ++i) {
-    const int c = i >> 1;
-    fb[i].v = *reinterpret_cast<const bf16x8*>(sW + ((((i & 1) ? wb1 : wb0) ^ ((c % 4) << 5)) + 128 * (c / 4)));
-  }
-#pragma unroll
-  for (int i = 0; i < 24; ++i) {
-    Frag<bf16> fx;
-    fx.v = as_bf16x8(x.v[i >> 1]);
-    mma((i & 1) ? a1 : a0, fb[i], fx);
-  }
-  __builtin_amdgcn_sched_group_barrier(0x100, DEPTH, 0);
-#pragma unroll
-  for (int i = 0; i < 24 - DEPTH; ++i) {
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-  }
-#pragma unroll
-  for (int i = 0; i < DEPTH; ++i) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-  __builtin_amdgcn_sched_barrier(0);
-}
 // ---- gradient tiles of the attention backward: parked and read back by tile128.h; sibling of attention_v2.hip tiles_write, which
-// has a run-time token count and plain stores (here: NTOK, and the XB_NT / XB_NOSTORE switches of gstore)
+// has a run-time token count (here: NTOK)
 __device__ __forceinline__ void tiles_write(const u32x4 (&v)[NTILE][4], bf16* __restrict__ g0, size_t ld, int lane) {
   const int rl = lane >> 3, seg = lane & 7;
 #pragma unroll
@@ -196,7 +123,7 @@ __device__ __forceinline__ void tiles_write(const u32x4 (&v)[NTILE][4], bf16* __
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int row = wv * 32 + i * 8 + rl;
-      if (row < NTOK) gstore<(XB_NT & 2) != 0>(g0 + (size_t)row * ld + seg * 8, v[wv][i]);
+      if (row < NTOK) *reinterpret_cast<u32x4*>(g0 + (size_t)row * ld + seg * 8) = v[wv][i];
     }
 }
 
@@ -280,9 +207,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
   const int depth = p.depth;
 
   if (w == NCW) {
-#ifdef X_DMAPRIO
-    __builtin_amdgcn_s_setprio(X_DMAPRIO);
-#endif
     // ================================================================ DMA wave
     const int lane = threadIdx.x & 63;
     for (int ib = depth - 1; ib >= 0; --ib) {
@@ -306,11 +230,11 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
       bf16* dq0 = b.dqkv + (size_t)img * NTOK * LDQ;
       const unsigned char* stg0 = smem + A_STG;
       auto issue_kv = [&](int h) {
-        dma_matrix_all<A_AUX>(qkv0 + INNER + h * HD, LDQ, NTOK, smem + A_K, lane);
-        dma_matrix_all<A_AUX>(qkv0 + 2 * INNER + h * HD, LDQ, NTOK, smem + A_V, lane);
+        dma_matrix_all(qkv0 + INNER + h * HD, LDQ, NTOK, smem + A_K, lane);
+        dma_matrix_all(qkv0 + 2 * INNER + h * HD, LDQ, NTOK, smem + A_V, lane);
       };
-      auto issue_q = [&](int h) { dma_matrix_all<A_AUX>(qkv0 + h * HD, LDQ, NTOK, smem + A_Q, lane); };
-      auto issue_g = [&](int h) { dma_matrix_all<A_AUX>(do0 + h * HD, INNER, NTOK, smem + A_G, lane); };
+      auto issue_q = [&](int h) { dma_matrix_all(qkv0 + h * HD, LDQ, NTOK, smem + A_Q, lane); };
+      auto issue_g = [&](int h) { dma_matrix_all(do0 + h * HD, INNER, NTOK, smem + A_G, lane); };
       const unsigned char* xw = wimg + (size_t)NCHUNK * STAGE + 3 * SLOT;                 // the nine qkv chunks
       auto issue_xt = [&](int j) { dma_row_tiles(dq0 + j * 64, LDQ, smem + X_TILES + (j % 3) * X_TSET, lane); };
       wait_vm<0>();                                       // chunk 0 (fetched during the epilogue) has landed long ago
@@ -390,11 +314,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
   }
 
   // ==================================================================== compute waves
-#if defined(X_PRIO) && X_PRIO == 1      // experiments: static issue priority for the younger wave of every SIMD pair
-  if (w >= 4) __builtin_amdgcn_s_setprio(1);
-#elif defined(X_PRIO) && X_PRIO == 2    // ... for the older one
-  if (w < 4) __builtin_amdgcn_s_setprio(1);
-#endif
   const int row0 = 32 * w;
   const int live = NTOK - row0 < 32 ? NTOK - row0 : 32;
   const size_t grow0 = (size_t)img * NTOK + row0;
@@ -432,7 +351,7 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
           int rr = row0 + row;
           rr = rr < NTOK ? rr : NTOK - 1;
           const bf16x8* gsrc = reinterpret_cast<const bf16x8*>(b.gp + ((size_t)img * NTOK + rr) * HID + chunk * CH + vec * 8);
-          gpraw[i] = (XB_NTLD & 1) ? __builtin_nontemporal_load(gsrc) : *gsrc;
+          gpraw[i] = *gsrc;
         }
       };
       load_gp(0);
@@ -459,15 +378,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
           for (int r = 0; r < 16; ++r) a1[r] = 0.f;
           int wbase = woff0 + ht * 32 * (E * 2);
           asm volatile("" : "+v"(wbase));
-#ifdef X_NOPIPE
-#pragma unroll
-          for (int c = 0; c < 12; ++c) {
-            Frag<bf16> fb, fx;
-            fb.v = *reinterpret_cast<const bf16x8*>(sW1 + ((wbase ^ ((c % 4) << 5)) + 128 * (c / 4)));
-            fx.v = as_bf16x8(dyf.v[c]);
-            mma(a1, fb, fx);                               // D rows = hidden (rows stored swap23-ed), D cols = tokens
-          }
-#else
           {
             Frag<bf16> fb[12];
 #pragma unroll
@@ -495,7 +405,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
           for (int bt = 0; bt < 6; ++bt)
             fw2[bt].v = *reinterpret_cast<const bf16x8*>(smem + (w2o ^ (unsigned)((2 * ht) << 5)) + bt * 32 * ROWB);
           __builtin_amdgcn_sched_barrier(0);
-#endif
           Frag<bf16> pg[2];
 #pragma unroll
           for (int hs = 0; hs < 2; ++hs) {
@@ -507,18 +416,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
             pg[hs].v = dv;
             *reinterpret_cast<bf16x8*>(smem + to + TILE) = dv;
           }
-#ifdef X_NOPIPE
-#pragma unroll
-          for (int hs = 0; hs < 2; ++hs) {
-            const int s = 2 * ht + hs;
-            Frag<bf16> fw[6];
-#pragma unroll
-            for (int bt = 0; bt < 6; ++bt)
-              fw[bt].v = *reinterpret_cast<const bf16x8*>(smem + (w2o ^ (unsigned)(s << 5)) + bt * 32 * ROWB);
-#pragma unroll
-            for (int bt = 0; bt < 6; ++bt) mma(acc2[bt], fw[bt], pg[hs]);   // D rows = input features, D cols = tokens
-          }
-#else
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int bt = 0; bt < 6; ++bt)
@@ -534,7 +431,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
           }
           __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
           __builtin_amdgcn_sched_barrier(0);
-#endif
         }
         // the chunk's du tile out as whole row pieces
         own_tile_fence();
@@ -549,13 +445,13 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const int idx = ln + 64 * i, row = idx >> 3, vec = idx & 7;
-            gstore<(XB_NT & 1) != 0>(b.du + (grow0 + row) * HID + chunk * CH + vec * 8, dv0[i]);
+            store_du(b.du + (grow0 + row) * HID + chunk * CH + vec * 8, dv0[i]);
           }
         } else {
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const int idx = ln + 64 * i, row = idx >> 3, vec = idx & 7;
-            if (row < live) gstore<(XB_NT & 1) != 0>(b.du + (grow0 + row) * HID + chunk * CH + vec * 8, dv0[i]);
+            if (row < live) store_du(b.du + (grow0 + row) * HID + chunk * CH + vec * 8, dv0[i]);
           }
         }
       }
@@ -579,12 +475,7 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
         for (int ht = 0; ht < 2; ++ht)
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[ht][r] = 0.f;
-#ifdef X_NOPIPE
-        gemm_k192(acc[0], sW, 0, dxf, L);
-        gemm_k192(acc[1], sW, 1, dxf, L);
-#else
-        gemm_k192x2<PIPE_P>(acc[0], acc[1], sW, dxf, L);
-#endif
+        gemm_k192x2<PIPE_P, true>(acc[0], acc[1], sW, dxf, L);
         u32x4 pc[4];
 #pragma unroll
         for (int ht = 0; ht < 2; ++ht)
@@ -707,7 +598,7 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
             f32x16 sa, da;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { sa[r] = 0.f; da[r] = 0.f; }
-            row_pair_mma<XB_ROWPIPE != 0>(sa, da, Ks, Vs, rb, t, qf, gf);
+            row_pair_mma(sa, da, Ks, Vs, rb, t, qf, gf);
             float ds[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -753,7 +644,7 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
             f32x16 sa, da;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { sa[r] = 0.f; da[r] = 0.f; }
-            row_pair_mma<XB_ROWPIPE != 0>(sa, da, Qs, Gs, rb, t, kf, vf);
+            row_pair_mma(sa, da, Qs, Gs, rb, t, kf, vf);
             float pp[16], ds[16];
 #pragma unroll
             for (int q4 = 0; q4 < 4; ++q4) {
@@ -823,7 +714,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
 #pragma unroll
         for (int bt = 0; bt < 6; ++bt) mma(accx[bt], fw[bt], fx);
       }
-#ifndef X_NOPIPE
       // the 28 fragments of the step (4 x (own rows + 6 weight fragments)) PIPE_X reads ahead of the 24 MFMAs
       __builtin_amdgcn_sched_group_barrier(0x100, PIPE_X, 0);
 #pragma unroll
@@ -832,7 +722,6 @@ __global__ __launch_bounds__(NTHREADS) void vit_chain_bwd_kernel(BwdArgs p) {
         if (i < 28 - PIPE_X) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
-#endif
     }
     // ================================================================ dx = d(x_mid) + LN1'(dxn1); the next block's dy
     // (requesting the operand rows of this epilogue three steps earlier would hide their latency, but 104 more live registers in

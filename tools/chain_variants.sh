@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of builds of the two one-launch encoder kernels on ONE box:  gpurun -- 'ROUNDS=3 bash tools/chain_variants.sh "-DX_PRIO=1" "fwd:-DX_NOPIPE" ...'
+# A/B of builds of the two one-launch encoder kernels on ONE box:  ROUNDS=3 bash tools/chain_variants.sh "-DFOO=1" "fwd:-DBAR" ...
 # Every flag set (plus "base" = as committed) is built first; then ROUNDS rounds run all builds in turn (interleaved: the box's clock drifts
 # by 1 - 2 % over a minute, so single runs of different builds do not compare) under rocprofv3 kernel stats; prints the mean kernel times.
 # A flag set prefixed with "fwd:" / "bwd:" rebuilds only that kernel with the flags.
