@@ -213,6 +213,8 @@ class _FwdState:
         gs = m._grad_sync
         if not m.defer_grad_reduction or (gs is not None and gs.bucket_elems < m._gflat.numel()):
             return                                     # somebody reads block gradients before the backward pass is over
+        if self.grads_attached():
+            return                                     # autograd adds each node's gradients to .grad as the node returns: reduce at once
         pe = m.__dict__.get("_pe_params")
         if pe is None:
             pe = m.__dict__["_pe_params"] = [p for n, p in m._named.items() if n.startswith("patchembed.")]
@@ -240,6 +242,13 @@ class _FwdState:
             L.check(L.lib().rgbnm_reduce_hold_begin(), "reduce_hold_begin")
         self.holding = True
         _HOLDER.st = self
+
+    def grads_attached(self):
+        """True when autograd ADDS this backward's gradients to .grad tensors that already exist (gradient accumulation, or
+        zero_grad(set_to_none=False)): the backward then writes a side buffer (FlatParamModule._grad_buffer), or .grad was attached
+        by hand.  AccumulateGrad reads a node's gradients as soon as the node returns, so nothing of such a pass may be held."""
+        m = self.model
+        return self.gbuf.data_ptr() != m._gflat.data_ptr() or any(p.grad is not None for p in m._named.values())
 
     def end_hold(self):
         if self.holding:
@@ -517,6 +526,8 @@ class _BlockFn(torch.autograd.Function):
             m._check_prep_gen(st)
             st.chain_bwd = st.drop is None and m._chain_backward(a, dy)
             st.dw_pending = []
+            if not st.chain_bwd:
+                m._ensure_block_shadows(st)
         try:
             if st.drop is not None:
                 # the masks are regenerated from this forward's seed (st.drop_seed); dy_m / dxmid_m live in the arena
@@ -640,6 +651,7 @@ class _EncoderFn(torch.autograd.Function):
                     idx -= n
                 dx = a.dx_blk[0]
             else:
+                m._ensure_block_shadows(st)
                 cur = dy
                 for idx in range(D - 1, -1, -1):
                     dx = a.dx[idx & 1]
@@ -735,7 +747,9 @@ class ViT(FlatParamModule):
     gradients are held during the backward pass and run as one launch in front of the patch embedding's backward (rgbnm.h,
     rgbnm_reduce_hold_*): parameter gradients of the blocks are then final only when `backward()` returns.  Safe with no
     gradient exchange or with FlatGradSync's single all-reduce after the backward; NOT with torch DDP or any hook that reads
-    `.grad` during the backward (leave it False there)."""
+    `.grad` during the backward (leave it False there).  A backward whose gradients autograd adds to `.grad` tensors that are still
+    attached (gradient accumulation, `zero_grad(set_to_none=False)`) reads them node by node: the hold is off for that pass
+    (_FwdState.grads_attached) and every node reduces at once -- the same bits, a few more launches."""
     defer_grad_reduction = False
     dw_group_overlapped = 4        # blocks per grouped weight-gradient launch while gradient slices are exchanged during the backward
     single_encoder_node = True     # all blocks as one autograd node when the one-launch forward is on (_EncoderFn); False: one node per block
@@ -854,6 +868,7 @@ class ViT(FlatParamModule):
         self._descs_dev = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
         self._bias_perm = torch.zeros(max(bo, 1), device=dev, dtype=torch.float32)
         self._shadow = {}
+        self._shadow_gen = {}          # per dtype: the _prep_gen of the latest prep that wrote the block Linears' shadows (not skipped)
         if self.embed_kind == "sep":
             # feature column of coefficient (p1, p2) of luma block (pdh, pdw) in the 16x16 tile that the sub-block kernel emits
             self._eye16 = torch.eye(16, device=dev, dtype=torch.float32)
@@ -957,9 +972,10 @@ class ViT(FlatParamModule):
         assert max(idx.max(), idb.max()) < 2 ** 31
         return torch.from_numpy(idx.astype(np.int32)).to(dev), torch.from_numpy(idb.astype(np.int32)).to(dev)
 
-    def _prep(self, cdtype, chains=True):
+    def _prep(self, cdtype, chains=True, shadows=False):
         """fp32 masters -> operand shadows (cast, qkv de-interleave, transposes) and, for the one-launch encoder kernels, their
-        chain images -- ONE launch per step.  chains=False: a step on the per-block kernels (dropout): shadows only."""
+        chain images -- ONE launch per step.  chains=False: a step on the per-block kernels (dropout): shadows only.
+        shadows=True: never skip the block Linears' shadows (_ensure_block_shadows)."""
         if cdtype not in self._shadow:
             self._shadow[cdtype] = torch.zeros(self._sh_total, device=self._flat.device, dtype=cdtype)
         self._cur_dtype = cdtype
@@ -969,7 +985,9 @@ class ViT(FlatParamModule):
         img_b = (self._chain_img_bwd.data_ptr() if chain and L.lib().rgbnm_get_option(b"bwd_chain") and torch.is_grad_enabled()
                  else None)
         # the block Linears' own shadows are only read by the per-operation kernels: skipped while both directions run as chains
-        skip = bool(img_f and (img_b or not torch.is_grad_enabled()) and not self._chain_refused)
+        skip = bool(img_f and (img_b or not torch.is_grad_enabled()) and not self._chain_refused and not shadows)
+        if not skip:
+            self._shadow_gen[cdtype] = self._prep_gen
         L.check(L.lib().rgbnm_prep_weights_chain(L.dt_of(cdtype), self._descs_dev.data_ptr(), self._ndesc, self._flat.data_ptr(),
                                                  self._shadow[cdtype].data_ptr(), self._bias_perm.data_ptr(), img_f, img_b,
                                                  1 if skip else 0, L.stream()), "prep_weights")
@@ -1008,6 +1026,13 @@ class ViT(FlatParamModule):
             warnings.warn("rgb-no-more_amd: another forward of this model ran between a forward and its backward; the backward uses the "
                           "weight operands of the LATEST forward (identical unless the parameters changed in between)", RuntimeWarning,
                           stacklevel=3)
+
+    def _ensure_block_shadows(self, st):
+        """A backward on the per-operation kernels reads the block Linears' shadows.  The prep of its forward skipped them if both
+        chain kernels were switched on then; with bwd_chain switched off since, they hold the weights of some earlier step (or
+        nothing): write them now, from the same masters, as the refusal path of _chain_backward does."""
+        if self._shadow_gen.get(st.arena.cdtype, 0) < st.prep_gen:
+            self._prep(st.arena.cdtype, shadows=True)
 
     def _warn_chain_refused(self, which):
         """The library refused the one-launch encoder kernel for a model that looks eligible from here (E = 192, 3 heads, bf16,
