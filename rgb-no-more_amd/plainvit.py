@@ -177,9 +177,12 @@ class _Arena:
             self.scratch = L.BlockScratch(self.du.data_ptr(), self.dxn.data_ptr(), self.dx_mid.data_ptr(),
                                           self.dattn.data_ptr(), self.dqkv.data_ptr(), self.ws.data_ptr(), ws_bytes)
         self.ws_bytes = ws_bytes
-        self.ws_blk = self.ws_head = self.hold_table = self.hold_table_host = self.scratch_blk = None      # allocated by the first held backward (_FwdState.begin_hold)
+        # ---- built on first use, None until then: every lazily built member is named here and has ONE builder below
         self.chain_table = None      # host array of rgbnm_chain_block, built by the first one-launch forward (ViT._chain_forward)
-        self.chain_bwd_table = self.chain_bwd_dy = None     # the same for the backward (ViT._chain_backward: + per-block operand buffers)
+        self.ws_blk = self.ws_head = self.hold_table = self.hold_table_host = self.scratch_blk = None      # build_hold
+        self.du_blk = self.dxmid_blk = self.dqkv_blk = self.dx_blk = self.dattn_chain = self.lnpart = self.ws_chain = None     # build_chain_bwd
+        self.chain_bwd_table = self.chain_bwd_dy = None     # build_chain_bwd: host array of rgbnm_chain_bwd_block and the dy it was built for
+        self.drop_dy = self.drop_dxmid = None               # build_dropout
         self.acts = []
         for i in range(D):
             b = self.blk[i if need_grad else 0]
@@ -193,8 +196,66 @@ class _Arena:
     def xbuf(self, i):
         return self.x[i] if self.need_grad else self.x[i & 1]
 
+    def build_hold(self, m):
+        """What the first held backward needs (_FwdState.begin_hold): the partial sums of every block now live until the end of the pass."""
+        if self.ws_blk is not None:
+            return
+        dev = self.ws.device
+        self.ws_blk = torch.empty(m.depth * self.ws_bytes, device=dev, dtype=torch.uint8)
+        # ... and the head's three producers side by side (self.ws stays the patch embedding's)
+        self.ws_head = torch.empty(L.lib().rgbnm_head_bwd_workspace(C.byref(self.cfg), m._ncls_pad), device=dev, dtype=torch.uint8)
+        self.hold_table = torch.zeros(L.lib().rgbnm_reduce_hold_table_bytes(), device=dev, dtype=torch.uint8)
+        # host record of what hold_table holds: allocated and freed WITH it (rgbnm.h), so a recycled device address
+        # never inherits somebody else's "already uploaded"
+        self.hold_table_host = torch.zeros(self.hold_table.numel(), dtype=torch.uint8)
+        self.scratch_blk = [L.BlockScratch(self.du.data_ptr(), self.dxn.data_ptr(), self.dx_mid.data_ptr(), self.dattn.data_ptr(),
+                                           self.dqkv.data_ptr(), self.ws_blk.data_ptr() + i * self.ws_bytes, self.ws_bytes)
+                            for i in range(m.depth)]
 
-_HOLDER = threading.local()     # .st = the _FwdState whose held-reduction bracket is open on this (autograd) thread
+    def build_chain_bwd(self, m, dy):
+        """What the one-launch backward needs (ViT._chain_backward): per-block operand buffers, once, and the host array of
+        rgbnm_chain_bwd_block, again whenever the last block's dy has moved."""
+        if self.chain_bwd_table is not None and self.chain_bwd_dy == dy.data_ptr():
+            return
+        from . import chain as _chain
+        D, dev = m.depth, self.ws.device
+        if self.chain_bwd_table is None:
+            M, E, I = self.B * m.n_tokens, m.emb_size, m.inner
+            e = lambda *s, dt=self.cdtype: torch.empty(*s, device=dev, dtype=dt)  # noqa: E731
+            self.du_blk = [e(M, 4 * E) for _ in range(D)]
+            self.dxmid_blk = [e(M, E) for _ in range(D)]
+            self.dqkv_blk = [e(M, 3 * I) for _ in range(D)]
+            self.dx_blk = [e(M, E) for _ in range(D)]
+            self.dattn_chain = e(M, I)
+            self.lnpart = torch.empty(D, 2, self.B, 2, E, device=dev, dtype=torch.float32)
+            # every block's split sums side by side (the weight-gradient GEMMs of several blocks run as one launch); the held
+            # bracket's region serves when build_hold ran first
+            self.ws_chain = self.ws_blk if self.ws_blk is not None else torch.empty(D * self.ws_bytes, device=dev, dtype=torch.uint8)
+        blocks = (L.ChainBwdBlock * D)()
+        for i in range(D):
+            bp, ac = m._bparams[i], self.acts[i]
+            blocks[i] = L.ChainBwdBlock(
+                m._chain_img_bwd.data_ptr() + i * _chain.BLOCK_ELEMS * 2, bp.ln1_g, bp.ln2_g, ac.x_in, ac.mean1, ac.rstd1,
+                ac.qkv, ac.lse, ac.attn, ac.x_mid, ac.mean2, ac.rstd2, ac.u,
+                dy.data_ptr() if i == D - 1 else self.dx_blk[i + 1].data_ptr(),
+                self.du_blk[i].data_ptr(), self.dxmid_blk[i].data_ptr(), self.dqkv_blk[i].data_ptr(), self.dx_blk[i].data_ptr(),
+                self.lnpart[i, 0].data_ptr(), self.lnpart[i, 1].data_ptr())
+        self.chain_bwd_table = blocks
+        self.chain_bwd_dy = dy.data_ptr()
+
+    def build_dropout(self, m):
+        """Masked dy / d(x_mid) of one block's backward with dropout (ViT._begin_dropout)."""
+        if self.need_grad and self.drop_dy is None:
+            M, E = self.B * m.n_tokens, m.emb_size
+            self.drop_dy = torch.empty(M, E, device=self.ws.device, dtype=self.cdtype)
+            self.drop_dxmid = torch.empty(M, E, device=self.ws.device, dtype=self.cdtype)
+
+
+class _Holder(threading.local):
+    st = None                   # the _FwdState whose held-reduction bracket is open on this (autograd) thread
+
+
+_HOLDER = _Holder()
 
 
 class _FwdState:
@@ -202,8 +263,14 @@ class _FwdState:
 
     def __init__(self, model, arena, gbuf):
         self.model, self.arena, self.gbuf = model, arena, gbuf
-        self.holding = False
+        self.prep_gen = model._prep_gen        # the prep this forward ran on (ViT._check_prep_gen, _ensure_block_shadows)
+        self.ln_chain = False                  # per-operation forward: fc2 of block i also emits LN1 of block i+1 (ViT.forward sets it)
+        self.holding = False                   # this state's held-reduction bracket is open (begin_hold .. end_hold / cancel_hold)
         self.drop = self.drop_seed = None      # dropout p > 0: per-block rgbnm_dropout structs and this forward's device seed
+        self.chain_fwd = self.chain_bwd = False        # the one-launch kernel ran this pass's forward / backward data path
+        self.dw_pending = []                   # chain backward: (block, BlockGrads, dy pointer) whose weight gradients are not launched yet
+        self.pe_feat_ok = False                # arena.feat holds this forward's patch features (group embedding)
+        self.pe_done = None                    # data_ptr of the dx0 whose patch-embedding gradients flush_dw has already computed
 
     # ---- held gradient reductions (rgbnm.h rgbnm_reduce_hold_*; ViT.defer_grad_reduction): opened after the head's backward,
     # closed in front of the patch embedding's, whose own reductions run at once (both nodes run on the same autograd thread:
@@ -215,26 +282,13 @@ class _FwdState:
             return                                     # somebody reads block gradients before the backward pass is over
         if self.grads_attached():
             return                                     # autograd adds each node's gradients to .grad as the node returns: reduce at once
-        pe = m.__dict__.get("_pe_params")
-        if pe is None:
-            pe = m.__dict__["_pe_params"] = [p for n, p in m._named.items() if n.startswith("patchembed.")]
-        if not all(p.requires_grad for p in pe):
+        if not all(p.requires_grad for p in m._pe_params_list()):
             return                                     # a frozen patch embedding has no backward node to close the bracket
-        if a.ws_blk is None:                           # the partial sums of every block now live until the end of the pass
-            a.ws_blk = torch.empty(m.depth * a.ws_bytes, device=a.ws.device, dtype=torch.uint8)
-            # ... and the head's three producers side by side (a.ws stays the patch embedding's)
-            a.ws_head = torch.empty(L.lib().rgbnm_head_bwd_workspace(C.byref(a.cfg), m._ncls_pad), device=a.ws.device, dtype=torch.uint8)
-            a.hold_table = torch.zeros(L.lib().rgbnm_reduce_hold_table_bytes(), device=a.ws.device, dtype=torch.uint8)
-            # host record of what hold_table holds: allocated and freed WITH it (rgbnm.h), so a recycled device address
-            # never inherits somebody else's "already uploaded"
-            a.hold_table_host = torch.zeros(a.hold_table.numel(), dtype=torch.uint8)
-            a.scratch_blk = [L.BlockScratch(a.du.data_ptr(), a.dxn.data_ptr(), a.dx_mid.data_ptr(), a.dattn.data_ptr(),
-                                            a.dqkv.data_ptr(), a.ws_blk.data_ptr() + i * a.ws_bytes, a.ws_bytes)
-                             for i in range(m.depth)]
+        a.build_hold(m)
         # one bracket per host thread (the library's queue is thread-local): a second forward state in the same backward pass
         # (two models, or one model applied twice) closes the bracket that is open -- its held reductions run now, its remaining
         # blocks reduce the ordinary way -- before it opens its own
-        other = getattr(_HOLDER, "st", None)
+        other = _HOLDER.st
         if other is not None and other is not self:
             other.end_hold()
         if L.lib().rgbnm_reduce_hold_begin() != 0:     # a bracket left open by a backward pass that died on this thread
@@ -264,6 +318,60 @@ class _FwdState:
             _HOLDER.st = None
             L.lib().rgbnm_reduce_hold_cancel()
 
+    # ---- weight gradients behind the one-launch backward (_BlocksFn.backward): blocks wait in dw_pending until their group runs
+    def dw_group(self):
+        """(blocks per grouped weight-gradient launch, whether a LATER node may finish what this one leaves pending).
+        AccumulateGrad, DDP's bucket hooks and any parameter hook read a node's gradients as soon as the node returns, so a node's
+        weight-gradient GEMMs must have been launched by then (deferring them to block 0's node handed DDP stale
+        buffers).  Only two readers wait: the held bracket, under which by contract nobody reads a block gradient before backward()
+        returns, and the flat exchange, which owns the gradients and is told (`ready`) when a group has run -- both only while the
+        backward writes the model's own flat buffer: a side buffer is ADDED to attached gradients by autograd, node by node.
+        The more blocks share a launch the fewer token splits it has (rgbnm_vit_blocks_bwd_dw): everything a node may take at once
+        it does, except under an exchange that is not held, whose transfers overlap the backward group by group."""
+        m = self.model
+        exchange = m._grad_sync is not None
+        group = m.dw_group_overlapped if exchange and not self.holding else m.depth
+        return min(group, CHAIN_MAX_DEPTH), self.gbuf.data_ptr() == m._gflat.data_ptr() and (self.holding or exchange)
+
+    def flush_dw(self, whole_encoder):
+        """ONE grouped launch for the blocks in dw_pending (descending), then their gradients are final: tell the exchange.
+        whole_encoder: the caller is the node of all blocks, which returns a.dx_blk[0] -- the launch that holds every block may take
+        the patch embedding's weight gradient along (same token axis: 252 + 4 = 256 tiles; its own launch and partial sums are gone)."""
+        m, a = self.model, self.arena
+        pend, self.dw_pending = self.dw_pending, []
+        n = len(pend)
+        scs = [L.BlockScratch(a.du_blk[i].data_ptr(), a.dxn.data_ptr(), a.dxmid_blk[i].data_ptr(), a.dattn_chain.data_ptr(),
+                              a.dqkv_blk[i].data_ptr(), a.ws_chain.data_ptr() + i * a.ws_bytes, a.ws_bytes) for i, _, _ in pend]
+        pa = (C.POINTER(L.BlockActs) * n)(*[C.pointer(a.acts[i]) for i, _, _ in pend])
+        pg = (C.POINTER(L.BlockGrads) * n)(*[C.pointer(g) for _, g, _ in pend])
+        ps = (C.POINTER(L.BlockScratch) * n)(*[C.pointer(x) for x in scs])
+        pdy = (C.c_void_p * n)(*[d for _, _, d in pend])
+        p2 = (C.c_void_p * n)(*[a.lnpart[i, 0].data_ptr() for i, _, _ in pend])
+        p1 = (C.c_void_p * n)(*[a.lnpart[i, 1].data_ptr() for i, _, _ in pend])
+        if (whole_encoder and n == m.depth and m.embed_kind == "group" and self.pe_feat_ok
+                and all(p.requires_grad for p in m._pe_params_list())):
+            gw, gb = self.pe_grads()
+            L.check(L.lib().rgbnm_vit_blocks_bwd_dw_pe(C.byref(a.cfg), n, pa, pg, ps, pdy, p2, p1, a.dx_blk[0].data_ptr(),
+                                                       a.feat.data_ptr(), gw.data_ptr(), gb.data_ptr(), a.ws.data_ptr(), a.ws_bytes,
+                                                       L.stream()), "vit_blocks_bwd_dw_pe")
+            self.pe_done = a.dx_blk[0].data_ptr()
+        else:
+            L.check(L.lib().rgbnm_vit_blocks_bwd_dw(C.byref(a.cfg), n, pa, pg, ps, pdy, p2, p1, L.stream()), "vit_blocks_bwd_dw")
+        if m._grad_sync is not None:
+            for i, _, _ in pend:
+                m._grad_sync.ready(self.gbuf, m._block_names[i])
+
+    # ---- what the four patch-embedding nodes' backwards share
+    def pe_grads(self):
+        return [self.model._gview(self.gbuf, n) for n in self.model._pe_names]
+
+    def pe_return(self, grads, tail=()):
+        """The last gradients of the step: flush the exchange (parallel.py); the node's return value (y, cbcr, st take none)."""
+        m = self.model
+        if m._grad_sync is not None:
+            m._grad_sync.ready(self.gbuf, m._pe_names, last=True)
+        return (None, None, None) + tuple(grads) + tail
+
     def __del__(self):
         try:
             self.model._release_arena(self.arena)
@@ -291,20 +399,18 @@ class _PatchEmbedFn(torch.autograd.Function):
         st = ctx.st
         m, a = st.model, st.arena
         dx0 = dx0.contiguous()
-        gw, gb = m._gview(st.gbuf, "patchembed.projection.0.weight"), m._gview(st.gbuf, "patchembed.projection.0.bias")
+        gw, gb = st.pe_grads()
         # held reductions (head, encoder blocks and this node's own: a.ws is no other node's region) run as ONE launch now, before
         # the exchange
         try:
-            if getattr(st, "pe_done", None) != dx0.data_ptr():       # (else: computed by the encoder node's grouped launch)
+            if st.pe_done != dx0.data_ptr():       # (else: computed by the encoder node's grouped launch)
                 L.check(L.lib().rgbnm_patch_embed_bwd(C.byref(a.cfg), dx0.data_ptr(), a.feat.data_ptr(), gw.data_ptr(),
                                                       gb.data_ptr(), a.ws.data_ptr(), a.ws_bytes, L.stream()), "patch_embed_bwd")
         except BaseException:
             st.cancel_hold()
             raise
         st.end_hold()
-        if m._grad_sync is not None:            # last gradients of the step: flush the exchange (parallel.py)
-            m._grad_sync.ready(st.gbuf, ["patchembed.projection.0.weight", "patchembed.projection.0.bias"], last=True)
-        return None, None, None, gw, gb, None
+        return st.pe_return((gw, gb), tail=(None,))
 
 
 _PE2_NAMES = ["patchembed.projection_Y.1.weight", "patchembed.projection_Y.1.bias", "patchembed.projection_C.1.weight",
@@ -349,7 +455,7 @@ class _PatchEmbed2Fn(torch.autograd.Function):
         Ey = E // 6 * 4
         dx0 = dx0.contiguous()
         es = a.feat.element_size()
-        gr = [m._gview(st.gbuf, n) for n in _PE2_NAMES]
+        gr = st.pe_grads()
         ws, wsb = a.ws.data_ptr(), a.ws_bytes
         # d linearMix (the identity part of the shadow has no gradient)
         L.check(lib.rgbnm_gemm_tn(dt, dx0.data_ptr(), E, a.pe_g.data_ptr(), E, gr[4].data_ptr(), gr[5].data_ptr(), M, E,
@@ -362,9 +468,7 @@ class _PatchEmbed2Fn(torch.autograd.Function):
                                   256, 0, 0, ws, wsb, L.stream()), "pe2 dWy")
         L.check(lib.rgbnm_gemm_tn(dt, dh.data_ptr() + Ey * es, E, a.feat.data_ptr() + 256 * es, 384, gr[2].data_ptr(),
                                   gr[3].data_ptr(), M, E - Ey, 128, 0, 0, ws, wsb, L.stream()), "pe2 dWc")
-        if m._grad_sync is not None:
-            m._grad_sync.ready(st.gbuf, _PE2_NAMES, last=True)
-        return (None, None, None) + tuple(gr)
+        return st.pe_return(gr)
 
 
 _PES_NAMES = ([f"patchembed.LinearY.{i}.{k}" for i in range(4) for k in ("weight", "bias")] +
@@ -406,7 +510,7 @@ class _PatchEmbedSepFn(torch.autograd.Function):
         m, a = st.model, st.arena
         lib, dt, M, E = L.lib(), a.cfg.dtype, a.cfg.B * a.cfg.N, a.cfg.E
         dx0 = dx0.contiguous()
-        gr = [m._gview(st.gbuf, n) for n in _PES_NAMES]
+        gr = st.pe_grads()
         ws, wsb = a.ws.data_ptr(), a.ws_bytes
         L.check(lib.rgbnm_gemm_tn(dt, dx0.data_ptr(), E, a.pe_g.data_ptr(), E, gr[12].data_ptr(), gr[13].data_ptr(), M, E,
                                   E, 0, 0, ws, wsb, L.stream()), "pe-sep dWmix")
@@ -421,9 +525,7 @@ class _PatchEmbedSepFn(torch.autograd.Function):
         for i in range(6):                                   # diagonal blocks of the dense gradient = the six Linears
             gr[2 * i].copy_(dwbd[i * e6:(i + 1) * e6].index_select(1, m._sep_cols[i]))
             gr[2 * i + 1].copy_(dbcat[i * e6:(i + 1) * e6])
-        if m._grad_sync is not None:
-            m._grad_sync.ready(st.gbuf, _PES_NAMES, last=True)
-        return (None, None, None) + tuple(gr)
+        return st.pe_return(gr)
 
 
 _PE3_NAMES = ["patchembed.projectionY.1.weight", "patchembed.projectionY.1.bias", "patchembed.projectionC.1.weight",
@@ -469,209 +571,98 @@ class _PatchEmbedConcatFn(torch.autograd.Function):
         dxv = dx0.contiguous().view(B, 294, E)
         dty = dxv[:, :196].contiguous()
         dtc = dxv[:, 196:].contiguous()
-        gr = [m._gview(st.gbuf, n) for n in _PE3_NAMES]
+        gr = st.pe_grads()
         ws, wsb = a.ws.data_ptr(), a.ws_bytes
         L.check(lib.rgbnm_gemm_tn(dt, dty.data_ptr(), E, a.feat.data_ptr(), 384, gr[0].data_ptr(), gr[1].data_ptr(),
                                   B * 196, E, 256, 0, 0, ws, wsb, L.stream()), "pe3 dWy")
         L.check(lib.rgbnm_gemm_tn(dt, dtc.data_ptr(), E, a.featC.data_ptr(), 384, gr[2].data_ptr(), gr[3].data_ptr(),
                                   B * 98, E, 256, 0, 0, ws, wsb, L.stream()), "pe3 dWc")
-        if m._grad_sync is not None:
-            m._grad_sync.ready(st.gbuf, _PE3_NAMES, last=True)
-        return (None, None, None) + tuple(gr)
+        return st.pe_return(gr)
 
 
-class _BlockFn(torch.autograd.Function):
+class _BlocksFn(torch.autograd.Function):
+    """Encoder blocks [lo, hi) as ONE autograd node.  ViT.forward applies it once as (0, depth) when the one-launch forward is
+    switched on (single_encoder_node): the forward is then one C call (rgbnm_vit_chain_fwd), the backward one
+    (rgbnm_vit_chain_bwd) plus the grouped weight-gradient launch(es) -- instead of twelve pass-through nodes whose Python /
+    autograd bookkeeping was 1.3 ms of the 2.5 ms an eager step costs the host.  Otherwise (dropout, other dtypes and widths,
+    single_encoder_node = False) it is applied once per block as (i, i + 1).  The one-launch kernels serve either layout: the node
+    of block 0 runs the whole forward and the node of the last block the whole backward data path, the others hand buffers on;
+    should a kernel not be eligible (an option switched off, no usable GELU table), every node runs the per-operation C entries
+    for its own blocks."""
+
     @staticmethod
-    def forward(ctx, x, st, idx, *params):
+    def forward(ctx, x, st, lo, hi, *params):
         m, a = st.model, st.arena
-        assert x.data_ptr() == a.xbuf(idx).data_ptr()
+        assert x.data_ptr() == a.xbuf(lo).data_ptr()
+        ctx.st, ctx.lo, ctx.hi = st, lo, hi
         if st.drop is not None:
             # dropout p > 0 (ViT.train_dropout): the per-block entries with the masked epilogues (rgbnm.h rgbnm_vit_block_fwd_drop)
-            L.check(L.lib().rgbnm_vit_block_fwd_drop(C.byref(a.cfg), C.byref(m._bparams[idx]), C.byref(a.acts[idx]),
-                                                     C.byref(st.drop[idx]), L.stream()), "vit_block_fwd_drop")
-            ctx.st, ctx.idx = st, idx
-            return a.xbuf(idx + 1).detach()
-        # the whole encoder forward as ONE launch (rgbnm.h rgbnm_vit_chain_fwd): block 0's node runs it, the nodes of the other
-        # blocks only hand their output buffer on -- the autograd graph (one backward node per block) stays what it was
-        if idx == 0:
+            for idx in range(lo, hi):
+                L.check(L.lib().rgbnm_vit_block_fwd_drop(C.byref(a.cfg), C.byref(m._bparams[idx]), C.byref(a.acts[idx]),
+                                                         C.byref(st.drop[idx]), L.stream()), "vit_block_fwd_drop")
+            return a.xbuf(hi).detach()
+        if lo == 0:
             st.chain_fwd = m._chain_forward(a)
-        if st.chain_fwd:
-            ctx.st, ctx.idx = st, idx
-            return a.xbuf(idx + 1).detach()
-        # consecutive blocks are chained: fc2 of block i also emits LN1 of block i+1 (rgbnm.h, rgbnm_vit_block_fwd_chain)
-        chain = st.ln_chain
-        last = idx + 1 >= m.depth
-        nxt_p = C.byref(m._bparams[idx + 1]) if chain and not last else None
-        nxt_a = C.byref(a.acts[idx + 1]) if chain and not last else None
-        L.check(L.lib().rgbnm_vit_block_fwd_chain(C.byref(a.cfg), C.byref(m._bparams[idx]), C.byref(a.acts[idx]),
-                                                  1 if (chain and idx > 0) else 0, nxt_p, nxt_a, L.stream()),
-                "vit_block_fwd")
-        ctx.st, ctx.idx = st, idx
-        return a.xbuf(idx + 1).detach()
-
-    @staticmethod
-    def backward(ctx, dy):
-        st, idx = ctx.st, ctx.idx
-        m, a = st.model, st.arena
-        dy = dy.contiguous()
-        dx = a.dx[idx & 1]
-        if dx.data_ptr() == dy.data_ptr():
-            dx = a.dx[(idx + 1) & 1]
-        grads = [m._gview(st.gbuf, n) for n in m._block_names[idx]]
-        g = L.BlockGrads(*[t.data_ptr() for t in grads])
-        scratch = a.scratch_blk[idx] if st.holding else a.scratch
-        # the data path of EVERY block's backward as one launch (rgbnm.h rgbnm_vit_chain_bwd), issued by the first block node
-        # that runs (the last block); each node then only launches its weight-gradient GEMMs and reductions
-        if idx == m.depth - 1:
-            m._check_prep_gen(st)
-            st.chain_bwd = st.drop is None and m._chain_backward(a, dy)
-            st.dw_pending = []
-            if not st.chain_bwd:
-                m._ensure_block_shadows(st)
-        try:
-            if st.drop is not None:
-                # the masks are regenerated from this forward's seed (st.drop_seed); dy_m / dxmid_m live in the arena
-                L.check(L.lib().rgbnm_vit_block_bwd_drop(C.byref(a.cfg), C.byref(m._bparams[idx]), C.byref(a.acts[idx]),
-                                                         C.byref(g), C.byref(scratch), C.byref(st.drop[idx]), dy.data_ptr(),
-                                                         dx.data_ptr(), L.stream()), "vit_block_bwd_drop")
-            elif getattr(st, "chain_bwd", False):
-                # the weight-gradient GEMMs of several blocks share ONE grouped launch (rgbnm_vit_blocks_bwd_dw: the more blocks,
-                # the fewer token splits); a block's gradients are final -- and handed to the exchange -- when its group has run
-                dx = a.dx_blk[idx]
-                st.dw_pending.append((idx, g, dy.data_ptr()))       # (no reference to the gradient views: autograd must be able to adopt them)
-                if st.gbuf.data_ptr() != m._gflat.data_ptr():
-                    group = 1          # a side buffer that autograd ADDS to attached gradients when this node returns: no deferring
-                elif st.holding:
-                    group = m.depth    # held reductions: by contract nobody reads a block gradient before backward() returns
-                elif m._grad_sync is not None:
-                    group = m.dw_group_overlapped      # the flat exchange owns the gradients and is told (ready) when a group has run
-                else:
-                    # plain autograd / torch DDP: AccumulateGrad, DDP's bucket hooks and any param hook read the gradient as soon as
-                    # THIS node returns, so its weight-gradient GEMMs must have been launched by then (deferring them to
-                    # block 0's node handed DDP stale buffers)
-                    group = 1
-                if len(st.dw_pending) >= min(group, CHAIN_MAX_DEPTH) or idx == 0:
-                    pend, st.dw_pending = st.dw_pending, []
-                    n = len(pend)
-                    scs = [L.BlockScratch(a.du_blk[i].data_ptr(), a.dxn.data_ptr(), a.dxmid_blk[i].data_ptr(), a.dattn_chain.data_ptr(),
-                                          a.dqkv_blk[i].data_ptr(), a.ws_chain.data_ptr() + i * a.ws_bytes, a.ws_bytes)
-                           for i, _, _ in pend]
-                    pa = (C.POINTER(L.BlockActs) * n)(*[C.pointer(a.acts[i]) for i, _, _ in pend])
-                    pg = (C.POINTER(L.BlockGrads) * n)(*[C.pointer(gg) for _, gg, _ in pend])
-                    ps = (C.POINTER(L.BlockScratch) * n)(*[C.pointer(x) for x in scs])
-                    pdy = (C.c_void_p * n)(*[d for _, _, d in pend])
-                    p2 = (C.c_void_p * n)(*[a.lnpart[i, 0].data_ptr() for i, _, _ in pend])
-                    p1 = (C.c_void_p * n)(*[a.lnpart[i, 1].data_ptr() for i, _, _ in pend])
-                    L.check(L.lib().rgbnm_vit_blocks_bwd_dw(C.byref(a.cfg), n, pa, pg, ps, pdy, p2, p1, L.stream()), "vit_blocks_bwd_dw")
-                    if m._grad_sync is not None:
-                        for i, _, _ in pend[:-1]:
-                            m._grad_sync.ready(st.gbuf, m._block_names[i])
-                else:
-                    by_name = dict(zip(m._block_names[idx], grads))
-                    return (dx, None, None) + tuple(by_name[n] for n in m._block_param_order[idx])
-            else:
-                L.check(L.lib().rgbnm_vit_block_bwd(C.byref(a.cfg), C.byref(m._bparams[idx]), C.byref(a.acts[idx]),
-                                                    C.byref(g), C.byref(scratch), dy.data_ptr(), dx.data_ptr(),
-                                                    L.stream()), "vit_block_bwd")
-            if m._grad_sync is not None:        # this block's gradients are final: start their all-reduce now
-                m._grad_sync.ready(st.gbuf, m._block_names[idx])
-        except BaseException:
-            st.cancel_hold()                    # never leave the autograd thread's bracket open behind an exception
-            raise
-        # grads come back in BlockGrads field order; reorder to the order the params were passed in
-        by_name = dict(zip(m._block_names[idx], grads))
-        return (dx, None, None) + tuple(by_name[n] for n in m._block_param_order[idx])
-
-
-class _EncoderFn(torch.autograd.Function):
-    """All encoder blocks as ONE autograd node (the default when the one-launch forward is switched on): the forward is one C call
-    (rgbnm_vit_chain_fwd), the backward one (rgbnm_vit_chain_bwd) plus the grouped weight-gradient launch(es) -- instead of twelve
-    pass-through nodes whose Python / autograd bookkeeping was 1.3 ms of the 2.5 ms an eager step costs the host.  Should a kernel
-    turn out not to be eligible (an option switched off, no usable GELU table), the per-block C entries run inside this node."""
-
-    @staticmethod
-    def forward(ctx, x, st, *params):
-        m, a = st.model, st.arena
-        assert x.data_ptr() == a.xbuf(0).data_ptr()
-        st.chain_fwd = m._chain_forward(a)
         if not st.chain_fwd:
+            # consecutive blocks are chained: fc2 of block i also emits LN1 of block i+1 (rgbnm.h, rgbnm_vit_block_fwd_chain)
             chain = st.ln_chain
-            for idx in range(m.depth):
+            for idx in range(lo, hi):
                 last = idx + 1 >= m.depth
                 nxt_p = C.byref(m._bparams[idx + 1]) if chain and not last else None
                 nxt_a = C.byref(a.acts[idx + 1]) if chain and not last else None
                 L.check(L.lib().rgbnm_vit_block_fwd_chain(C.byref(a.cfg), C.byref(m._bparams[idx]), C.byref(a.acts[idx]),
                                                           1 if (chain and idx > 0) else 0, nxt_p, nxt_a, L.stream()), "vit_block_fwd")
-        ctx.st = st
-        return a.xbuf(m.depth).detach()
+        return a.xbuf(hi).detach()   # fresh tensor object per call (arena buffers are reused across steps)
 
     @staticmethod
     def backward(ctx, dy):
-        st = ctx.st
+        st, lo, hi = ctx.st, ctx.lo, ctx.hi
         m, a = st.model, st.arena
-        D = m.depth
         dy = dy.contiguous()
-        grads = [[m._gview(st.gbuf, n) for n in m._block_names[i]] for i in range(D)]
-        gs = [L.BlockGrads(*[t.data_ptr() for t in grads[i]]) for i in range(D)]
-        m._check_prep_gen(st)
+        grads = [[m._gview(st.gbuf, n) for n in m._block_names[i]] for i in range(lo, hi)]
+        gs = [L.BlockGrads(*[t.data_ptr() for t in g]) for g in grads]
         try:
-            if m._chain_backward(a, dy):
-                # weight gradients: all blocks in one grouped launch, or groups of dw_group_overlapped blocks while gradient slices
-                # are exchanged during the backward (a group's gradients are handed to the exchange as soon as it has run)
-                group = D if (m._grad_sync is None or st.holding) else m.dw_group_overlapped
-                group = min(group, CHAIN_MAX_DEPTH)            # (rgbnm_vit_blocks_bwd_dw takes at most twelve blocks per call)
-                idx = D - 1
-                while idx >= 0:
-                    pend = list(range(idx, max(idx - group, -1), -1))
-                    n = len(pend)
-                    scs = [L.BlockScratch(a.du_blk[i].data_ptr(), a.dxn.data_ptr(), a.dxmid_blk[i].data_ptr(), a.dattn_chain.data_ptr(),
-                                          a.dqkv_blk[i].data_ptr(), a.ws_chain.data_ptr() + i * a.ws_bytes, a.ws_bytes) for i in pend]
-                    pa = (C.POINTER(L.BlockActs) * n)(*[C.pointer(a.acts[i]) for i in pend])
-                    pg = (C.POINTER(L.BlockGrads) * n)(*[C.pointer(gs[i]) for i in pend])
-                    ps = (C.POINTER(L.BlockScratch) * n)(*[C.pointer(x) for x in scs])
-                    pdy = (C.c_void_p * n)(*[dy.data_ptr() if i == D - 1 else a.dx_blk[i + 1].data_ptr() for i in pend])
-                    p2 = (C.c_void_p * n)(*[a.lnpart[i, 0].data_ptr() for i in pend])
-                    p1 = (C.c_void_p * n)(*[a.lnpart[i, 1].data_ptr() for i in pend])
-                    # the launch that holds block 0 also takes the patch embedding's weight gradient (same token axis; dx0 is
-                    # a.dx_blk[0], which this node returns): 252 + 4 = 256 tiles -- its own launch and partial sums are gone
-                    pe = None
-                    if (pend[-1] == 0 and n == D and m.embed_kind == "group" and getattr(st, "pe_feat_ok", False)
-                            and all(p.requires_grad for p in m._pe_params_list())):
-                        pe = (m._gview(st.gbuf, "patchembed.projection.0.weight"), m._gview(st.gbuf, "patchembed.projection.0.bias"))
-                    if pe is None:
-                        L.check(L.lib().rgbnm_vit_blocks_bwd_dw(C.byref(a.cfg), n, pa, pg, ps, pdy, p2, p1, L.stream()), "vit_blocks_bwd_dw")
-                    else:
-                        L.check(L.lib().rgbnm_vit_blocks_bwd_dw_pe(C.byref(a.cfg), n, pa, pg, ps, pdy, p2, p1, a.dx_blk[0].data_ptr(),
-                                                                   a.feat.data_ptr(), pe[0].data_ptr(), pe[1].data_ptr(),
-                                                                   a.ws.data_ptr(), a.ws_bytes, L.stream()), "vit_blocks_bwd_dw_pe")
-                        st.pe_done = a.dx_blk[0].data_ptr()
-                    if m._grad_sync is not None:
-                        for i in pend:
-                            m._grad_sync.ready(st.gbuf, m._block_names[i])
-                    idx -= n
-                dx = a.dx_blk[0]
+            if hi == m.depth:               # the first encoder node of the backward pass: the data path of EVERY block as one launch
+                m._check_prep_gen(st)
+                st.dw_pending = []
+                st.chain_bwd = st.drop is None and m._chain_backward(a, dy)
+                if not st.chain_bwd:
+                    m._ensure_block_shadows(st)
+            if st.chain_bwd:
+                # only the weight-gradient GEMMs and their reductions are left: grouped launches (dw_group states the policy)
+                group, later_node_may_finish = st.dw_group()
+                for idx in range(hi - 1, lo - 1, -1):
+                    # (no reference to the gradient views goes on st: autograd must be able to adopt them)
+                    st.dw_pending.append((idx, gs[idx - lo], dy.data_ptr() if idx == hi - 1 else a.dx_blk[idx + 1].data_ptr()))
+                    if len(st.dw_pending) >= group or idx == 0:
+                        st.flush_dw(lo == 0 and hi == m.depth)
+                if st.dw_pending and not later_node_may_finish:
+                    st.flush_dw(False)
+                dx = a.dx_blk[lo]
             else:
-                m._ensure_block_shadows(st)
                 cur = dy
-                for idx in range(D - 1, -1, -1):
+                for idx in range(hi - 1, lo - 1, -1):
                     dx = a.dx[idx & 1]
                     if dx.data_ptr() == cur.data_ptr():
                         dx = a.dx[(idx + 1) & 1]
                     scratch = a.scratch_blk[idx] if st.holding else a.scratch
-                    L.check(L.lib().rgbnm_vit_block_bwd(C.byref(a.cfg), C.byref(m._bparams[idx]), C.byref(a.acts[idx]),
-                                                        C.byref(gs[idx]), C.byref(scratch), cur.data_ptr(), dx.data_ptr(),
-                                                        L.stream()), "vit_block_bwd")
-                    if m._grad_sync is not None:
+                    if st.drop is not None:
+                        # the masks are regenerated from this forward's seed (st.drop_seed); dy_m / dxmid_m live in the arena
+                        L.check(L.lib().rgbnm_vit_block_bwd_drop(C.byref(a.cfg), C.byref(m._bparams[idx]), C.byref(a.acts[idx]),
+                                                                 C.byref(gs[idx - lo]), C.byref(scratch), C.byref(st.drop[idx]),
+                                                                 cur.data_ptr(), dx.data_ptr(), L.stream()), "vit_block_bwd_drop")
+                    else:
+                        L.check(L.lib().rgbnm_vit_block_bwd(C.byref(a.cfg), C.byref(m._bparams[idx]), C.byref(a.acts[idx]),
+                                                            C.byref(gs[idx - lo]), C.byref(scratch), cur.data_ptr(), dx.data_ptr(),
+                                                            L.stream()), "vit_block_bwd")
+                    if m._grad_sync is not None:        # this block's gradients are final: start their all-reduce now
                         m._grad_sync.ready(st.gbuf, m._block_names[idx])
                     cur = dx
         except BaseException:
             st.cancel_hold()                    # never leave the autograd thread's bracket open behind an exception
             raise
-        out = []
-        for i in range(D):
-            by_name = dict(zip(m._block_names[i], grads[i]))
-            out += [by_name[n] for n in m._block_param_order[i]]
-        return (dx, None) + tuple(out)
+        # grads come back in BlockGrads field order; reorder to the order the params were passed in
+        return (dx, None, None, None) + tuple(g[k] for i, g in zip(range(lo, hi), grads) for k in m._block_grad_perm[i])
 
 
 class _HeadFn(torch.autograd.Function):
@@ -735,8 +726,7 @@ class _HeadFn(torch.autograd.Function):
             raise
         if padded:
             st.begin_hold()
-        by_name = dict(zip(names, grads))
-        return (dx, None) + tuple(by_name[n] for n in m._head_param_order)
+        return (dx, None) + tuple(grads[k] for k in m._head_grad_perm)      # HeadGrads field order -> the order the params were passed in
 
 
 # ------------------------------------------------------------------ the model
@@ -752,7 +742,7 @@ class ViT(FlatParamModule):
     (_FwdState.grads_attached) and every node reduces at once -- the same bits, a few more launches."""
     defer_grad_reduction = False
     dw_group_overlapped = 4        # blocks per grouped weight-gradient launch while gradient slices are exchanged during the backward
-    single_encoder_node = True     # all blocks as one autograd node when the one-launch forward is on (_EncoderFn); False: one node per block
+    single_encoder_node = True     # all blocks as one autograd node when the one-launch forward is on (_BlocksFn); False: one node per block
     # training with drop_p > 0: False refuses (NotImplementedError); True runs the reference's three dropout sites per block on the device
     # (rgbnm.h, dropout mask contract): masks from this library's Philox stream, not torch's, and the per-block kernels instead of
     # the one-launch encoder
@@ -817,6 +807,10 @@ class ViT(FlatParamModule):
         self._flat = None
         self._arenas = {}
         self.compute_dtype = None      # None: follow autocast; or force torch.float32 / torch.bfloat16 / torch.float16
+        # host state that lives as long as the model; what is tied to the device or to the Parameter objects is _flatten's
+        self._prep_gen = 0             # counts _prep calls: the shadows and the chain images are model-global (_check_prep_gen)
+        self._warned_prep_gen = self._warned_chain_forward = self._warned_chain_backward = False      # each warning is given once
+        self._b2pad = self._abp = self._pe_params = None      # reset by every _flatten, which see
 
     # ---------------------------------------------------------------- flat buffers / shadows
     def _names(self):
@@ -830,6 +824,9 @@ class ViT(FlatParamModule):
             raise L.RgbnmError("model parameters must live on a HIP device (no CPU fallback)")
         params = self._pack_parameters()
         offs = self._offs
+        # what was built for the old device or from the old name -> Parameter map (`_named`) goes with them, as _arenas does below:
+        # the padded head's bias buffer, the block parameters in _BlocksFn's argument order, the patch embedding's parameters
+        self._b2pad = self._abp = self._pe_params = None
         # ---- Linear descriptors + shadow layout
         if self.embed_kind == "group":
             lin = [("pe", "patchembed.projection.0", 0)]
@@ -937,6 +934,10 @@ class ViT(FlatParamModule):
         self._head_param_order = [n for n in self._names() if n.startswith("classhead.")]
         self._pe_names = {"group": ["patchembed.projection.0.weight", "patchembed.projection.0.bias"], "sep_sub": _PE2_NAMES,
                           "sep": _PES_NAMES, "concat": _PE3_NAMES}[self.embed_kind]
+        # the kernels hand gradients back in field order, autograd wants them in the order the parameters were passed in
+        # (_block_param_order / _head_param_order): out[j] = grads[perm[j]]
+        self._block_grad_perm = [[names.index(n) for n in order] for names, order in zip(self._block_names, self._block_param_order)]
+        self._head_grad_perm = [self._head_names.index(n) for n in self._head_param_order]
 
     def grad_ready_order(self):
         """[(names, last)] in the order the autograd nodes report finished gradients to the gradient exchange."""
@@ -946,10 +947,15 @@ class ViT(FlatParamModule):
                 [(self._pe_names, True)])
 
     def _pe_params_list(self):
-        pe = self.__dict__.get("_pe_params")
-        if pe is None:
-            pe = self.__dict__["_pe_params"] = [p for n, p in self._named.items() if n.startswith("patchembed.")]
-        return pe
+        if self._pe_params is None:
+            self._pe_params = [p for n, p in self._named.items() if n.startswith("patchembed.")]
+        return self._pe_params
+
+    def _all_block_params(self):
+        """The block parameters in the order the node of all blocks takes them (_BlocksFn as (0, depth))."""
+        if self._abp is None:
+            self._abp = [self._named[n] for order in self._block_param_order for n in order]
+        return self._abp
 
     def _pptr(self, name):
         return self._flat.data_ptr() + self._offs[name] * 4
@@ -979,7 +985,7 @@ class ViT(FlatParamModule):
         if cdtype not in self._shadow:
             self._shadow[cdtype] = torch.zeros(self._sh_total, device=self._flat.device, dtype=cdtype)
         self._cur_dtype = cdtype
-        self._prep_gen = getattr(self, "_prep_gen", 0) + 1        # (the shadows and the chain images are model-global: see _check_prep_gen)
+        self._prep_gen += 1        # (the shadows and the chain images are model-global: see _check_prep_gen)
         chain = chains and cdtype == torch.bfloat16 and self._chain_idx is not None
         img_f = self._chain_img.data_ptr() if chain and L.lib().rgbnm_get_option(b"fwd_chain") else None
         img_b = (self._chain_img_bwd.data_ptr() if chain and L.lib().rgbnm_get_option(b"bwd_chain") and torch.is_grad_enabled()
@@ -1005,7 +1011,7 @@ class ViT(FlatParamModule):
                     self._sh_ptr(f"proj{i}", "ws"), self._sh_ptr(f"proj{i}", "wst"),
                     self._sh_ptr(f"fc1{i}", "ws"), self._sh_ptr(f"fc1{i}", "wst"),
                     self._sh_ptr(f"fc2{i}", "ws"), self._sh_ptr(f"fc2{i}", "wst")))
-            if self._ncls_pad != self.n_classes and getattr(self, "_b2pad", None) is None:
+            if self._ncls_pad != self.n_classes and self._b2pad is None:
                 self._b2pad = torch.zeros(self._ncls_pad, device=self._flat.device, dtype=torch.float32)
             b2 = self._b2pad.data_ptr() if self._ncls_pad != self.n_classes else self._pptr("classhead.ch_linear2.bias")
             hp = L.HeadParams(self._pptr("classhead.ch_lrnorm.weight"), self._pptr("classhead.ch_lrnorm.bias"),
@@ -1021,7 +1027,7 @@ class ViT(FlatParamModule):
         """The operand shadows / chain images a backward reads are the ones of the LATEST forward (one set per model, rewritten by
         every forward).  A forward between a training forward and its backward is harmless while the weights are the same, but
         after an optimizer step (or swapped-in weights) that backward would run against the newer weights: say so."""
-        if getattr(st, "prep_gen", None) != getattr(self, "_prep_gen", None) and not getattr(self, "_warned_prep_gen", False):
+        if st.prep_gen != self._prep_gen and not self._warned_prep_gen:
             self._warned_prep_gen = True
             warnings.warn("rgb-no-more_amd: another forward of this model ran between a forward and its backward; the backward uses the "
                           "weight operands of the LATEST forward (identical unless the parameters changed in between)", RuntimeWarning,
@@ -1038,9 +1044,9 @@ class ViT(FlatParamModule):
         """The library refused the one-launch encoder kernel for a model that looks eligible from here (E = 192, 3 heads, bf16,
         option on): no usable GELU table.  The per-operation kernels run instead -- same results, about half the
         speed -- so say it once instead of silently."""
-        key = "_warned_chain_" + which
-        if not getattr(self, key, False):
-            setattr(self, key, True)
+        key = "_warned_chain_" + which          # _warned_chain_forward / _warned_chain_backward (__init__)
+        if not self.__dict__[key]:
+            self.__dict__[key] = True
             warnings.warn(f"rgb-no-more_amd: the one-launch encoder {which} kernel refused this model (no GELU "
                           f"table); running the per-operation kernels (about 2x slower)", RuntimeWarning, stacklevel=3)
 
@@ -1078,31 +1084,8 @@ class ViT(FlatParamModule):
         if (a.cdtype != torch.bfloat16 or self._chain_idx is None or not a.need_grad
                 or not L.lib().rgbnm_get_option(b"bwd_chain")):
             return False
-        D, dev = self.depth, self._flat.device
-        if a.chain_bwd_table is None or a.chain_bwd_dy != dy.data_ptr():
-            from . import chain as _chain
-            M, E, I = a.B * self.n_tokens, self.emb_size, self.inner
-            if a.chain_bwd_table is None:
-                e = lambda *s, dt=a.cdtype: torch.empty(*s, device=dev, dtype=dt)  # noqa: E731
-                a.du_blk = [e(M, 4 * E) for _ in range(D)]
-                a.dxmid_blk = [e(M, E) for _ in range(D)]
-                a.dqkv_blk = [e(M, 3 * I) for _ in range(D)]
-                a.dx_blk = [e(M, E) for _ in range(D)]
-                a.dattn_chain = e(M, I)
-                a.lnpart = torch.empty(D, 2, a.B, 2, E, device=dev, dtype=torch.float32)
-                # every block's split sums side by side (the weight-gradient GEMMs of several blocks run as one launch)
-                a.ws_chain = a.ws_blk if a.ws_blk is not None else torch.empty(D * a.ws_bytes, device=dev, dtype=torch.uint8)
-            blocks = (L.ChainBwdBlock * D)()
-            for i in range(D):
-                bp, ac = self._bparams[i], a.acts[i]
-                blocks[i] = L.ChainBwdBlock(
-                    self._chain_img_bwd.data_ptr() + i * _chain.BLOCK_ELEMS * 2, bp.ln1_g, bp.ln2_g, ac.x_in, ac.mean1, ac.rstd1,
-                    ac.qkv, ac.lse, ac.attn, ac.x_mid, ac.mean2, ac.rstd2, ac.u,
-                    dy.data_ptr() if i == D - 1 else a.dx_blk[i + 1].data_ptr(),
-                    a.du_blk[i].data_ptr(), a.dxmid_blk[i].data_ptr(), a.dqkv_blk[i].data_ptr(), a.dx_blk[i].data_ptr(),
-                    a.lnpart[i, 0].data_ptr(), a.lnpart[i, 1].data_ptr())
-            a.chain_bwd_table = blocks
-            a.chain_bwd_dy = dy.data_ptr()
+        a.build_chain_bwd(self, dy)
+        D = self.depth
         starts = list(range(0, D, CHAIN_MAX_DEPTH))
         for s0 in reversed(starts):             # the last blocks first; a launch's first block (lowest index) leaves the next launch its dy
             n = min(CHAIN_MAX_DEPTH, D - s0)
@@ -1167,7 +1150,6 @@ class ViT(FlatParamModule):
         self._prep(cdtype, chains=not drop)
         arena = self._acquire_arena(B, cdtype, need_grad)
         st = _FwdState(self, arena, self._grad_buffer() if need_grad else None)
-        st.prep_gen = self._prep_gen
         st.ln_chain = bool(L.lib().rgbnm_vit_ln_chain(C.byref(arena.cfg))) and not drop
         if drop:
             self._begin_dropout(st)
@@ -1183,10 +1165,10 @@ class ViT(FlatParamModule):
             h = _PatchEmbedConcatFn.apply(x, cbcr, st, *[named[n] for n in _PE3_NAMES])
         if (not drop and self.single_encoder_node and cdtype == torch.bfloat16 and self._chain_idx is not None
                 and L.lib().rgbnm_get_option(b"fwd_chain")):
-            h = _EncoderFn.apply(h, st, *self._all_block_params())
+            h = _BlocksFn.apply(h, st, 0, self.depth, *self._all_block_params())
         else:
             for i in range(self.depth):
-                h = _BlockFn.apply(h, st, i, *[named[n] for n in self._block_param_order[i]])
+                h = _BlocksFn.apply(h, st, i, i + 1, *[named[n] for n in self._block_param_order[i]])
         out = _HeadFn.apply(h, st, *[named[n] for n in self._head_param_order])
         if isinstance(out, tuple):
             out, edge = out
@@ -1200,17 +1182,7 @@ class ViT(FlatParamModule):
         a = st.arena
         st.drop_seed = torch.empty(1, device=self._flat.device, dtype=torch.int64).random_(-2 ** 63, None)
         self.last_dropout_seed = st.drop_seed
-        if a.need_grad and getattr(a, "drop_dy", None) is None:
-            M, E = a.B * self.n_tokens, self.emb_size
-            a.drop_dy = torch.empty(M, E, device=self._flat.device, dtype=a.cdtype)       # masked dy / d(x_mid) of one block's backward
-            a.drop_dxmid = torch.empty(M, E, device=self._flat.device, dtype=a.cdtype)
+        a.build_dropout(self)
         dy_m = a.drop_dy.data_ptr() if a.need_grad else None
         dxm_m = a.drop_dxmid.data_ptr() if a.need_grad else None
         st.drop = [L.Dropout(st.drop_seed.data_ptr(), self.drop_p, i, dy_m, dxm_m) for i in range(self.depth)]
-
-    def _all_block_params(self):
-        named = self._named
-        key = id(named)
-        if getattr(self, "_abp_key", None) != key:
-            self._abp_key, self._abp = key, [named[n] for i in range(self.depth) for n in self._block_param_order[i]]
-        return self._abp
