@@ -367,6 +367,37 @@ size_t rgbnm_clip_adamw_wd_workspace(void);
 int rgbnm_clip_adamw_wd_step(float* p, const float* g, float* m, float* v, const unsigned char* wd_flag_per_256,
                              long long n, float lr, float beta1, float beta2, float eps, int step, float wd_factor,
                              float max_norm, float* norm_out, void* workspace, size_t workspace_bytes, void* stream);
+/* The same tail for float16 training under a loss scale that lives on the device: what the reference's default AMP step does
+ * around its optimizers (utils/configs.py:18, 37-40: AMPDTYPE fp16, GradScaler(1.6, 0.625, 600); pipeline_utils.py:541; train.py:
+ * 160-167: scale(loss).backward(), unscale_, clip_grad_norm_, step, step, update(); pipeline_utils.py:399-409: clip_gradscaler to
+ * [2^-4, 2^18]) inside the tail's two launches, with no host sync and never a third launch.
+ * The state block is caller-owned device memory, written by the second launch only, with ordinary stores: */
+typedef struct rgbnm_loss_scale_state {
+  float scale;         /* current loss scale: what the loss was multiplied by, what the gradients in g carry */
+  int growth_tracker;  /* unskipped steps since the last change of the scale (GradScaler._growth_tracker) */
+  int step;            /* Adam steps actually taken: the step a call takes is step + 1 */
+  int skipped;         /* running total of skipped steps */
+  float found_inf;     /* 0 or 1, of the latest call */
+  int reserved[3];     /* bias corrections need no state: they are an fp64 pow of beta and step + 1 on the device */
+} rgbnm_loss_scale_state;
+/* rgbnm_clip_adamw_wd_step's arguments without `step`, then the state and the scaler's constants.
+ * Launch 1 reads scale, forms inv = (float)(1.0 / (double)scale) (GradScaler.unscale_'s reciprocal) and sums (g inv)^2 in the order
+ * of the unscaled entry; it leaves inv, step, scale and the bias corrections of step + 1 (bc1 = (float)(1 - beta1^t), bc2_sqrt =
+ * (float)sqrt(1 - beta2^t), fp64 pow on the device: the expressions of the unscaled entry's host code) in the workspace.
+ * Launch 2 reads those from the workspace only.  Total norm non-finite: p, m, v are not written, skipped += 1, found_inf = 1,
+ * scale = (float)((double)scale * backoff_factor), growth_tracker = 0.  Otherwise g' = (g inv) coef (two roundings, unscale
+ * first), then the arithmetic of the unscaled entry; step += 1, found_inf = 0, growth_tracker += 1, and when it reaches
+ * growth_interval: scale = (float)((double)scale * growth_factor) if that is finite, growth_tracker = 0 -- the arithmetic of
+ * torch._amp_update_scale_.  Then scale is clamped to [scale_min, scale_max].  norm_out (may be NULL) receives the norm of the
+ * UNSCALED gradients (non-finite on a skipped step).
+ * RGBNM_EINVAL for a NULL pointer (norm_out excepted), n <= 0 or n % 256 != 0, growth_interval < 1, a factor that is not > 0,
+ * scale_min > scale_max (or either NaN); RGBNM_EWORKSPACE for a short workspace: nothing is launched, the state is untouched. */
+size_t rgbnm_clip_adamw_wd_scaled_workspace(void);
+int rgbnm_clip_adamw_wd_step_scaled(float* p, const float* g, float* m, float* v, const unsigned char* wd_flag_per_256,
+                                    long long n, float lr, float beta1, float beta2, float eps, float wd_factor, float max_norm,
+                                    float* norm_out, rgbnm_loss_scale_state* state, double growth_factor, double backoff_factor,
+                                    int growth_interval, float scale_min, float scale_max, void* workspace,
+                                    size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Composite stages: one call per autograd node (ViT, plainvit.py:559-611)

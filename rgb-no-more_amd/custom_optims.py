@@ -8,7 +8,12 @@
   `state_dict()` / `load_state_dict()` carry the Adam moments and the step count in torch.optim.AdamW's own layout
   (state[i] = {step, exp_avg, exp_avg_sq} per parameter), so train.py's checkpoint / resume (train.py:195,
   pipeline_utils.py:490-580) works, and a checkpoint written by the reference's AdamW loads here (and vice versa).
+* `DeviceLossScaler` -- torch.amp.GradScaler(1.6, 0.625, 600) + pipeline_utils.clip_gradscaler (train.py:160-167,
+  pipeline_utils.py:399-409, 541) with the scale, the inf / NaN check, the skipped step and the scale update on the device,
+  inside FusedClipAdamWWD's two launches (rgbnm_clip_adamw_wd_step_scaled): fp16 training without a host sync.
 """
+import math
+
 import torch
 from torch.optim.optimizer import Optimizer
 
@@ -39,6 +44,7 @@ class FusedClipAdamWWD(Optimizer):
                                                     weight_decay=weight_decay, max_norm=max_norm))
         self._m = m
         self._step = 0
+        self._dev_step = None          # the DeviceLossScaler whose state block holds the step count while it is the truth
         self._state_ready = False
         self.last_norm = None
 
@@ -48,7 +54,8 @@ class FusedClipAdamWWD(Optimizer):
         if not self._state_ready or self._exp_avg.numel() != m._flat.numel() or self._exp_avg.device != m._flat.device:
             self._exp_avg = torch.zeros_like(m._flat)
             self._exp_avg_sq = torch.zeros_like(m._flat)
-            self._ws = torch.empty(L.lib().rgbnm_clip_adamw_wd_workspace(), device=m._flat.device, dtype=torch.uint8)
+            self._ws = torch.empty(max(L.lib().rgbnm_clip_adamw_wd_workspace(), L.lib().rgbnm_clip_adamw_wd_scaled_workspace()),
+                                   device=m._flat.device, dtype=torch.uint8)
             self._norm = torch.zeros(1, device=m._flat.device, dtype=torch.float32)
             self._gather = None
             self._state_ready = True
@@ -62,8 +69,16 @@ class FusedClipAdamWWD(Optimizer):
             self.state[p] = {"step": torch.tensor(float(self._step)), "exp_avg": m._gview(self._exp_avg, n),
                              "exp_avg_sq": m._gview(self._exp_avg_sq, n)}
 
+    def _read_back_step(self):
+        """After steps under a DeviceLossScaler the step count lives on the device (skipped steps do not count): fetch it.
+        The one host sync of that mode; state_dict() and the first plain step() after it come through here."""
+        if self._dev_step is not None:
+            self._step = self._dev_step._device_step()
+            self._dev_step = None
+
     def state_dict(self):
         self._ensure()
+        self._read_back_step()
         for st in self.state.values():
             st["step"] = torch.tensor(float(self._step))
         return super().state_dict()
@@ -93,6 +108,7 @@ class FusedClipAdamWWD(Optimizer):
         if len(steps) > 1:
             raise ValueError(f"FusedClipAdamWWD keeps ONE step count for all parameters; the state has {sorted(steps)}")
         self._step = steps.pop() if steps else 0
+        self._dev_step = None                        # the loaded count is the truth; the next scaled step uploads it
         self._publish_state()
 
     def _flat_grads(self):
@@ -114,17 +130,151 @@ class FusedClipAdamWWD(Optimizer):
         return self._gather.data_ptr()
 
     @torch.no_grad()
-    def step(self):
+    def step(self, loss_scaler=None):
+        """One fused step.  loss_scaler: a DeviceLossScaler (call it through loss_scaler.step(optimizer), as train.py calls
+        gradscaler.step): the gradients carry its scale; they are unscaled, checked, and the step is taken or skipped on the
+        device, where the scale is updated too.  The Adam step count then lives in the scaler's state block (initialised from
+        the host count on first use; state_dict() reads it back, the only sync; a later plain step() reads it back once
+        first), and last_norm is the norm of the UNSCALED gradients (non-finite on a skipped step).
+        FlatGradSync.wait() stays in front: the gradients are final, and the same on every rank, before the check runs, and
+        the all-reduced sum of a non-finite gradient is non-finite on every rank, so all ranks skip together."""
         self._ensure()
         g = self.param_groups[0]
         m = self._m
-        self._step += 1
+        if loss_scaler is not None and not loss_scaler._enabled:
+            loss_scaler = None
+        if loss_scaler is None:
+            self._read_back_step()
+            self._step += 1
         if m._grad_sync is not None:       # overlapped flat all-reduce (parallel.FlatGradSync): gradients are final after this
             m._grad_sync.wait()
         gptr = self._flat_grads()
-        L.check(L.lib().rgbnm_clip_adamw_wd_step(
-            m._flat.data_ptr(), gptr, self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr(),
-            m._wd_flags.data_ptr(), m._flat.numel(), g["lr"], g["betas"][0], g["betas"][1], g["eps"], self._step,
-            (g["lr"] / g["base_lr"]) * g["weight_decay"], g["max_norm"] if g["max_norm"] else 0.0,
-            self._norm.data_ptr(), self._ws.data_ptr(), self._ws.numel(), L.stream()), "clip_adamw_wd_step")
+        wd_factor = (g["lr"] / g["base_lr"]) * g["weight_decay"]
+        max_norm = g["max_norm"] if g["max_norm"] else 0.0
+        if loss_scaler is None:
+            L.check(L.lib().rgbnm_clip_adamw_wd_step(
+                m._flat.data_ptr(), gptr, self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr(),
+                m._wd_flags.data_ptr(), m._flat.numel(), g["lr"], g["betas"][0], g["betas"][1], g["eps"], self._step,
+                wd_factor, max_norm, self._norm.data_ptr(), self._ws.data_ptr(), self._ws.numel(), L.stream()),
+                "clip_adamw_wd_step")
+        else:
+            s = loss_scaler
+            state = s._device_state(m._flat.device)
+            if self._dev_step is not s:
+                self._read_back_step()                 # (another scaler's count, if there was one)
+                s._set_device_step(self._step)
+                self._dev_step = s
+            L.check(L.lib().rgbnm_clip_adamw_wd_step_scaled(
+                m._flat.data_ptr(), gptr, self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr(),
+                m._wd_flags.data_ptr(), m._flat.numel(), g["lr"], g["betas"][0], g["betas"][1], g["eps"],
+                wd_factor, max_norm, self._norm.data_ptr(), state.data_ptr(), s._growth_factor, s._backoff_factor,
+                s._growth_interval, s._scale_min, s._scale_max, self._ws.data_ptr(), self._ws.numel(), L.stream()),
+                "clip_adamw_wd_step_scaled")
         self.last_norm = self._norm
+
+
+class DeviceLossScaler:
+    """torch.amp.GradScaler for FusedClipAdamWWD with everything on the device.  The defaults are the reference's:
+    GradScaler(growth 1.6, backoff 0.625, interval 600) (utils/configs.py:37-40, pipeline_utils.py:541), clamped after every
+    update to [2^-4, 2^18] (clip_gradscaler, pipeline_utils.py:399-409).  train.py:160-167 becomes
+
+        scaler.scale(loss).backward()
+        scaler.step(optimizer)          # unscale_ + clip_grad_norm_ + both optimizer steps + update + clip_gradscaler
+        scaler.update()                 # no-op, kept for the loop's shape
+
+    with no host sync: scale() multiplies by a device scalar that aliases the state block's scale, the fused tail reads and
+    updates the block (include/rgbnm.h, rgbnm_loss_scale_state).  get_scale(), skipped_steps() and state_dict() sync; they
+    are for logging and checkpoints.  state_dict() has torch.amp.GradScaler's keys, so a scaler state written by the
+    reference's checkpoint (pipeline_utils.py:490-516) loads here and the reverse.  Before the first device use the state is
+    held on the host (as GradScaler holds its init_scale)."""
+
+    def __init__(self, init_scale=2.0 ** 16, growth_factor=1.6, backoff_factor=0.625, growth_interval=600,
+                 scale_min=2.0 ** -4, scale_max=2.0 ** 18, enabled=True):
+        if enabled:
+            if not growth_factor > 0.0 or not backoff_factor > 0.0:
+                raise ValueError("growth_factor and backoff_factor must be positive")
+            if int(growth_interval) < 1:
+                raise ValueError("growth_interval must be at least 1")
+            if not scale_min <= scale_max:
+                raise ValueError("scale_min must not exceed scale_max")
+        self._enabled = bool(enabled)
+        self._growth_factor, self._backoff_factor = float(growth_factor), float(backoff_factor)
+        self._growth_interval = int(growth_interval)
+        self._scale_min, self._scale_max = float(scale_min), float(scale_max)
+        self._host = {"scale": float(init_scale), "_growth_tracker": 0}     # until the state block exists
+        self._state = None          # int32 [8] on the device: rgbnm_loss_scale_state
+        self._scale_t = None        # 0-dim fp32 view of its first word
+
+    def is_enabled(self):
+        return self._enabled
+
+    def _device_state(self, device):
+        if self._state is None:
+            st = torch.zeros(8, dtype=torch.int32)
+            st[:1].view(torch.float32)[0] = self._host["scale"]
+            st[1] = self._host["_growth_tracker"]
+            st[3] = self._host.get("skipped", 0)
+            self._state = st.to(device)
+            self._scale_t = self._state[:1].view(torch.float32)[0]
+        return self._state
+
+    def _pull(self):
+        """Device state -> host copy (syncs)."""
+        if self._state is not None:
+            st = self._state.cpu()
+            self._host = {"scale": float(st[:1].view(torch.float32)[0]), "_growth_tracker": int(st[1]), "skipped": int(st[3])}
+        return self._host
+
+    def _device_step(self):
+        return int(self._state[2].item())
+
+    def _set_device_step(self, step):
+        self._state[2:3].fill_(int(step))
+
+    def scale(self, loss):
+        if not self._enabled:
+            return loss
+        self._device_state(loss.device)
+        return loss * self._scale_t
+
+    def step(self, optimizer):
+        if not isinstance(optimizer, FusedClipAdamWWD):
+            raise TypeError(f"DeviceLossScaler.step needs a FusedClipAdamWWD (the scaler lives in its fused tail), got "
+                            f"{type(optimizer).__name__}")
+        if not self._enabled:
+            return optimizer.step()
+        return optimizer.step(loss_scaler=self)
+
+    def update(self):
+        """Nothing to do: the scale was updated (and clamped) on the device inside step().  Kept so that the loop keeps
+        train.py's shape."""
+
+    def get_scale(self):
+        """The current scale as a float (syncs; logging only)."""
+        return self._pull()["scale"] if self._enabled else 1.0
+
+    def skipped_steps(self):
+        """Steps skipped so far because a gradient was not finite (syncs; logging only)."""
+        return self._pull().get("skipped", 0) if self._enabled else 0
+
+    def state_dict(self):
+        if not self._enabled:
+            return {}
+        h = self._pull()
+        return {"scale": h["scale"], "growth_factor": self._growth_factor, "backoff_factor": self._backoff_factor,
+                "growth_interval": self._growth_interval, "_growth_tracker": h["_growth_tracker"]}
+
+    def load_state_dict(self, state_dict):
+        if not self._enabled:
+            return
+        if len(state_dict) == 0:
+            raise RuntimeError("The source state dict is empty, possibly because it was saved from a disabled scaler.")
+        self._growth_factor, self._backoff_factor = float(state_dict["growth_factor"]), float(state_dict["backoff_factor"])
+        self._growth_interval = int(state_dict["growth_interval"])
+        self._host = {"scale": float(state_dict["scale"]), "_growth_tracker": int(state_dict["_growth_tracker"]),
+                      "skipped": self._pull().get("skipped", 0)}
+        if self._state is not None:
+            st = torch.zeros(2, dtype=torch.int32)
+            st[:1].view(torch.float32)[0] = self._host["scale"]
+            st[1] = self._host["_growth_tracker"]
+            self._state[:2].copy_(st)

@@ -12,7 +12,7 @@ DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 EPI_NONE, EPI_RES, EPI_GELU, EPI_POS, EPI_DGELU, EPI_TANH, EPI_DTANH = range(7)
 EPI_RES_DROP, EPI_GELU_DROP = 7, 8      # rgbnm_gemm_nt_drop only
 
-_vp, _i, _f, _sz, _ll = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_longlong
+_vp, _i, _f, _sz, _ll, _d = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_longlong, C.c_double
 # seconds the host spent blocked on the pinned-slot rings of the per-step records (augment parameters, mixup lambda): the host runs
 # up to 16 steps ahead of the GPU and waits HERE; a value near zero over a timed loop means the host, not the GPU, paces the loop
 HOST_WAIT = {"sec": 0.0}
@@ -131,6 +131,9 @@ PROTOTYPES = {
     "rgbnm_mixup_target": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "rgbnm_clip_adamw_wd_workspace": (_sz, []),
     "rgbnm_clip_adamw_wd_step": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _i, _f, _f, _vp, _vp, _sz, _vp]),
+    "rgbnm_clip_adamw_wd_scaled_workspace": (_sz, []),
+    "rgbnm_clip_adamw_wd_step_scaled": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _f, _f, _vp, _vp, _d, _d, _i, _f, _f,
+                                             _vp, _sz, _vp]),
     "rgbnm_vit_workspace": (_sz, [_P(VitCfg)]),
     "rgbnm_vit_workspace_ex": (_sz, [_P(VitCfg), _i]),
     "rgbnm_head_bwd_workspace": (_sz, [_vp, _i]),
