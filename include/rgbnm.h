@@ -159,11 +159,17 @@ int rgbnm_gemm_tn_group_end(void* stream);
  * dW / db hold nothing, until _end returns. */
 void rgbnm_gemm_tn_group_begin_n(int max_jobs);
 /* Brackets nest by joining: a _begin inside an open bracket (also the ones rgbnm_head_bwd / rgbnm_vit_block_bwd open internally)
- * only counts, its _end neither launches nor closes anything; the jobs run at the OUTERMOST _end.  A _begin on a thread whose queue
- * still holds jobs of a pass that died before its _end starts from an empty queue (those jobs are dropped, never launched).
- * _begin_id names the bracket (id != 0): rgbnm_gemm_tn_group_abort(id), callable from ANY host thread, makes the thread that owns
- * the bracket drop its queue without launching, the next time it touches it -- for callers whose backward nodes run on an autograd
- * worker thread while the pass is found abandoned on another one (swinv2.py).  Reference: none (torch launches every GEMM at once). */
+ * only counts, its _end neither launches nor closes anything; the jobs run at the OUTERMOST _end.  The library cannot tell a bracket
+ * whose pass died before its _end from one that is still open -- the next _begin on that thread would join it, and neither pass's
+ * jobs would run at that _begin's _end --, so an UNNAMED bracket (_begin, _begin_n) must be closed by the thread that opened it, on
+ * every path.  A pass that can die before its _end takes a NAMED bracket and _abort:
+ * _begin_id names the bracket (id != 0; only an outermost one: inside an open bracket it joins like _begin_n and the open bracket
+ * keeps its name or its lack of one): rgbnm_gemm_tn_group_abort(id), callable from ANY host thread, makes the thread that owns
+ * the bracket drop its queue without launching and close the bracket -- at once when called on the owning thread, else the next
+ * time the owner touches its queue -- for callers whose backward nodes run on an autograd worker thread while the pass is found
+ * abandoned on another one (swinv2.py).  _abort of 0 does nothing; _abort of an id that names no open bracket changes nothing for
+ * the brackets that are open (it waits for a bracket of that name: ids are one per pass, never reused for a live one).
+ * Reference: none (torch launches every GEMM at once). */
 void rgbnm_gemm_tn_group_begin_id(int max_jobs, unsigned long long id);
 void rgbnm_gemm_tn_group_abort(unsigned long long id);
 

@@ -839,7 +839,9 @@ __global__ __launch_bounds__(256) void prep_weights_kernel(const rgbnm_linear_de
         const int r = r0 + ty + 8 * k, c = c0 + tx;
         float v = 0.f;
         if (t < tr * tc && r < d.N && c < d.K) {
-          v = vv[u][k] + ((d.add_identity && r == c) ? 1.0f : 0.0f);
+          v = vv[u][k];
+          if (d.add_identity && r == c) v += 1.0f;               // (not `+ (diagonal ? 1.0f : 0.0f)`: -0.0f + 0.0f is +0.0f, and a
+                                                                 // master's -0 must reach the shadows as torch's cast gives it)
           if (!shadows) {
           } else if (d.pair) {                                   // diag(W, W): row pitch 2K, second copy at (N, K)
             shadow[d.ws_off + (size_t)r * (2 * d.K) + c] = from_f32<T>(v);
@@ -912,13 +914,14 @@ __global__ __launch_bounds__(256) void prep_weights_kernel(const rgbnm_linear_de
 
 // Brackets nest by JOINING: a begin inside an open bracket (rgbnm_head_bwd or rgbnm_vit_block_bwd called by somebody who has
 // opened rgbnm_gemm_tn_group_begin_n) only counts, and its flush neither launches nor closes anything -- the jobs wait for the
-// outer end (the inner flush used to close the caller's bracket silently).  A begin on a thread whose queue still holds
-// jobs starts from an EMPTY queue: they are leftovers of a pass that died between begin and end, their operands may be gone.
+// outer end (the inner flush used to close the caller's bracket silently).  A bracket whose pass died between begin and
+// end looks exactly like an open one: the next begin on that thread JOINS it (tests/test_tn_bracket.py pins this), so an unnamed
+// bracket must be closed by its opener and a pass that can die takes a named one and rgbnm_gemm_tn_group_abort.  Whatever clears
+// g_tn_defer (the outermost flush, both abort paths) also leaves g_tn_n, g_tn_tiles, g_tn_depth and g_tn_id at zero: nothing to
+// reset here.
 void rgbnm_tn_defer_begin_n(int max_jobs) {
   tn_check_abort();
   if (g_tn_defer) { ++g_tn_depth; return; }
-  g_tn_n = g_tn_tiles = g_tn_depth = 0;
-  g_tn_id = 0;
   g_tn_defer = true;
   g_tn_cap = max_jobs < 1 ? 1 : (max_jobs > TN_QMAX ? TN_QMAX : max_jobs);
 }

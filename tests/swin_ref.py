@@ -1,5 +1,6 @@
-"""fp64 reference and launch geometry of the SwinV2 window attention (csrc/swin_attn.hip), shared by tests/test_swin_edges.py
-(GPU) and tests/test_swin_edges_cpu.py.  A plain module, imported by name from the tests (not a conftest.py).
+"""fp64 reference and launch geometry of the SwinV2 window attention (csrc/swin_attn.hip) and fp64 reference, derived bound and
+fp32 emulation of the sub-block embedding (csrc/swin.hip), shared by tests/test_swin_edges.py (GPU) and
+tests/test_swin_edges_cpu.py.  A plain module, imported by name from the tests (not a conftest.py).
 
 - partition(x, B, res, shift): token-major [B res^2, X] -> windows [B nW, 64, X] with torch.roll and reshapes (the layout of
   oracle/swin_torch.window_attention; nothing here shares index code with the kernel).  Window w = (image, window row, window
@@ -214,3 +215,79 @@ def win_bwd(L, v, dO, O_k, lse_k, uT, uP, eta=0.0):
     mdv = P.transpose(-1, -2) @ dO.abs()
     r["E_dv"] = (P * e).transpose(-1, -2) @ dO.abs() + (uP + 64 * U) * mdv + eta * dO.abs().sum(-2, keepdim=True)
     return r
+
+
+# ------------------------------------------------------------------------------------------------------------- embedding
+# rgbnm_swin_embed (csrc/swin.hip swin_embed_kernel): every 8 x 8 DCT block X becomes A^T X A, split into 2 x 2 sub-blocks of
+# 4 x 4 coefficients (luma) or 4 x 4 sub-blocks of 2 x 2 (chroma); token (2 Hb, 2 Wb) grid, 16 + 2 x 4 features per token.
+EMBED_CASES = [(1, 2, 2), (1, 2, 6), (1, 6, 2), (3, 6, 10), (2, 4, 14)]       # (B, Hb, Wb)
+EMBED_BLOCKS_PER_WG = 4
+# The bound's c (in units of u = 2^-24), derived, not fitted.  The kernel takes t[r][c] = sum_k A[k][r] X[k][c] and then
+# v[r][c] = sum_k t[r][k] A[k][c] as two sequential 8-term fp32 dot products (fma or multiply + add: each term meets at most 8
+# roundings), so with g8 = 8u / (1 - 8u) (Higham, Accuracy and Stability, Lemma 3.1 / eq. 3.5):
+#   |t^ - t| <= g8 (|A|^T |X|),    |v^ - sum_k t^ A| <= g8 (|t^| |A|) <= g8 (1 + g8) mag,    mag = |A|^T |X| |A|
+#   |v^ - v| <= g8 mag + g8 (1 + g8) mag = (2 g8 + g8^2) mag = 16.0000114 u mag.
+# The input is widened to fp32 exactly and A is the caller's fp32 matrix, so nothing else rounds before the store; the store
+# rounds v^ to the output type: at most half an ulp of v^, which is at most one ulp_TO of the reference.
+_G8 = 8 * U / (1 - 8 * U)
+EMBED_C = (2 * _G8 + _G8 * _G8) / U
+
+
+def embed_blocks(B, Hb, Wb):
+    """(luma blocks, chroma blocks) of one call: the kernel numbers them luma first and gives a workgroup 4."""
+    return B * Hb * Wb, B * 2 * (Hb // 2) * (Wb // 2)
+
+
+def embed_matrices(dtype=torch.float64):
+    """(A_luma, A_chroma): the conversion matrices the model hands the kernel (oracle/swin_torch._conv)."""
+    return ST._conv(4, 2, dtype), ST._conv(2, 4, dtype)
+
+
+def embed_inputs(B, Hb, Wb, seed):
+    """The committed inputs of a case: detfill.normalish luma [B, 1, Hb, Wb, 8, 8] and chroma [B, 2, Hb/2, Wb/2, 8, 8], fp32."""
+    from rgb_no_more_amd import detfill
+    y = torch.from_numpy(detfill.normalish((B, 1, Hb, Wb, 8, 8), seed))
+    c = torch.from_numpy(detfill.normalish((B, 2, Hb // 2, Wb // 2, 8, 8), seed + 1))
+    return y, c
+
+
+def embed_ref(y, cbcr, Ay, Ac):
+    """fp64 reference and forward-error magnitude of the embedding, [B, 2 Hb, 2 Wb, 24] each: A^T X A per block and
+    |A|^T |X| |A|, then the header's einops split -- rows '(p1 pdh)', columns '(p2 pdw)', coefficient-major -- written as one
+    einops pattern; nothing here shares index arithmetic with the kernel.  y, cbcr: any float dtype (their values, in fp64);
+    Ay, Ac: the fp32 / fp64 matrices the kernel is given."""
+    import einops
+    out = []
+    for x, A, sub in ((y, Ay, 2), (cbcr, Ac, 4)):
+        x64, A64 = x.double(), A.double()
+        both = []
+        for t in (A64.T @ x64 @ A64, A64.abs().T @ x64.abs() @ A64.abs()):
+            both.append(einops.rearrange(t, "b c h w (p1 pdh) (p2 pdw) -> b (h pdh) (w pdw) (c p1 p2)", pdh=sub, pdw=sub))
+        out.append(both)
+    (fy, my), (fc, mc) = out
+    return torch.cat([fy, fc], dim=3), torch.cat([my, mc], dim=3)
+
+
+def embed_emulate(y, cbcr, Ay, Ac, fma=True):
+    """The kernel's arithmetic on the CPU: fp32 inputs (already widened), two sequential 8-term fp32 dot products per element in
+    the kernel's order, k ascending, from t = 0.  fma: one rounding per term (the product of two fp32 is exact in fp64); else
+    the product is rounded to fp32 first.  Returns fp32 [B, 2 Hb, 2 Wb, 24] (laid out by embed_ref's einops pattern)."""
+    import einops
+    f32, f64 = torch.float32, torch.float64
+
+    def term(a, b, acc):
+        p = a.to(f64) * b.to(f64)
+        if not fma:
+            p = p.to(f32).to(f64)
+        return (p + acc.to(f64)).to(f32)
+    out = []
+    for x, A, sub in ((y, Ay, 2), (cbcr, Ac, 4)):
+        x, A = x.to(f32), A.to(f32)
+        t = torch.zeros_like(x)
+        for k in range(8):                                   # t[r][c] += A[k][r] X[k][c]
+            t = term(A[k, :, None], x[..., k, None, :], t)
+        v = torch.zeros_like(x)
+        for k in range(8):                                   # v[r][c] += t[r][k] A[k][c]
+            v = term(t[..., :, k, None], A[k, None, :], v)
+        out.append(einops.rearrange(v, "b c h w (p1 pdh) (p2 pdw) -> b (h pdh) (w pdw) (c p1 p2)", pdh=sub, pdw=sub))
+    return torch.cat(out, dim=3)

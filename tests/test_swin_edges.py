@@ -1,5 +1,6 @@
 """Element-wise edge tests of SwinV2's own kernels (tests/kernel_check.py): window attention forward / backward, the
-lanes-per-row LayerNorm past its grid caps, the continuous position bias at model block counts, merge gather and token mean.
+lanes-per-row LayerNorm past its grid caps, the continuous position bias at model block counts, merge gather, token mean and
+the sub-block embedding.
 
 Every case writes into canary-filled guarded outputs, reads inputs whose trailing rows are NaN, gets a workspace of exactly the
 size its *_workspace() entry returns (checked for margin writes only), asserts the device kernel it was meant to reach, and is
@@ -27,6 +28,11 @@ grid whose waves walk >= 3 windows with a ragged last range, (d) the XCD-aware s
 Position bias: table t = relu(coords W1^T + b1) W2^T: 18 u |W2| (|coords||W1|^T + |b1|) (two fma, a 512-term fp32 dot
 product); bias = 16 sigmoid(t): 16 s(1-s) E_t + 4 u bias; d table: 16 s(1-s) 64 u sum|dbias| + |sum dbias| 16 |s(1-s)(1-2s)| E_t
 + 4 u |dt|; dW2 / db1 / dW1 sums over the 225 entries: E_dt through the sums + 40 u of the sums' magnitudes.
+
+Embedding (rgbnm_swin_embed): A^T X A per 8 x 8 block as two sequential 8-term fp32 dot products, then the einops split into
+sub-block tokens: ulp_TO(ref) + EMBED_C u |A|^T |X| |A| with EMBED_C = 2 g8 + g8^2 = 16.0000114 DERIVED in tests/swin_ref.py, not
+fitted; all nine in / out type pairs at grids with Hb != Wb, NaN behind both inputs, single-coefficient probes for luma and each
+chroma channel.  Worst ratio on one MI355X: 0.201 into fp32, 0.500 / 0.499 into bf16 / fp16; the eleven tests take 2 s.
 """
 import math
 
@@ -480,3 +486,71 @@ def test_token_mean_paths(dt):
         ref = (dy.double() / N)[:, None, :].expand(B, N, C).reshape(B * N, C)
         worst("bwd", check_bound(dx.t, ref, ref.abs(), dt, 1, N * U, where + " dx (row, column)"))
     worst.report(f"token_mean {NAMES[dt]}")
+
+
+# ------------------------------------------------------------------------------------------------------------- embedding
+EMBED_MARKS = {"float": F32, "f": F32, "__bf16": BF16, "DF16b": BF16, "_Float16": F16, "DF16_": F16}
+
+
+def embed_instantiation(names):
+    """(TI, TO) of the one swin_embed_kernel a call dispatched, from the demangled or the mangled name."""
+    import re
+    hits = [n for n in names if "swin_embed_kernel" in n]
+    assert len(hits) == 1 and len(names) == 1, sorted(set(names))
+    m = (re.search(r"swin_embed_kernel<\s*([\w ]+?)\s*,\s*([\w ]+?)\s*>", hits[0])
+         or re.search(r"swin_embed_kernelI(f|DF16b|DF16_)(f|DF16b|DF16_)E", hits[0]))
+    assert m, hits[0]
+    return EMBED_MARKS[m.group(1)], EMBED_MARKS[m.group(2)]
+
+
+def embed_call(y, c, Ay, Ac, to, B, Hb, Wb, where):
+    """One launch on inputs with NaN behind them, into a guarded [B 2Hb 2Wb, 24] output."""
+    yb = nan_padded(y.reshape(-1, 64), None, 7)
+    cb = nan_padded(c.reshape(-1, 64), None, 7)
+    out = guarded(B * 4 * Hb * Wb, 24, to)
+    rc, names = launched(lambda: L.lib().rgbnm_swin_embed(L.dt_of(y.dtype), L.dt_of(to), yb.data_ptr(), cb.data_ptr(),
+                                                          Ay.data_ptr(), Ac.data_ptr(), out.t.data_ptr(), B, Hb, Wb, L.stream()))
+    L.check(rc, where)
+    assert embed_instantiation(names) == (y.dtype, to), (where, names)
+    out.check(where)                                       # margins intact, every (token, feature) element written
+    return out.t.reshape(B, 2 * Hb, 2 * Wb, 24)
+
+
+@pytest.mark.parametrize("to", DTS3, ids=lambda t: "out-" + NAMES[t])
+@pytest.mark.parametrize("ti", DTS3, ids=lambda t: "in-" + NAMES[t])
+def test_swin_embed_edges(ti, to):
+    """swin_embed_kernel, all nine in / out type pairs, at grids with Hb != Wb (the token arithmetic takes H and W apart, for luma
+    and for chroma) and block counts that fill the last workgroup (4 blocks each) and leave it half empty: every element within
+    ulp_TO(ref) + EMBED_C u mag of the fp64 result of the TI-rounded inputs (swin_ref.py derives EMBED_C = 16.0000114).
+    Worst ratio measured on one MI355X: 0.201 into fp32 (0.173 / 0.185 / 0.201 from fp32 / bf16 / fp16), 0.500 into bf16 and
+    0.499 into fp16 (the store's half ulp); the eleven embedding tests take 2 s."""
+    worst = KC.Worst()
+    Ay, Ac = (a.float().to(DEV) for a in R.embed_matrices())
+    for i, (B, Hb, Wb) in enumerate(R.EMBED_CASES):
+        y, c = (t.to(DEV).to(ti) for t in R.embed_inputs(B, Hb, Wb, 50 + 2 * i))
+        where = f"swin_embed {NAMES[ti]}->{NAMES[to]} B={B} Hb={Hb} Wb={Wb}"
+        got = embed_call(y, c, Ay, Ac, to, B, Hb, Wb, where)
+        ref, mag = R.embed_ref(y, c, Ay, Ac)
+        worst(f"{NAMES[ti]}->{NAMES[to]}", check_bound(got, ref, mag, to, 1, R.EMBED_C * U, where))
+    worst.report("swin_embed")
+
+
+@pytest.mark.parametrize("B,Hb,Wb", [(1, 2, 6), (2, 6, 2)])
+def test_swin_embed_single_coefficient_probes(B, Hb, Wb):
+    """One non-zero coefficient in one block, luma and each chroma channel, on non-square grids: it reaches exactly the tokens and
+    features the einops split dictates -- the non-zero pattern is the reference's -- and nothing else is non-zero."""
+    Ay, Ac = (a.float().to(DEV) for a in R.embed_matrices())
+    b = B - 1
+    probes = [("luma", 0, (b, 0, Hb - 1, Wb - 2, 3, 5)), ("luma-dc", 0, (b, 0, 1, 0, 0, 0)),
+              ("cb", 1, (b, 0, Hb // 2 - 1, Wb // 2 - 1, 5, 2)), ("cr", 1, (b, 1, 0, Wb // 2 - 1, 6, 7))]
+    for name, which, at in probes:
+        y = torch.zeros(B, 1, Hb, Wb, 8, 8, device=DEV)
+        c = torch.zeros(B, 2, Hb // 2, Wb // 2, 8, 8, device=DEV)
+        (y, c)[which][at] = 1.0
+        where = f"swin_embed probe {name} B={B} Hb={Hb} Wb={Wb} at {at}"
+        got = embed_call(y, c, Ay, Ac, F32, B, Hb, Wb, where)
+        ref, mag = R.embed_ref(y, c, Ay, Ac)
+        sub = 2 if which == 0 else 4
+        assert int((ref != 0).sum()) == 64 and int((ref != 0).any(-1).sum()) == sub * sub, where       # (the probe's own reach)
+        assert torch.equal(got != 0, ref != 0), f"{where}: non-zero pattern differs from the einops split's"
+        check_bound(got, ref, mag, F32, 1, R.EMBED_C * U, where)

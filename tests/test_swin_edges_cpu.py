@@ -4,7 +4,9 @@
 - the Python copy of head_grid() reproduces rgbnm_window_attention_bwd_workspace at 256 CUs for every case of the GPU list, and
   that list reaches every launch class at 256 CUs;
 - the element-wise bound accepts the reference rounded to T and rejects defects that the norm-wise bars of tests/test_swin.py
-  let through.
+  let through;
+- the embedding's reference equals the oracle in fp64, its derived bound accepts an fp32 emulation in the kernel's order and
+  rejects layout defects, and the case list reaches both tails a 4-block workgroup can have.
 """
 import math
 
@@ -207,3 +209,82 @@ def test_bound_accepts_rounded_reference_and_rejects_defects():
     assert float((bad - ref).norm() / ref.norm()) < 3e-2
     with pytest.raises(AssertionError, match="out of bound"):
         check_bound(bad.float(), ref, Eb, torch.float32, 1, c["dbias"], "dbias without the slice of wave 5")
+
+
+# ------------------------------------------------------------------------------------------------------------- embedding
+def test_embed_reference_is_the_oracle_in_fp64():
+    """swin_ref.embed_ref (one einops pattern) equals oracle/swin_torch.decompose_features in fp64, bit for bit, on every case."""
+    Ay, Ac = R.embed_matrices()
+    for i, (B, Hb, Wb) in enumerate(R.EMBED_CASES):
+        y, c = (t.double() for t in R.embed_inputs(B, Hb, Wb, 50 + 2 * i))
+        ref, mag = R.embed_ref(y, c, Ay, Ac)
+        assert ref.shape == (B, 2 * Hb, 2 * Wb, 24)
+        assert torch.equal(ref, ST.decompose_features(y, c)), (B, Hb, Wb)
+        assert bool((mag >= ref.abs()).all())
+
+
+def test_embed_cases_and_the_workgroup_tail():
+    """A workgroup takes 4 blocks, luma first.  With Hb and Wb even -- odd ones are refused -- a call has 4m luma and 2m chroma
+    blocks: the luma / chroma boundary always falls between workgroups and the last workgroup is either full or holds two
+    blocks; remainders 1 and 3 cannot occur.  The cases reach both, with Hb < Wb, Hb > Wb and Hb = Wb, B = 1 and B > 1."""
+    rem = set()
+    for B, Hb, Wb in R.EMBED_CASES:
+        ny, nc = R.embed_blocks(B, Hb, Wb)
+        assert ny % R.EMBED_BLOCKS_PER_WG == 0 and nc * 2 == ny
+        rem.add((ny + nc) % R.EMBED_BLOCKS_PER_WG)
+    assert rem == {0, 2}
+    assert all((6 * m) % 4 in (0, 2) for m in range(1, 100))
+    assert {(Hb > Wb) - (Hb < Wb) for _, Hb, Wb in R.EMBED_CASES} == {-1, 0, 1}
+    assert {B > 1 for B, _, _ in R.EMBED_CASES} == {False, True}
+    assert R.EMBED_CASES == [(1, 2, 2), (1, 2, 6), (1, 6, 2), (3, 6, 10), (2, 4, 14)]
+
+
+@pytest.mark.parametrize("ti", [torch.float32, torch.bfloat16, torch.float16])
+def test_embed_bound_accepts_the_kernels_arithmetic_and_rejects_defects(ti):
+    """An fp32 emulation in the kernel's order (fma and multiply + add) passes ulp_TO(ref) + EMBED_C u mag on the committed inputs
+    for every output type; H for W in the token pitch, sub-block row and column exchanged, the sub-block-major split and a store two ulps off do not
+    (the bound's one ulp_TO admits any rounding direction of the store: the bits of that rounding are pinned by
+    tests/test_swin_fp16_kernels.py)."""
+    assert 16 < R.EMBED_C < 16.00002
+    Ay, Ac = (a.float() for a in R.embed_matrices())
+    for i, (B, Hb, Wb) in enumerate(R.EMBED_CASES):
+        y, c = (t.to(ti) for t in R.embed_inputs(B, Hb, Wb, 50 + 2 * i))
+        ref, mag = R.embed_ref(y, c, Ay, Ac)
+        for fma in (True, False):
+            emu = R.embed_emulate(y.float(), c.float(), Ay, Ac, fma)
+            for to in (torch.float32, torch.bfloat16, torch.float16):
+                assert check_bound(emu.to(to), ref, mag, to, 1, R.EMBED_C * U, f"emulation fma={fma}", verbose=False) <= 1.0
+        emu = R.embed_emulate(y.float(), c.float(), Ay, Ac)
+        if Hb < Wb:                                          # token pitch 2 Hb instead of 2 Wb: rows overlap, the tail is never written
+            flat = torch.full((B * 4 * Hb * Wb, 24), float("nan"))
+            i, j = torch.meshgrid(torch.arange(B * 2 * Hb), torch.arange(2 * Wb), indexing="ij")
+            flat[(i * 2 * Hb + j).reshape(-1)] = emu.reshape(-1, 24)
+            with pytest.raises(AssertionError):
+                check_bound(flat.reshape(ref.shape), ref, mag, torch.float32, 1, R.EMBED_C * U, "token pitch")
+        swapped = emu.clone()                                # sub-block row and column exchanged in the token arithmetic
+        swapped[..., :16] = emu[..., :16].reshape(B, Hb, 2, Wb, 2, 16).transpose(2, 4).reshape(B, 2 * Hb, 2 * Wb, 16)
+        with pytest.raises(AssertionError):
+            check_bound(swapped, ref, mag, torch.float32, 1, R.EMBED_C * U, "pdh / pdw exchanged")
+        wrong = emu.clone()                                  # luma rows split '(pdh p1)' instead of '(p1 pdh)'
+        ty = (Ay.double().T @ y.double() @ Ay.double()).float()
+        wrong[..., :16] = ty.reshape(B, 1, Hb, Wb, 2, 4, 2, 4).permute(0, 2, 4, 3, 6, 1, 5, 7).reshape(B, 2 * Hb, 2 * Wb, 16)
+        with pytest.raises(AssertionError):
+            check_bound(wrong, ref, mag, torch.float32, 1, R.EMBED_C * U, "sub-block-major")
+        off = (emu.double() + 2 * KC.ulp(ref, torch.bfloat16)).to(torch.bfloat16)             # two bf16 ulps off
+        with pytest.raises(AssertionError):
+            check_bound(off, ref, mag, torch.bfloat16, 1, R.EMBED_C * U, "two ulps")
+
+
+def test_embed_refusals_return_before_any_device_call():
+    lib = L.lib()
+
+    def call(B=2, Hb=4, Wb=6, ti=0, to=0, **kw):
+        p = dict(y=0x1000, c=0x2000, ay=0x3000, ac=0x4000, out=0x5000)
+        p.update(kw)
+        return lib.rgbnm_swin_embed(ti, to, p["y"], p["c"], p["ay"], p["ac"], p["out"], B, Hb, Wb, None)
+    for Hb, Wb in ((3, 4), (4, 3), (5, 7), (1, 2), (2, 1)):
+        assert call(Hb=Hb, Wb=Wb) == EINVAL, (Hb, Wb)
+    for B in (0, -1):
+        assert call(B=B) == EINVAL, B
+    for k in ("y", "c", "ay", "ac", "out"):
+        assert call(**{k: None}) == EINVAL, k
