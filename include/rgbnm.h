@@ -24,7 +24,8 @@
  *     arithmetic / dGELU), the pipelined and wide weight-gradient kernels, and the rgbnm_gemm_tn_group_* brackets (a queue holds
  *     jobs of one dtype: a job of another dtype runs what is queued first).  The other bf16-tuned kernels (one-launch chains,
  *     fused MLP, attention v2, LayerNorm-chained row-panel epilogues, the bf16 GELU table) are bf16 only and are skipped for
- *     fp16 whatever the option says.  Everything else (the augment stage, rgbnm_mixup) takes fp32 / bf16 only.
+ *     fp16 whatever the option says.  The data stage has fp16 through entries of its own: rgbnm_dct_augment_chain writes it
+ *     (RGBNM_AUG_OUT_F16) and rgbnm_mixup_any mixes to it; the three rgbnm_dct_augment* entries and rgbnm_mixup keep to fp32 / bf16.
  *   - tensors are dense row-major; "ld*" are row strides in elements.
  */
 #ifndef RGBNM_H
@@ -40,7 +41,8 @@ extern "C" {
 #define RGBNM_DT_F32 0
 #define RGBNM_DT_BF16 1
 #define RGBNM_DT_F16 2   /* see the list of entries above */
-#define RGBNM_DT_I16 2   /* only as out_dtype of rgbnm_dct_augment[_ex] (which has no fp16 output) */
+#define RGBNM_DT_I16 2   /* only as out_dtype of rgbnm_dct_augment[_ex / _packed]; their fp16 output is rgbnm_dct_augment_chain's
+                            RGBNM_AUG_OUT_F16, a code of its own because 2 is taken here */
 
 /* epilogues of rgbnm_gemm_nt */
 #define RGBNM_EPI_NONE 0   /* C = A.W^T (+bias)                                         */
@@ -246,7 +248,7 @@ int rgbnm_subblock_embed(int in_dtype, int out_dtype, const void* y, const void*
  * floats, may be NULL = no mixing) mixes image b with image b - 1 (mod B) as the values are loaded:
  *   x[b] <- round_in_dtype( fma(x[b - 1], lam[1], x[b] * lam[0]) )       (fp32 product, fp32 fma, ONE rounding to in_dtype)
  * for every in_dtype the entry accepts, fp16 included.  For fp32 and bf16 input that is what rgbnm_mixup(in_dtype -> in_dtype)
- * stores (rgbnm_mixup itself does not take fp16): the same bits as rgbnm_mixup followed by rgbnm_subblock_embed without the mixed
+ * stores (fp16: rgbnm_mixup_any): the same bits as rgbnm_mixup followed by rgbnm_subblock_embed without the mixed
  * batch ever existing in memory (two launches and a round trip of the batch less per step). */
 int rgbnm_subblock_embed_mix(int in_dtype, int out_dtype, const void* y, const void* cbcr, const float* lam_dev, const float* conv16,
                              void* feat, int B, int Hb, int Wb, int transpose_a, void* stream);
@@ -331,6 +333,33 @@ int rgbnm_dct_augment_packed(const int16_t* Ypacked, const int16_t* Cpacked, con
                              int Hy, int Wy, int Hc, int Wc, int entry_clamp, int nops, void* workspace, size_t workspace_bytes,
                              void* stream);
 
+/* The same two kernels behind one entry that also writes fp16 and takes RandAugment chains of more than two ops
+ * (train.py --ampdtype float16, --num_ops N).
+ * y_off / c_off both NULL: Y / C are the whole grids, as rgbnm_dct_augment_ex; both set: the host-cropped buffers of
+ * rgbnm_dct_augment_packed.  ops_dev / ops_host both NULL: the ops are the two slots of the parameters and nops is 0..2; both set:
+ * [B][nops] records (device and host copy, like the parameters), image b's chain at ops[b * nops], nops 0..RGBNM_AUG_MAX_OPS, and
+ * the op / fmag / iarg* fields of the parameters are ignored (pad a shorter chain with RGBNM_OP_IDENTITY).
+ * out_code: RGBNM_AUG_OUT_*.  F16 is ToRange in fp32 as for the other types, rounded once to IEEE half (nearest even): the bits
+ * of torch's .half() of the fp32 output.  Kernel 2 is one launch per batch whatever nops is; the clamp rules are unchanged (entry
+ * clamp in kernel 1's store, one full pass after the FIRST op of an image that entered unclamped, none for later ops: every op
+ * clamps what it writes).  For out_code 0 / 1 / 2 and nops <= 2 the output is bit-identical to rgbnm_dct_augment_ex / _packed,
+ * with the ops from the parameters or from an array holding the same ops.
+ * Crop boxes, entry_clamp, filters, workspace (rgbnm_dct_augment_workspace_ex) and the validation are those of the entries
+ * above; also refused with RGBNM_EINVAL: nops < 0 or > RGBNM_AUG_MAX_OPS, nops > 2 without an ops array, only one of ops_dev /
+ * ops_host (or of y_off / c_off), out_code outside 0..3, an op id outside 0..19 or MIDFREQAUG / SHARPNESS with filters == NULL in
+ * any of the nops slots. */
+#define RGBNM_AUG_MAX_OPS 8
+#define RGBNM_AUG_OUT_F32 0
+#define RGBNM_AUG_OUT_BF16 1
+#define RGBNM_AUG_OUT_I16 2
+#define RGBNM_AUG_OUT_F16 3
+typedef struct rgbnm_aug_op { int op; float fmag; int iarg0, iarg1, iarg2; } rgbnm_aug_op;   /* 20 bytes; fields as in rgbnm_aug_params */
+int rgbnm_dct_augment_chain(const int16_t* Y, const int16_t* C, const long long* y_off, const long long* c_off,
+                            const int16_t* quant, const rgbnm_aug_params* params_dev, const rgbnm_aug_params* params_host,
+                            const rgbnm_aug_op* ops_dev, const rgbnm_aug_op* ops_host, const float* conv16,
+                            const float* filters, void* outY, void* outC, int out_code, int size, int B, int Hy, int Wy,
+                            int Hc, int Wc, int entry_clamp, int nops, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Train-step tail
  * ------------------------------------------------------------------------------------------- */
@@ -364,6 +393,11 @@ int rgbnm_softxent_grad_mix(int dl_dtype, const float* logits, const long long* 
 /* RandomMixup_DCT (cls_transforms.py:163-176): out[b] = lam[0]*in[b] + lam[1]*in[b-1]; lam on device. */
 int rgbnm_mixup(int in_dtype, int out_dtype, const void* in, void* out, const float* lam_dev, int B,
                 long long per_sample, void* stream);
+/* rgbnm_mixup's contract with fp16: fp32 -> fp32 / bf16 and bf16 -> bf16 launch rgbnm_mixup's kernels (same bits); fp32 -> fp16
+ * and fp16 -> fp16 store round_f16(fma(in[b-1], lam[1], in[b] * lam[0])) -- fp32 product, fp32 fma, ONE rounding, the expression of
+ * rgbnm_subblock_embed_mix.  Every other pair, and per_sample % 4 != 0, returns RGBNM_EINVAL. */
+int rgbnm_mixup_any(int in_dtype, int out_dtype, const void* in, void* out, const float* lam_dev, int B,
+                    long long per_sample, void* stream);
 int rgbnm_mixup_target(const long long* labels, float* target, const float* lam_dev, int B, int C, void* stream);
 /* clip_grad_norm_(max_norm) + AdamW(weight_decay=0) + WeightDecay (train.py:163-165; custom_optims.py:37-42)
  * over flat fp32 buffers of n elements (n % 256 == 0; every tensor starts on a 256-element boundary);

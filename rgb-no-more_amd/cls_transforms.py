@@ -34,8 +34,8 @@ class LazyMixed:
         t = self.tensor
         o = torch.empty_like(t) if out is None else out
         B = t.shape[0]
-        L.check(L.lib().rgbnm_mixup(L.dt_of(t.dtype), L.dt_of(o.dtype), t.data_ptr(), o.data_ptr(), self.lam.data_ptr(), B,
-                                    t.numel() // B, L.stream()), "mixup")
+        L.check(L.lib().rgbnm_mixup_any(L.dt_of(t.dtype), L.dt_of(o.dtype), t.data_ptr(), o.data_ptr(), self.lam.data_ptr(), B,
+                                        t.numel() // B, L.stream()), "mixup")
         return o
 
 
@@ -80,7 +80,7 @@ class RandomMixup_DCT(torch.nn.Module):
         if alpha <= 0:
             raise ValueError("Alpha param can't be zero.")
         self.num_classes, self.alpha, self.inplace = num_classes, alpha, inplace
-        self.out_dtype = None   # None: keep the input dtype
+        self.out_dtype = None   # None: keep the input dtype (fp32 items also mix to bfloat16 / float16, fp16 and bf16 items keep theirs)
         # lazy = True: the batch items come back as LazyMixed (un-mixed tensor + lambda) for a rgb-no-more_amd model to mix while
         # it loads them -- same bits, two launches and one round trip of the batch less per step; the target is mixed at once
         self.lazy = False
@@ -141,8 +141,8 @@ class RandomMixup_DCT(torch.nn.Module):
             if o.shape != t.shape or o.dtype != od or not o.is_contiguous():
                 raise ValueError("out tensors must match the batch items in shape and output dtype")
             B = t.shape[0]
-            L.check(L.lib().rgbnm_mixup(L.dt_of(t.dtype), L.dt_of(od), t.data_ptr(), o.data_ptr(), lam.data_ptr(), B,
-                                        t.numel() // B, L.stream()), "mixup")
+            L.check(L.lib().rgbnm_mixup_any(L.dt_of(t.dtype), L.dt_of(od), t.data_ptr(), o.data_ptr(), lam.data_ptr(), B,
+                                            t.numel() // B, L.stream()), "mixup")
             outs.append(o)
         if self.lazy_target and (out is None or out[-1] is None):
             return (outs[0] if single else tuple(outs)), LazyTarget(target, lam, self.num_classes)

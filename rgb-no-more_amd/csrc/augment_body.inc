@@ -489,8 +489,21 @@ __device__ __forceinline__ void clamp_image(short* img, int tid, int nthreads) {
   for (int i = tid; i < NROWS; i += nthreads) p[i] = clamp8(p[i]);
 }
 
-template <typename TO>
-__global__ __launch_bounds__(AUG_THREADS) void dct_randaug_kernel(short* inter, const rgbnm_aug_params* __restrict__ prm,
+// Where kernel 2 reads an image's op records from: the two slots inside its rgbnm_aug_params (the three rgbnm_dct_augment* entries),
+// or nops consecutive rgbnm_aug_op records (rgbnm_dct_augment_chain with an ops array, nops <= RGBNM_AUG_MAX_OPS).  Overloads on the
+// pointer type: the kernel's text is the same for both, and each instantiation reads its records straight from memory.
+struct OpRec { int op; float fm; int i0, i1, i2; };
+__device__ __forceinline__ const rgbnm_aug_params* image_ops(const rgbnm_aug_params* prm, int b, int) { return prm + b; }
+__device__ __forceinline__ const rgbnm_aug_op* image_ops(const rgbnm_aug_op* ops, int b, int nops) { return ops + (size_t)b * nops; }
+__device__ __forceinline__ OpRec op_rec(const rgbnm_aug_params* pp, int slot) {
+  return OpRec{pp->op[slot], pp->fmag[slot], pp->iarg0[slot], pp->iarg1[slot], pp->iarg2[slot]};
+}
+__device__ __forceinline__ OpRec op_rec(const rgbnm_aug_op* pp, int slot) {
+  return OpRec{pp[slot].op, pp[slot].fmag, pp[slot].iarg0, pp[slot].iarg1, pp[slot].iarg2};
+}
+
+template <typename TO, typename REC>
+__global__ __launch_bounds__(AUG_THREADS) void dct_randaug_kernel(short* inter, const REC* __restrict__ prm,
                                                                   const float* __restrict__ filt, TO* __restrict__ outY,
                                                                   TO* __restrict__ outC, int clamped, int nops) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -514,7 +527,7 @@ __global__ __launch_bounds__(AUG_THREADS) void dct_randaug_kernel(short* inter, 
     d.S = d.pl ? S_C : S_Y; d.base = d.pl == 0 ? 0 : NY + (d.pl - 1) * NC1;
     return d;
   };
-  const rgbnm_aug_params* pp = prm + b;   // indexed per slot straight from memory (a local copy would go to scratch)
+  const REC* pp = image_ops(prm, b, nops);   // indexed per slot straight from memory (a local copy would go to scratch)
 #ifdef AUG_PROF
   const unsigned long long pr0 = __builtin_readcyclecounter();
   unsigned long long pr1 = pr0, pr2 = pr0, pr3 = pr0;
@@ -542,9 +555,10 @@ __global__ __launch_bounds__(AUG_THREADS) void dct_randaug_kernel(short* inter, 
 #ifdef AUG_PROF
     if (slot == 1) pr2 = __builtin_readcyclecounter();
 #endif
-    const int op = pp->op[slot];
-    const float fm = pp->fmag[slot];
-    const int i0 = pp->iarg0[slot], i1 = pp->iarg1[slot], i2 = pp->iarg2[slot];
+    const OpRec rec = op_rec(pp, slot);
+    const int op = rec.op;
+    const float fm = rec.fm;
+    const int i0 = rec.i0, i1 = rec.i1, i2 = rec.i2;
     if (op == RGBNM_OP_ROTATE90 || op == RGBNM_OP_TRANSLATEX || op == RGBNM_OP_TRANSLATEY) {
       // whole-block permutations (dct_ops.py:99-130, 748-774), in place: gather every destination row into registers, barrier, store.
       // Branch-free gathers (a row past the end re-reads the last row and is not stored), so that the LDS reads of all of a
@@ -761,7 +775,7 @@ __global__ __launch_bounds__(AUG_THREADS) void dct_randaug_kernel(short* inter, 
   for (int e8 = tid * 8; e8 < NIMG; e8 += AUG_THREADS * 8) {      // NY % 8 == 0: a vector never straddles Y / CbCr
     const short8v c = *reinterpret_cast<const short8v*>(img + e8);
     TO* dst = e8 < NY ? oy + e8 : oc + (e8 - NY);
-    if constexpr (sizeof(TO) == 2 && !__is_same(TO, bf16)) {
+    if constexpr (__is_same(TO, short)) {
       // raw int16 output (out_dtype 2): the coefficients as they are, no ToRange -- what the per-transform classes of
       // custom_transforms.py hand to the next transform of a Compose chain
       *reinterpret_cast<short8v*>(dst) = c;
@@ -783,6 +797,13 @@ __global__ __launch_bounds__(AUG_THREADS) void dct_randaug_kernel(short* inter, 
 #pragma unroll
         for (int k = 0; k < 8; ++k) o[k] = (bf16)v[k >> 2][k & 3];
         *reinterpret_cast<bf16x8*>(dst) = o;
+      } else if constexpr (__is_same(TO, f16)) {
+        // the fp32 ToRange value rounded ONCE to IEEE half (round to nearest even: from_f32<f16> keeps the compiler from folding
+        // the last fma into the conversion), eight coefficients per 16-byte store like bf16
+        f16x8 o;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = from_f32<f16>(v[k >> 2][k & 3]);
+        *reinterpret_cast<f16x8*>(dst) = o;
       } else {
         store4<TO>(dst, v[0]);
         store4<TO>(dst + 4, v[1]);
@@ -793,7 +814,7 @@ __global__ __launch_bounds__(AUG_THREADS) void dct_randaug_kernel(short* inter, 
   if ((tid & 63) == 0 && b < 256) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     unsigned long long* o = g_aug_prof2 + (b * 16 + (tid >> 6)) * 8;
-    o[0] = pr0; o[1] = pr1; o[2] = pr2; o[3] = pr3; o[4] = __builtin_readcyclecounter(); o[5] = pp->op[0]; o[6] = pp->op[1];
+    o[0] = pr0; o[1] = pr1; o[2] = pr2; o[3] = pr3; o[4] = __builtin_readcyclecounter(); o[5] = op_rec(pp, 0).op; o[6] = op_rec(pp, 1).op;
   }
 #endif
 }
@@ -817,13 +838,30 @@ inline int resize_grid() {
   return g;
 }
 
+// kernel 2 for one output type and one source of the op records
+template <typename TO, typename REC>
+inline int launch_randaug(short* inter, const REC* recs, const float* filters, void* outY, void* outC, int B, int clamped, int nops,
+                          size_t smem, hipStream_t st) {
+  static DevOnce attr;
+  if (attr.need()) {
+    if (hipFuncSetAttribute((const void*)dct_randaug_kernel<TO, REC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return RGBNM_ELAUNCH;
+    attr.done();
+  }
+  hipLaunchKernelGGL((dct_randaug_kernel<TO, REC>), dim3(B), dim3(AUG_THREADS), smem, st, inter, recs, filters, (TO*)outY, (TO*)outC,
+                     clamped, nops);
+  return RGBNM_OK;
+}
+
+// out_code: RGBNM_AUG_OUT_* (0 fp32, 1 bf16, 2 raw int16, 3 fp16; the three older entries refuse 3 before they get here).
+// ops_dev / ops_host: [B][nops] rgbnm_aug_op records that replace the op fields of the parameters (rgbnm_dct_augment_chain), or null.
 inline int launch(const int16_t* Yq, const int16_t* CbCrq, const int16_t* quant, const rgbnm_aug_params* params_dev,
                   const rgbnm_aug_params* params_host, const float* conv16, const float* filters, void* outY, void* outC,
-                  int out_dtype, int B, int Hy, int Wy, int Hc, int Wc, int entry_clamp, int nops, void* workspace,
-                  size_t ws_bytes, hipStream_t st, const long long* yoff = nullptr, const long long* coff = nullptr) {
+                  int out_code, int B, int Hy, int Wy, int Hc, int Wc, int entry_clamp, int nops, void* workspace,
+                  size_t ws_bytes, hipStream_t st, const long long* yoff = nullptr, const long long* coff = nullptr,
+                  const rgbnm_aug_op* ops_dev = nullptr, const rgbnm_aug_op* ops_host = nullptr) {
   if (ws_bytes < workspace_bytes(B)) return RGBNM_EWORKSPACE;
   if ((yoff != nullptr) != (coff != nullptr)) return RGBNM_EINVAL;
-  if (out_dtype != DT_F32 && out_dtype != DT_BF16 && out_dtype != 2) return RGBNM_EINVAL;      // before kernel 1 goes out, not after it
+  if (out_code < RGBNM_AUG_OUT_F32 || out_code > RGBNM_AUG_OUT_F16) return RGBNM_EINVAL;      // before kernel 1 goes out, not after it
   // host-side validation of every crop box (the HIP path implements the x2 / identity / /2 resize cases)
   for (int b = 0; b < B; ++b) {
     const rgbnm_aug_params& p = params_host[b];
@@ -833,16 +871,17 @@ inline int launch(const int16_t* Yq, const int16_t* CbCrq, const int16_t* quant,
     if (p.crop_i + p.crop_h > Hy || p.crop_j + p.crop_w > Wy) return RGBNM_EINVAL;
     if (CbCrq && (p.crop_i / 2 + p.crop_h / 2 > Hc || p.crop_j / 2 + p.crop_w / 2 > Wc)) return RGBNM_EINVAL;
     for (int s = 0; s < nops; ++s) {
-      if (p.op[s] < 0 || p.op[s] > RGBNM_OP_EQUALIZE) return RGBNM_EINVAL;
+      const int op = ops_host ? ops_host[(size_t)b * nops + s].op : p.op[s];
+      if (op < 0 || op > RGBNM_OP_EQUALIZE) return RGBNM_EINVAL;
       // the only readers of `filters`: without a bank kernel 2 would read through the null pointer
-      if (!filters && (p.op[s] == RGBNM_OP_MIDFREQAUG || p.op[s] == RGBNM_OP_SHARPNESS)) return RGBNM_EINVAL;
+      if (!filters && (op == RGBNM_OP_MIDFREQAUG || op == RGBNM_OP_SHARPNESS)) return RGBNM_EINVAL;
     }
   }
   // algorithmic bytes of the stage (SURVEY.md 8d): the crop box in (192 w^2 B for side w: luma w^2 blocks + 2 chroma planes of
-  // (w/2)^2, 128 B each) + the quantisation tables, the S x S image out in out_dtype -- the int16 intermediate is not counted
+  // (w/2)^2, 128 B each) + the quantisation tables, the S x S image out in its output type -- the int16 intermediate is not counted
   double abytes = 0.0;
   for (int b = 0; b < B; ++b) abytes += 192.0 * params_host[b].crop_w * params_host[b].crop_w + 384.0;
-  abytes += (double)B * NIMG * (out_dtype == DT_F32 ? 4.0 : 2.0);
+  abytes += (double)B * NIMG * (out_code == RGBNM_AUG_OUT_F32 ? 4.0 : 2.0);
   const int tslot = rgbnm_trace_begin(TR_AUG, 0.0, abytes, st);
   const int grid = resize_grid();
   for (int b0 = 0; b0 < B; b0 += RESIZE_MAXB) {          // the cost prefix table of one launch covers RESIZE_MAXB images
@@ -864,33 +903,16 @@ inline int launch(const int16_t* Yq, const int16_t* CbCrq, const int16_t* quant,
   entry_clamp &= 1;
   short* inter = (short*)workspace;
   const size_t smem = (IMG_IN_LDS ? NIMG * sizeof(short) : 0) + 256 + 1024 + UNITS * 4;   // image + reduction scratch + Solarize mask + block decode table
-  if (out_dtype == DT_F32) {
-    static DevOnce attr;
-    if (attr.need()) {
-      if (hipFuncSetAttribute((const void*)dct_randaug_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return RGBNM_ELAUNCH;
-      attr.done();
-    }
-    hipLaunchKernelGGL((dct_randaug_kernel<float>), dim3(B), dim3(AUG_THREADS), smem, st, inter, params_dev, filters,
-                       (float*)outY, (float*)outC, entry_clamp, nops);
-  } else if (out_dtype == DT_BF16) {
-    static DevOnce attr;
-    if (attr.need()) {
-      if (hipFuncSetAttribute((const void*)dct_randaug_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return RGBNM_ELAUNCH;
-      attr.done();
-    }
-    hipLaunchKernelGGL((dct_randaug_kernel<bf16>), dim3(B), dim3(AUG_THREADS), smem, st, inter, params_dev, filters,
-                       (bf16*)outY, (bf16*)outC, entry_clamp, nops);
-  } else if (out_dtype == 2) {          // raw int16 coefficients (no ToRange)
-    static DevOnce attr;
-    if (attr.need()) {
-      if (hipFuncSetAttribute((const void*)dct_randaug_kernel<short>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return RGBNM_ELAUNCH;
-      attr.done();
-    }
-    hipLaunchKernelGGL((dct_randaug_kernel<short>), dim3(B), dim3(AUG_THREADS), smem, st, inter, params_dev, filters,
-                       (short*)outY, (short*)outC, entry_clamp, nops);
-  } else {
-    return RGBNM_EINVAL;
-  }
+  int rc;
+#define AUG_K2(TO)                                                                                                               \
+  (ops_dev ? launch_randaug<TO, rgbnm_aug_op>(inter, ops_dev, filters, outY, outC, B, entry_clamp, nops, smem, st)                \
+           : launch_randaug<TO, rgbnm_aug_params>(inter, params_dev, filters, outY, outC, B, entry_clamp, nops, smem, st))
+  if (out_code == RGBNM_AUG_OUT_F32) rc = AUG_K2(float);
+  else if (out_code == RGBNM_AUG_OUT_BF16) rc = AUG_K2(bf16);
+  else if (out_code == RGBNM_AUG_OUT_I16) rc = AUG_K2(short);          // raw int16 coefficients (no ToRange)
+  else rc = AUG_K2(f16);
+#undef AUG_K2
+  if (rc != RGBNM_OK) return rc;
   rgbnm_trace_end(tslot, st);
   LAUNCH_CHECK();
   return RGBNM_OK;

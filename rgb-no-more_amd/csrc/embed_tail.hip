@@ -577,6 +577,22 @@ int rgbnm_mixup(int in_dtype, int out_dtype, const void* in, void* out, const fl
   return RGBNM_OK;
 }
 
+int rgbnm_mixup_any(int in_dtype, int out_dtype, const void* in, void* out, const float* lam_dev, int B,
+                    long long per_sample, void* stream) {
+  if (out_dtype != DT_F16) return in_dtype == DT_F16 ? RGBNM_EINVAL : rgbnm_mixup(in_dtype, out_dtype, in, out, lam_dev, B, per_sample, stream);
+  if (!in || !out || !lam_dev || B <= 0 || per_sample <= 0 || (per_sample & 3)) return RGBNM_EINVAL;
+  const long long n = (long long)B * per_sample;
+  const dim3 grid((unsigned)min(4096LL, cdivl(n, 1024))), blk(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (in_dtype == DT_F32)
+    hipLaunchKernelGGL((mixup_kernel<float, f16>), grid, blk, 0, st, (const float*)in, (f16*)out, lam_dev, B, per_sample);
+  else if (in_dtype == DT_F16)
+    hipLaunchKernelGGL((mixup_kernel<f16, f16>), grid, blk, 0, st, (const f16*)in, (f16*)out, lam_dev, B, per_sample);
+  else return RGBNM_EINVAL;
+  LAUNCH_CHECK();
+  return RGBNM_OK;
+}
+
 int rgbnm_mixup_target(const long long* labels, float* target, const float* lam_dev, int B, int C, void* stream) {
   if (!labels || !target || !lam_dev || B <= 0 || C <= 0) return RGBNM_EINVAL;
   hipLaunchKernelGGL(mixup_target_kernel, dim3((unsigned)min(2048LL, cdivl((long long)B * C, 256))), dim3(256), 0,

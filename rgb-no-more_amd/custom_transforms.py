@@ -4,8 +4,9 @@ The reference composes per-sample CPU transforms inside DataLoader workers (data
     RandomResizedCrop_DCT(28, scale=(0.05,1), ratio=(1,1)) -> RandomFlip_DCT(0.5) -> RandAugment_dct(2, 3, 11, ops)
     -> ToRange(-1, 1, -1024, 1016)
 Here the same chain runs as two HIP kernels per batch (csrc/augment.hip) on the raw int16 coefficients that
-`dct_manip.read_coefficients` returns.  Random parameters are drawn on the host with the reference's distributions
-(`sample_params`, class names / argument meaning kept) or supplied explicitly (parity tests pin them).
+`dct_manip.read_coefficients` returns, for up to AUG_MAX_OPS RandAugment operations and float32 / bfloat16 / float16
+output.  Random parameters are drawn on the host with the reference's distributions (`sample_params`, class names /
+argument meaning kept) or supplied explicitly (parity tests pin them).
 
     aug = TrainTransform_DCT(size=28, ops_list=cfg.TRAIN.AUGLIST, num_ops=2, magnitude=3)
     Y, CbCr = aug(Yq, CbCrq, quant)            # (B,1,28,28,8,8), (B,2,14,14,8,8) in [-1, 1]
@@ -37,6 +38,14 @@ class AugParams(C.Structure):
     _fields_ = [("crop_i", C.c_int), ("crop_j", C.c_int), ("crop_h", C.c_int), ("crop_w", C.c_int), ("flip", C.c_int),
                 ("op", C.c_int * 2), ("fmag", C.c_float * 2), ("iarg0", C.c_int * 2), ("iarg1", C.c_int * 2),
                 ("iarg2", C.c_int * 2)]
+
+
+class AugOp(C.Structure):
+    """rgbnm_aug_op: one operation of a chain handed to rgbnm_dct_augment_chain as an array (B, nops)."""
+    _fields_ = [("op", C.c_int), ("fmag", C.c_float), ("iarg0", C.c_int), ("iarg1", C.c_int), ("iarg2", C.c_int)]
+
+
+AUG_MAX_OPS = L.AUG_MAX_OPS
 
 
 def _factors(n):
@@ -448,12 +457,12 @@ class RandAugment_dct(torch.nn.Module):
         meta = magnitude_table(self.num_magnitude_bins, (S, S))
         chosen = [list(ops)] * B if ops is not None else \
             [sample_ops(self.ops_list, self.num_ops, self.magnitude, meta, S) for _ in range(B)]
-        # the kernel chains two operations per pass (cfg.TRAIN.NUMOPS default 2); longer chains run as further passes over the int16
-        # result -- the entry clamp of a later pass is the identity on what the previous pass's per-op clamp left
+        # the kernel chains AUG_MAX_OPS operations per pass; longer chains run as further passes over the int16 result -- the entry
+        # clamp of a later pass is the identity on what the previous pass's per-op clamp left
         n = max([len(c) for c in chosen] + [1])
         if not any(o[0] in DFT_OPS for c in chosen for o in c):
-            for k in range(0, n, 2):
-                Y, C = _run_chain(Y, C, S, [_whole(Y)] * B, None, [c[k:k + 2] for c in chosen], 1, torch.int16)
+            for k in range(0, n, AUG_MAX_OPS):
+                Y, C = _run_chain(Y, C, S, [_whole(Y)] * B, None, [c[k:k + AUG_MAX_OPS] for c in chosen], 1, torch.int16)
             return _pack(Y, C, single, batched)
         # a DFT-plane op somewhere: one op per pass.  Pass k runs the kernel ops of position k (the entry clamp belongs to the first
         # pass only: the reference clamps once, custom_transforms.py:1106-1107); samples whose op k is Rotate / ShearX / ShearY sit
@@ -486,15 +495,15 @@ class ToRange(torch.nn.Module):
         super().__init__()
         self.val_min, self.val_max, self.orig_min, self.orig_max, self.dtype = val_min, val_max, orig_min, orig_max, dtype
         self._fused = (val_min, val_max, orig_min, orig_max) == (-1, 1, -1024, 1016)
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise NotImplementedError("ToRange output dtype: float32 or bfloat16")
+        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise NotImplementedError("ToRange output dtype: float32, bfloat16 or float16")
 
     def forward(self, coeff):
         Y, C, single, batched = _unpack(coeff)
         if not self._fused or Y.shape[2] != Y.shape[3] or Y.shape[2] not in (28, 32):
             # any other range (the class default is orig_max = 1024, which no pipeline uses) or grid: the reference's statements
             # (custom_transforms.py:447-451) as device tensor ops -- cast to self.dtype FIRST, then the two statements in that
-            # dtype, same operations in the same order, same bits (for bf16 too)
+            # dtype, same operations in the same order, same bits (for bf16 and fp16 too)
             L.require_cuda(Y) if C is None else L.require_cuda(Y, C)
 
             def f(x):
@@ -504,6 +513,7 @@ class ToRange(torch.nn.Module):
                 x = (x - self.orig_min) / den
                 return self.val_min + x * (self.val_max - self.val_min)
             return _pack(f(Y), None if C is None else f(C), single, batched)
+        # the kernel: ToRange in fp32, ONE rounding to bf16 / fp16 (the fused transform's convention, not cast-first)
         return _pack(*_run_chain(Y, C, Y.shape[2], [_whole(Y)] * Y.shape[0], None, None, 0, self.dtype), single, batched)
 
 
@@ -516,9 +526,11 @@ class TrainTransform_DCT(torch.nn.Module):
         if size not in (28, 32):
             raise NotImplementedError("HIP augment path covers 28x28-block (imagenet_dct) and 32x32-block "
                                       "(imagenet_dct_swin) outputs")
-        if num_ops > 2:
-            raise NotImplementedError("the fused transform chains two operations per sample (cfg.TRAIN.NUMOPS default 2); longer "
-                                      "chains: the per-transform classes, RandAugment_dct(num_ops=N)")
+        if num_ops > AUG_MAX_OPS:
+            raise NotImplementedError(f"the fused transform chains at most {AUG_MAX_OPS} operations per sample (cfg.TRAIN.NUMOPS "
+                                      "default 2); longer chains: the per-transform classes, RandAugment_dct(num_ops=N)")
+        if out_dtype not in (torch.float32, torch.bfloat16, torch.float16, torch.int16):
+            raise NotImplementedError("augment output dtype: float32, bfloat16, float16 (or int16: the raw coefficients)")
         self.size, self.flip_p, self.num_ops, self.magnitude = size, flip_p, num_ops, magnitude
         self.num_magnitude_bins = num_magnitude_bins
         self.ops_list = list(VITTI_OPS if ops_list is None else ops_list)
@@ -579,6 +591,21 @@ class TrainTransform_DCT(torch.nn.Module):
                     a.op[s] = 0
         return arr, nops
 
+    def pack_chain(self, params):
+        """pack() for chains of up to AUG_MAX_OPS operations: the parameter array (crop box and flip; its two op slots stay
+        Identity and are not read), the operations as an AUG_OP_DTYPE array (B, nops), shorter chains padded with Identity, and
+        nops -- the arguments of rgbnm_dct_augment_chain."""
+        B = len(params)
+        nops = max([len(p["ops"]) for p in params] + [0])
+        if nops > AUG_MAX_OPS:
+            raise ValueError(f"one pass of the augment kernels takes at most {AUG_MAX_OPS} operations per sample")
+        arr, _ = self.pack([dict(p, ops=[]) for p in params])
+        ops = np.zeros((B, nops), dtype=AUG_OP_DTYPE)
+        for b, p in enumerate(params):
+            for s, (name, mag, aux) in enumerate(p["ops"]):
+                ops[b, s] = encode_op(name, mag, aux, self.bank, self.size)
+        return arr, ops, nops
+
     def forward(self, Yq, CbCrq, quant, params=None, entry_flags=None):
         """Yq (B,1,Hy,Wy,8,8) int16, CbCrq (B,2,Hc,Wc,8,8) int16 or None, quant (B,3,8,8) int16 -- device tensors.
         entry_flags: rgbnm_dct_augment_ex's `entry_clamp` argument (default: clamp before the ops unless eval_mode)."""
@@ -589,9 +616,14 @@ class TrainTransform_DCT(torch.nn.Module):
         Hc, Wc = (CbCrq.shape[2], CbCrq.shape[3]) if CbCrq is not None else (Hy // 2, Wy // 2)
         if params is None:
             params = self.sample_params(B, Hy, Wy)
-        arr, nops = self.pack(params)
         dev = Yq.device
-        pdev = _params_to_device(self, np.frombuffer(bytes(arr), dtype=np.uint8), dev)
+        ops = None
+        if max([len(p["ops"]) for p in params] + [0]) > 2:
+            arr, ops, nops = self.pack_chain(params)
+        else:
+            arr, nops = self.pack(params)
+        host = np.frombuffer(bytes(arr), dtype=np.uint8)
+        pdev = _params_to_device(self, host if ops is None else np.concatenate([host, ops.view(np.uint8).reshape(-1)]), dev)
         if self._conv16 is None or self._conv16.device != dev:
             self._conv16 = dops.generate_conversion_matrix(8, 2).to(dev).contiguous()
         filt = self.bank.device_tensor(dev)
@@ -601,12 +633,19 @@ class TrainTransform_DCT(torch.nn.Module):
             self._ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
         oy = torch.empty(B, 1, S, S, 8, 8, device=dev, dtype=self.out_dtype)
         oc = torch.empty(B, 2, S // 2, S // 2, 8, 8, device=dev, dtype=self.out_dtype)
-        odt = 2 if self.out_dtype == torch.int16 else L.dt_of(self.out_dtype)      # 2: raw int16, no ToRange (rgbnm.h)
-        rc = L.lib().rgbnm_dct_augment_ex(Yq.data_ptr(), L.ptr(CbCrq), quant.data_ptr(), pdev.data_ptr(),
-                                          C.cast(arr, C.c_void_p), self._conv16.data_ptr(), L.ptr(filt), oy.data_ptr(),
-                                          oc.data_ptr(), odt, S, B, Hy, Wy, Hc, Wc,
-                                          (0 if self.eval_mode else 1) if entry_flags is None else entry_flags, nops,
-                                          self._ws.data_ptr(), self._ws.numel(), L.stream())
+        odt = L.aug_out_code(self.out_dtype)      # 2: raw int16, no ToRange (rgbnm.h)
+        entry = (0 if self.eval_mode else 1) if entry_flags is None else entry_flags
+        if ops is None and odt != L.AUG_OUT_F16:
+            rc = L.lib().rgbnm_dct_augment_ex(Yq.data_ptr(), L.ptr(CbCrq), quant.data_ptr(), pdev.data_ptr(),
+                                              C.cast(arr, C.c_void_p), self._conv16.data_ptr(), L.ptr(filt), oy.data_ptr(),
+                                              oc.data_ptr(), odt, S, B, Hy, Wy, Hc, Wc, entry, nops,
+                                              self._ws.data_ptr(), self._ws.numel(), L.stream())
+        else:       # fp16 output or more than two operations: the chain entry (the ops follow the parameters in pdev)
+            rc = L.lib().rgbnm_dct_augment_chain(Yq.data_ptr(), L.ptr(CbCrq), None, None, quant.data_ptr(), pdev.data_ptr(),
+                                                 C.cast(arr, C.c_void_p), None if ops is None else pdev.data_ptr() + host.nbytes,
+                                                 None if ops is None else ops.ctypes.data, self._conv16.data_ptr(), L.ptr(filt),
+                                                 oy.data_ptr(), oc.data_ptr(), odt, S, B, Hy, Wy, Hc, Wc, entry, nops,
+                                                 self._ws.data_ptr(), self._ws.numel(), L.stream())
         if rc == -1:
             raise L.RgbnmError("dct_augment: invalid parameters (crop side must be size/2, size or 2*size luma blocks "
                                "with even offsets inside the coefficient grid; see include/rgbnm.h)")
@@ -626,6 +665,8 @@ def EvalTransform_DCT(**kw):
 AUG_DTYPE = np.dtype([("crop", "i4", 4), ("flip", "i4"), ("op", "i4", 2), ("fmag", "f4", 2), ("iarg0", "i4", 2),
                       ("iarg1", "i4", 2), ("iarg2", "i4", 2)])
 assert AUG_DTYPE.itemsize == C.sizeof(AugParams)
+AUG_OP_DTYPE = np.dtype([("op", "i4"), ("fmag", "f4"), ("iarg0", "i4"), ("iarg1", "i4"), ("iarg2", "i4")])
+assert AUG_OP_DTYPE.itemsize == C.sizeof(AugOp)
 
 
 class FastParamSampler:
@@ -646,8 +687,8 @@ class FastParamSampler:
                 enc[k, s] = encode_op(n, mag * sg if signed else mag, aux, t.bank, t.size)
         self.enc = enc
         idx = np.arange(len(names))
-        is_chroma = np.array([n in CHROMA_OPS for n in names])
-        is_gray = np.array([n == "Grayscale" for n in names])
+        is_chroma = np.array([n in CHROMA_OPS for n in names], dtype=bool)       # (dtype: an empty op list is a bool array too)
+        is_gray = np.array([n == "Grayscale" for n in names], dtype=bool)
         self.cand_all = idx
         self.cand_after_gray = idx[~is_chroma]          # Grayscale first: no chroma op afterwards (:1116-1117)
         self.cand_after_chroma = idx[~is_gray]          # chroma op first: no Grayscale afterwards (:1118-1119)
@@ -724,6 +765,37 @@ class FastParamSampler:
             prev = k
         return out, nops
 
+    def sample_chain(self, B, H, W):
+        """sample() for any num_ops up to AUG_MAX_OPS: (packed, ops, nops) with the crop boxes and flips in `packed` (its own two
+        op slots stay Identity) and the operations as an AUG_OP_DTYPE array (B, nops) for apply_packed(..., ops=ops).
+        The exclusion rule is cumulative over the chain (custom_transforms.py:1112-1119, sample_ops above): once Grayscale was
+        drawn no CHROMA_OPS member follows (Grayscale included), once another chroma op was drawn no Grayscale follows.  sample()
+        looks at the previous slot only, which is the same thing for two operations."""
+        t, r = self.t, self.rng
+        out = np.zeros(B, dtype=AUG_DTYPE)
+        out["crop"] = self.sample_boxes(B, H, W)
+        out["flip"] = r.random(B) <= t.flip_p
+        nops = t.num_ops if self.names else 0
+        ops = np.zeros((B, nops), dtype=AUG_OP_DTYPE)
+        seen_gray, seen_chroma = np.zeros(B, dtype=bool), np.zeros(B, dtype=bool)
+        for s in range(nops):
+            ua = r.random(B)
+            k = np.where(seen_gray, self.cand_after_gray[(ua * len(self.cand_after_gray)).astype(int)],
+                         np.where(seen_chroma, self.cand_after_chroma[(ua * len(self.cand_after_chroma)).astype(int)],
+                                  self.cand_all[(ua * len(self.cand_all)).astype(int)]))
+            seen_gray |= self.is_gray[k]
+            seen_chroma |= self.is_chroma[k] & ~self.is_gray[k]
+            sg = np.where(self.signed[k], r.integers(0, 2, B), 0)
+            e = self.enc[k, sg]
+            for f, name in enumerate(AUG_OP_DTYPE.names):
+                ops[name][:, s] = e[:, f]
+            cut = k == self.k_cut
+            ops["iarg1"][cut, s] = r.integers(0, t.size, cut.sum()) // 2 * 2
+            ops["iarg2"][cut, s] = r.integers(0, t.size, cut.sum()) // 2 * 2
+            drop = k == self.k_drop
+            ops["iarg0"][drop, s] = r.random(drop.sum()) > 0.5
+        return out, ops, nops
+
 
 _PARAM_SLOTS = 16
 
@@ -754,8 +826,9 @@ def _params_to_device(t, host, dev):
     return pdev
 
 
-def apply_packed(transform, Yq, CbCrq, quant, packed, nops, y_off=None, c_off=None, grid=None, out=None):
-    """Run the augment kernels with an AUG_DTYPE array produced by FastParamSampler.sample().
+def apply_packed(transform, Yq, CbCrq, quant, packed, nops, y_off=None, c_off=None, grid=None, out=None, ops=None):
+    """Run the augment kernels with an AUG_DTYPE array produced by FastParamSampler.sample(), or with the (packed, ops, nops) of
+    sample_chain() (ops: AUG_OP_DTYPE (B, nops), up to AUG_MAX_OPS operations per sample).
     y_off / c_off (device int64 (B,)) + grid=(Hy, Wy): Yq / CbCrq are the flat HOST-CROPPED buffers of
     dct_manip.read_coefficients_batch_crop (image b's crop box alone at Yq[y_off[b]:]); same output, bit for bit."""
     t = transform
@@ -767,7 +840,13 @@ def apply_packed(transform, Yq, CbCrq, quant, packed, nops, y_off=None, c_off=No
         B, (Hy, Wy) = len(packed), grid
         Hc, Wc = (Hy + 1) // 2, (Wy + 1) // 2
     host = np.ascontiguousarray(packed)
-    pdev = _params_to_device(t, host, dev)
+    if ops is not None:
+        ops = np.ascontiguousarray(ops)
+        if ops.dtype != AUG_OP_DTYPE or ops.shape != (B, nops):
+            raise ValueError("ops must be an AUG_OP_DTYPE array of shape (B, nops)")
+    # (the ops follow the parameters in one device buffer: one copy through the pinned ring)
+    both = host if ops is None else np.concatenate([host.view(np.uint8).reshape(-1), ops.view(np.uint8).reshape(-1)])
+    pdev = _params_to_device(t, both, dev)
     if t._conv16 is None or t._conv16.device != dev:
         t._conv16 = dops.generate_conversion_matrix(8, 2).to(dev).contiguous()
     filt = t.bank.device_tensor(dev)
@@ -783,17 +862,27 @@ def apply_packed(transform, Yq, CbCrq, quant, packed, nops, y_off=None, c_off=No
         if (tuple(oy.shape) != (B, 1, S, S, 8, 8) or tuple(oc.shape) != (B, 2, S // 2, S // 2, 8, 8) or oy.dtype != t.out_dtype
                 or oc.dtype != t.out_dtype or not oy.is_contiguous() or not oc.is_contiguous()):
             raise ValueError("out tensors must be contiguous (B,1,S,S,8,8) / (B,2,S/2,S/2,8,8) in the transform's out_dtype")
-    if y_off is None:
+    if ops is not None or t.out_dtype == torch.float16:       # fp16 output or an ops array: the chain entry, both input layouts
+        if y_off is not None:
+            L.require_cuda(y_off, c_off)
+        L.check(L.lib().rgbnm_dct_augment_chain(Yq.data_ptr(), L.ptr(CbCrq), L.ptr(y_off), L.ptr(c_off), quant.data_ptr(),
+                                                pdev.data_ptr(), host.ctypes.data,
+                                                None if ops is None else pdev.data_ptr() + host.nbytes,
+                                                None if ops is None else ops.ctypes.data, t._conv16.data_ptr(), L.ptr(filt),
+                                                oy.data_ptr(), oc.data_ptr(), L.aug_out_code(t.out_dtype), S, B, Hy, Wy, Hc, Wc,
+                                                0 if t.eval_mode else 1, nops, t._ws.data_ptr(), t._ws.numel(), L.stream()),
+                "dct_augment_chain")
+    elif y_off is None:
         L.check(L.lib().rgbnm_dct_augment_ex(Yq.data_ptr(), L.ptr(CbCrq), quant.data_ptr(), pdev.data_ptr(),
                                              host.ctypes.data, t._conv16.data_ptr(), L.ptr(filt), oy.data_ptr(),
-                                             oc.data_ptr(), L.dt_of(t.out_dtype), S, B, Hy, Wy, Hc, Wc,
+                                             oc.data_ptr(), L.aug_out_code(t.out_dtype), S, B, Hy, Wy, Hc, Wc,
                                              0 if t.eval_mode else 1, nops, t._ws.data_ptr(), t._ws.numel(), L.stream()),
                 "dct_augment")
     else:
         L.require_cuda(y_off, c_off)
         L.check(L.lib().rgbnm_dct_augment_packed(Yq.data_ptr(), L.ptr(CbCrq), y_off.data_ptr(), c_off.data_ptr(),
                                                  quant.data_ptr(), pdev.data_ptr(), host.ctypes.data, t._conv16.data_ptr(),
-                                                 L.ptr(filt), oy.data_ptr(), oc.data_ptr(), L.dt_of(t.out_dtype), S, B, Hy, Wy,
+                                                 L.ptr(filt), oy.data_ptr(), oc.data_ptr(), L.aug_out_code(t.out_dtype), S, B, Hy, Wy,
                                                  Hc, Wc, 0 if t.eval_mode else 1, nops, t._ws.data_ptr(), t._ws.numel(),
                                                  L.stream()), "dct_augment_packed")
     return oy, oc

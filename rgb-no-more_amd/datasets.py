@@ -8,6 +8,8 @@ composes the device transform classes of `custom_transforms` exactly as the refe
 transforms accept one sample (C,H,W,8,8) -- the reference's calling convention -- or a whole batch (B,C,H,W,8,8);
 `fused=True` returns the one-launch-pair batch transform (`TrainTransform_DCT` / `EvalTransform_DCT`) instead, which takes
 the RAW quantised coefficients plus the quantisation tables and also does the de-quantisation of datasets.py:288-293.
+`dtype` is float32, bfloat16 or float16 (train.py --ampdtype) and `num_ops` any chain length (--num_ops) in both forms: the fused
+transform runs up to custom_transforms.AUG_MAX_OPS operations in its one launch pair, RandAugment_dct that many per pass.
 """
 import torch
 

@@ -9,6 +9,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "librgbnm.so")
 
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
+# rgbnm_dct_augment_chain (include/rgbnm.h RGBNM_AUG_*): output codes of the augment stage (2 is raw int16 there, so fp16 is 3) and
+# the longest op chain of one pass
+AUG_OUT_F32, AUG_OUT_BF16, AUG_OUT_I16, AUG_OUT_F16 = 0, 1, 2, 3
+AUG_MAX_OPS = 8
 EPI_NONE, EPI_RES, EPI_GELU, EPI_POS, EPI_DGELU, EPI_TANH, EPI_DTANH = range(7)
 EPI_RES_DROP, EPI_GELU_DROP = 7, 8      # rgbnm_gemm_nt_drop only
 
@@ -122,12 +126,15 @@ PROTOTYPES = {
                                   _sz, _vp]),
     "rgbnm_dct_augment_packed": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
                                       _i, _vp, _sz, _vp]),
+    "rgbnm_dct_augment_chain": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
+                                     _i, _vp, _sz, _vp]),
     "rgbnm_softxent": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "rgbnm_softxent_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "rgbnm_softxent_grad": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "rgbnm_softxent_loss_mix": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "rgbnm_softxent_grad_mix": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "rgbnm_mixup": (_i, [_i, _i, _vp, _vp, _vp, _i, _ll, _vp]),
+    "rgbnm_mixup_any": (_i, [_i, _i, _vp, _vp, _vp, _i, _ll, _vp]),
     "rgbnm_mixup_target": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "rgbnm_clip_adamw_wd_workspace": (_sz, []),
     "rgbnm_clip_adamw_wd_step": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _i, _f, _f, _vp, _vp, _sz, _vp]),
@@ -255,6 +262,14 @@ def dt_of(t):
     if t == torch.float16:
         return DT_F16
     raise TypeError(f"unsupported dtype {t} (float32, bfloat16 or float16)")
+
+
+def aug_out_code(t):
+    """RGBNM_AUG_OUT_* of a torch dtype (the augment stage's own codes; int16 = the raw coefficients, no ToRange)."""
+    try:
+        return {torch.float32: AUG_OUT_F32, torch.bfloat16: AUG_OUT_BF16, torch.int16: AUG_OUT_I16, torch.float16: AUG_OUT_F16}[t]
+    except KeyError:
+        raise TypeError(f"unsupported augment output dtype {t} (float32, bfloat16, float16 or int16)") from None
 
 
 def ptr(t):

@@ -121,7 +121,7 @@ def main():
         lab = torch.randint(0, 999, (B,), device=dev)
         legs = {}
         for cfg in CONFIGS:
-            adt = torch.bfloat16 if cfg == "bf16" else torch.float32          # augment output (no fp16 augment output)
+            adt = torch.bfloat16 if cfg == "bf16" else torch.float32          # augment output (fed float16 instead: tools/aug_chain_step.py)
             cdt = torch.float16 if cfg in F16_CONFIGS else torch.bfloat16
             aug = CT.TrainTransform_DCT(size=32 if swin else 28, out_dtype=adt)
             mix = rg.cls_transforms.RandomMixup_DCT(1000, alpha=0.2)
