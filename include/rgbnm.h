@@ -438,6 +438,34 @@ int rgbnm_clip_adamw_wd_step_scaled(float* p, const float* g, float* m, float* v
                                     float* norm_out, rgbnm_loss_scale_state* state, double growth_factor, double backoff_factor,
                                     int growth_interval, float scale_min, float scale_max, void* workspace,
                                     size_t workspace_bytes, void* stream);
+/* The scaled tail with the learning-rate schedule on the device as well: what train.py's loop does around it with a host
+ * scheduler (train.py:149-152 warm-up, 174-176 scheduler.step(); custom_optims.py:37-42 reads group['lr'] / group['base_lr']).
+ * lr and wd_factor leave the argument list, so no argument of the two launches changes between steps and a captured call
+ * (hipGraph) replays correctly.  The schedule has a state block of its own, caller-owned device memory, written by the second
+ * launch only, with ordinary stores: */
+typedef struct rgbnm_lr_sched_state {
+  int iter;            /* calls seen so far, skipped steps included: the index the NEXT call looks up */
+  float lr;            /* the lr the latest call used (logging) */
+  float wd_factor;     /* the wd_factor the latest call used (logging) */
+  int reserved[5];
+} rgbnm_lr_sched_state;
+/* rgbnm_clip_adamw_wd_step_scaled with (lr, wd_factor) replaced by (lr_table, table_len, base_lr, weight_decay) and `sched` behind
+ * `state`.  lr_table is device memory of table_len doubles; entry k is the host scheduler's param_groups[0]['lr'] at the
+ * optimizer.step() of iteration k.  Launch 1 additionally reads sched->iter, takes k = min(iter, table_len - 1), lr_d = lr_table[k]
+ * and leaves lr = (float)lr_d, wd_factor = (float)((lr_d / base_lr) * weight_decay) (one fp64 divide, one fp64 multiply, one
+ * rounding: the host expression of the scaled entry's caller) and iter in the workspace, next to inv, step, scale and the bias
+ * corrections.  Launch 2 reads them from the workspace only and performs the scaled entry's arithmetic: same bits as
+ * rgbnm_clip_adamw_wd_step_scaled called with those two floats.  Its workgroup 0 then writes sched->iter = iter + 1, sched->lr and
+ * sched->wd_factor -- on a skipped step too (the reference steps its scheduler every iteration); state->step keeps its rule.
+ * RGBNM_EINVAL for what the scaled entry refuses, a NULL lr_table or sched, table_len < 1, base_lr not > 0, weight_decay NaN or
+ * < 0; RGBNM_EWORKSPACE for a short workspace: nothing is launched, both state blocks are untouched. */
+size_t rgbnm_clip_adamw_wd_sched_workspace(void);
+int rgbnm_clip_adamw_wd_step_sched(float* p, const float* g, float* m, float* v, const unsigned char* wd_flag_per_256,
+                                   long long n, const double* lr_table, int table_len, double base_lr, double weight_decay,
+                                   float beta1, float beta2, float eps, float max_norm, float* norm_out,
+                                   rgbnm_loss_scale_state* state, rgbnm_lr_sched_state* sched, double growth_factor,
+                                   double backoff_factor, int growth_interval, float scale_min, float scale_max, void* workspace,
+                                   size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Composite stages: one call per autograd node (ViT, plainvit.py:559-611)

@@ -17,3 +17,5 @@ from . import eval  # noqa: F401,E402,A004
 from . import datasets  # noqa: F401,E402
 from . import loader  # noqa: F401,E402
 from .loader import DCTBatchLoader  # noqa: F401,E402
+from . import graphstep  # noqa: F401,E402
+from .graphstep import CapturedTrainStep  # noqa: F401,E402

@@ -463,6 +463,140 @@ __global__ __launch_bounds__(256) void adamw_scaled_kernel(ScaledArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The scaled tail with the learning-rate schedule on the device too (rgbnm_clip_adamw_wd_step_sched): no argument of the two
+// launches changes from step to step, so a captured call replays.  The pair stands beside the scaled pair (whose kernels, names
+// and bits stay) and repeats its arithmetic statement for statement; what differs is where lr and wd_factor come from.  The
+// workspace carries, behind the scaled entry's five words:
+//   [NORM_BLOCKS + 5] lr = (float)lr_table[k]     [+ 6] wd_factor = (float)((lr_table[k] / base_lr) * weight_decay)
+//   [NORM_BLOCKS + 7] iter (int bits), k = min(iter, table_len - 1)
+// wd_factor is one fp64 divide, one fp64 multiply and one rounding to fp32 -- FusedClipAdamWWD.step's host expression followed by
+// the double -> float of its call; there is no sum next to the product, so -ffp-contract=fast has nothing to fuse.
+constexpr int SCHED_WS_FLOATS = NORM_BLOCKS + 8;
+
+__global__ __launch_bounds__(256) void sqnorm_unscale_sched_kernel(const float* __restrict__ g, long long n, float* __restrict__ part,
+                                                                   const rgbnm_loss_scale_state* __restrict__ state,
+                                                                   const rgbnm_lr_sched_state* __restrict__ sched,
+                                                                   const double* __restrict__ lr_table, int table_len,
+                                                                   double base_lr, double weight_decay, float beta1, float beta2) {
+  __shared__ float red[4];
+  const float scale = state->scale;
+  const float inv = (float)(1.0 / (double)scale);
+  float a = 0.f;
+  // sqnorm_unscale_kernel's loop: the same four strides per turn, the same order of additions
+  constexpr long long STRIDE = (long long)NORM_BLOCKS * 256 * 4;
+  for (long long i = (blockIdx.x * 256LL + threadIdx.x) * 4; i < n; i += 4 * STRIDE) {
+    f32x4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long j = i + u * STRIDE;
+      v[u] = j < n ? *reinterpret_cast<const f32x4*>(g + j) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (i + u * STRIDE < n) {
+        const float x0 = v[u][0] * inv, x1 = v[u][1] * inv, x2 = v[u][2] * inv, x3 = v[u][3] * inv;
+        a += x0 * x0 + x1 * x1 + x2 * x2 + x3 * x3;
+      }
+  }
+  a = wave_sum(a);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const int step = state->step;
+    const double t = (double)step + 1.0;
+    part[NORM_BLOCKS] = inv;
+    reinterpret_cast<int*>(part)[NORM_BLOCKS + 1] = step;
+    part[NORM_BLOCKS + 2] = (float)(1.0 - pow((double)beta1, t));
+    part[NORM_BLOCKS + 3] = (float)sqrt(1.0 - pow((double)beta2, t));
+    part[NORM_BLOCKS + 4] = scale;
+    const int iter = sched->iter;
+    const int k = iter < 0 ? 0 : (iter < table_len ? iter : table_len - 1);     // an iter below 0 is not ours: stay in the table
+    const double lr_d = lr_table[k];
+    const double ratio = lr_d / base_lr;
+    part[NORM_BLOCKS + 5] = (float)lr_d;
+    part[NORM_BLOCKS + 6] = (float)(ratio * weight_decay);
+    reinterpret_cast<int*>(part)[NORM_BLOCKS + 7] = iter;
+  }
+}
+
+struct SchedArgs {
+  float* p; const float* g; float* m; float* v; const unsigned char* wd_flag; const float* part; float* norm_out;
+  rgbnm_loss_scale_state* state;
+  rgbnm_lr_sched_state* sched;
+  long long n;
+  double growth, backoff;
+  float beta1, beta2, eps, max_norm, scale_min, scale_max;
+  int growth_interval;
+};
+
+__global__ __launch_bounds__(256) void adamw_sched_kernel(SchedArgs a) {
+  __shared__ float red[4];
+  __shared__ float coef_s;
+  __shared__ int finite_s;
+  {
+    float t = a.part[threadIdx.x];   // NORM_BLOCKS == blockDim.x
+    t = wave_sum(t);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const float total = sqrtf(red[0] + red[1] + red[2] + red[3]);
+      float c = a.max_norm > 0.f ? a.max_norm / (total + 1e-6f) : 1.f;
+      coef_s = c < 1.f ? c : 1.f;
+      finite_s = isfinite(total) ? 1 : 0;
+      if (blockIdx.x == 0 && a.norm_out) a.norm_out[0] = total;
+    }
+    __syncthreads();
+  }
+  const bool finite = finite_s != 0;
+  const float lr = a.part[NORM_BLOCKS + 5], wd_factor = a.part[NORM_BLOCKS + 6];
+  if (finite) {
+    const float coef = coef_s;
+    const float inv = a.part[NORM_BLOCKS], bc1 = a.part[NORM_BLOCKS + 2], bc2_sqrt = a.part[NORM_BLOCKS + 3];
+    const float step = lr / bc1;
+    for (long long chunk = blockIdx.x; chunk * 256 < a.n; chunk += gridDim.x) {
+      const long long i = chunk * 256 + threadIdx.x;
+      const float gu = a.g[i] * inv;               // unscale_ first,
+      const float g = gu * coef;                   // then the clip: two roundings
+      const float m = a.beta1 * a.m[i] + (1.f - a.beta1) * g;
+      const float v = a.beta2 * a.v[i] + (1.f - a.beta2) * g * g;
+      a.m[i] = m;
+      a.v[i] = v;
+      float p = a.p[i];
+      p -= step * (m / (sqrtf(v) / bc2_sqrt + a.eps));
+      if (a.wd_flag[chunk]) p -= wd_factor * p;
+      a.p[i] = p;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {       // adamw_scaled_kernel's state update, then the schedule's
+    rgbnm_loss_scale_state* st = a.state;
+    float scale = a.part[NORM_BLOCKS + 4];
+    int tracker = st->growth_tracker;
+    if (!finite) {
+      scale = (float)((double)scale * a.backoff);
+      tracker = 0;
+      st->skipped = st->skipped + 1;
+    } else {
+      st->step = reinterpret_cast<const int*>(a.part)[NORM_BLOCKS + 1] + 1;
+      if (++tracker == a.growth_interval) {
+        const float grown = (float)((double)scale * a.growth);
+        if (isfinite(grown)) scale = grown;
+        tracker = 0;
+      }
+    }
+    if (scale > a.scale_max) scale = a.scale_max;
+    if (scale < a.scale_min) scale = a.scale_min;
+    st->scale = scale;
+    st->growth_tracker = tracker;
+    st->found_inf = finite ? 0.f : 1.f;
+    rgbnm_lr_sched_state* sc = a.sched;            // the scheduler steps every iteration, skipped or not (train.py:174-176)
+    sc->iter = reinterpret_cast<const int*>(a.part)[NORM_BLOCKS + 7] + 1;
+    sc->lr = lr;
+    sc->wd_factor = wd_factor;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -649,6 +783,37 @@ int rgbnm_clip_adamw_wd_step_scaled(float* p, const float* g, float* m, float* v
   a.scale_min = scale_min; a.scale_max = scale_max; a.growth_interval = growth_interval;
   const int grid = (int)min(4096LL, n / 256);
   hipLaunchKernelGGL(adamw_scaled_kernel, dim3(grid), dim3(256), 0, st, a);
+  rgbnm_trace_end(tslot, st);
+  LAUNCH_CHECK();
+  return RGBNM_OK;
+}
+
+size_t rgbnm_clip_adamw_wd_sched_workspace(void) { return SCHED_WS_FLOATS * sizeof(float); }
+
+int rgbnm_clip_adamw_wd_step_sched(float* p, const float* g, float* m, float* v, const unsigned char* wd_flag_per_256,
+                                   long long n, const double* lr_table, int table_len, double base_lr, double weight_decay,
+                                   float beta1, float beta2, float eps, float max_norm, float* norm_out,
+                                   rgbnm_loss_scale_state* state, rgbnm_lr_sched_state* sched, double growth_factor,
+                                   double backoff_factor, int growth_interval, float scale_min, float scale_max, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  if (!p || !g || !m || !v || !wd_flag_per_256 || !state || !workspace || n <= 0 || (n & 255)) return RGBNM_EINVAL;
+  if (growth_interval < 1 || !(growth_factor > 0.0) || !(backoff_factor > 0.0) || !(scale_min <= scale_max)) return RGBNM_EINVAL;
+  if (!lr_table || !sched || table_len < 1 || !(base_lr > 0.0) || !(weight_decay >= 0.0)) return RGBNM_EINVAL;
+  if (workspace_bytes < SCHED_WS_FLOATS * sizeof(float)) return RGBNM_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  float* part = (float*)workspace;
+  const int tslot = rgbnm_trace_begin(TR_OPT, 0.0, 32.0 * (double)n, st);      // the bytes of rgbnm_clip_adamw_wd_step
+  hipLaunchKernelGGL(sqnorm_unscale_sched_kernel, dim3(NORM_BLOCKS), dim3(256), 0, st, g, n, part, state, sched, lr_table,
+                     table_len, base_lr, weight_decay, beta1, beta2);
+  LAUNCH_CHECK();
+  SchedArgs a;
+  a.p = p; a.g = g; a.m = m; a.v = v; a.wd_flag = wd_flag_per_256; a.part = part; a.norm_out = norm_out; a.state = state;
+  a.sched = sched; a.n = n;
+  a.growth = growth_factor; a.backoff = backoff_factor;
+  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.max_norm = max_norm;
+  a.scale_min = scale_min; a.scale_max = scale_max; a.growth_interval = growth_interval;
+  const int grid = (int)min(4096LL, n / 256);
+  hipLaunchKernelGGL(adamw_sched_kernel, dim3(grid), dim3(256), 0, st, a);
   rgbnm_trace_end(tslot, st);
   LAUNCH_CHECK();
   return RGBNM_OK;

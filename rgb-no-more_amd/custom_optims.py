@@ -11,6 +11,9 @@
 * `DeviceLossScaler` -- torch.amp.GradScaler(1.6, 0.625, 600) + pipeline_utils.clip_gradscaler (train.py:160-167,
   pipeline_utils.py:399-409, 541) with the scale, the inf / NaN check, the skipped step and the scale update on the device,
   inside FusedClipAdamWWD's two launches (rgbnm_clip_adamw_wd_step_scaled): fp16 training without a host sync.
+* `DeviceLRSchedule` -- train.py's warm-up + cosine learning-rate schedule (train.py:149-152, 174-176, pipeline_utils.py:538) as
+  a float64 table on the device, looked up inside the same two launches (rgbnm_clip_adamw_wd_step_sched) once it is attached
+  with FusedClipAdamWWD.attach_schedule: no argument of the step changes between steps, so the step can be captured.
 """
 import math
 
@@ -47,6 +50,39 @@ class FusedClipAdamWWD(Optimizer):
         self._dev_step = None          # the DeviceLossScaler whose state block holds the step count while it is the truth
         self._state_ready = False
         self.last_norm = None
+        self._sched = None             # the attached DeviceLRSchedule
+        self._neutral = None           # the scale-1 DeviceLossScaler an attached schedule steps under when no scaler is given
+
+    def attach_schedule(self, schedule):
+        """From now on step() and step(loss_scaler=...) take lr and wd_factor from `schedule`'s device table
+        (rgbnm_clip_adamw_wd_step_sched) and do not read param_groups[0]['lr']; base_lr and weight_decay stay the group's.
+        Every upload happens here or on the first step after it (the table, the state blocks, the Adam step count); later
+        steps neither sync nor upload, so a step() under torch.cuda.graph capture succeeds and replays.
+        The entry always runs under a loss-scale block.  With no DeviceLossScaler (bf16 / fp32 training) the optimizer passes a
+        neutral one of its own (scale 1, both factors 1, scale_min = scale_max = 1): the arithmetic of the plain step on
+        gradients multiplied by 1.0f, with ONE visible consequence -- a non-finite gradient norm skips the step and counts in
+        skipped_steps(), where the plain step() would write NaN into the weights.  state_dict() and the read-back of the step
+        count behave as under a DeviceLossScaler."""
+        if not isinstance(schedule, DeviceLRSchedule):
+            raise TypeError(f"attach_schedule needs a DeviceLRSchedule, got {type(schedule).__name__}")
+        self._ensure()
+        dev = self._m._flat.device
+        schedule._device(dev)
+        if self._neutral is None:
+            self._neutral = DeviceLossScaler(init_scale=1.0, growth_factor=1.0, backoff_factor=1.0, scale_min=1.0, scale_max=1.0)
+        self._neutral._device_state(dev)
+        self._sched = schedule
+
+    def detach_schedule(self):
+        """Back to param_groups[0]['lr'] (the host scheduler's); the schedule keeps its position."""
+        self._sched = None
+        if self._dev_step is not None and self._dev_step is self._neutral:
+            self._read_back_step()
+
+    def skipped_steps(self):
+        """Steps the neutral loss-scale block skipped because the gradient norm was not finite (syncs; logging only).  Steps
+        under a DeviceLossScaler count in that scaler."""
+        return self._neutral.skipped_steps() if self._neutral is not None else 0
 
     def _ensure(self):
         m = self._m
@@ -54,8 +90,8 @@ class FusedClipAdamWWD(Optimizer):
         if not self._state_ready or self._exp_avg.numel() != m._flat.numel() or self._exp_avg.device != m._flat.device:
             self._exp_avg = torch.zeros_like(m._flat)
             self._exp_avg_sq = torch.zeros_like(m._flat)
-            self._ws = torch.empty(max(L.lib().rgbnm_clip_adamw_wd_workspace(), L.lib().rgbnm_clip_adamw_wd_scaled_workspace()),
-                                   device=m._flat.device, dtype=torch.uint8)
+            self._ws = torch.empty(max(L.lib().rgbnm_clip_adamw_wd_workspace(), L.lib().rgbnm_clip_adamw_wd_scaled_workspace(),
+                                       L.lib().rgbnm_clip_adamw_wd_sched_workspace()), device=m._flat.device, dtype=torch.uint8)
             self._norm = torch.zeros(1, device=m._flat.device, dtype=torch.float32)
             self._gather = None
             self._state_ready = True
@@ -74,7 +110,8 @@ class FusedClipAdamWWD(Optimizer):
         The one host sync of that mode; state_dict() and the first plain step() after it come through here."""
         if self._dev_step is not None:
             self._step = self._dev_step._device_step()
-            self._dev_step = None
+            if self._sched is None:    # (with a schedule attached the block stays the truth: a captured step goes on counting there)
+                self._dev_step = None
 
     def state_dict(self):
         self._ensure()
@@ -108,7 +145,10 @@ class FusedClipAdamWWD(Optimizer):
         if len(steps) > 1:
             raise ValueError(f"FusedClipAdamWWD keeps ONE step count for all parameters; the state has {sorted(steps)}")
         self._step = steps.pop() if steps else 0
-        self._dev_step = None                        # the loaded count is the truth; the next scaled step uploads it
+        if self._sched is not None and self._dev_step is not None:
+            self._dev_step._set_device_step(self._step)     # a captured step cannot upload it later: the block gets it now
+        else:
+            self._dev_step = None                    # the loaded count is the truth; the next scaled step uploads it
         self._publish_state()
 
     def _flat_grads(self):
@@ -143,6 +183,8 @@ class FusedClipAdamWWD(Optimizer):
         m = self._m
         if loss_scaler is not None and not loss_scaler._enabled:
             loss_scaler = None
+        if self._sched is not None:
+            return self._step_sched(loss_scaler)
         if loss_scaler is None:
             self._read_back_step()
             self._step += 1
@@ -171,6 +213,124 @@ class FusedClipAdamWWD(Optimizer):
                 s._growth_interval, s._scale_min, s._scale_max, self._ws.data_ptr(), self._ws.numel(), L.stream()),
                 "clip_adamw_wd_step_scaled")
         self.last_norm = self._norm
+
+    def _prepare_sched(self, loss_scaler=None):
+        """The loss-scale block an attached schedule steps under (loss_scaler's, or the neutral one), holding the Adam step
+        count.  Uploads and syncs on first use only; that first use cannot be a captured one."""
+        s = loss_scaler if loss_scaler is not None and loss_scaler._enabled else self._neutral
+        if s._state is None or self._dev_step is not s:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the first step() with an attached schedule (or after a change of loss scaler) uploads the "
+                                   "Adam step count and cannot be captured: take one eager step first")
+            s._device_state(self._m._flat.device)
+            self._read_back_step()                     # (another scaler's count, if there was one)
+            s._set_device_step(self._step)
+            self._dev_step = s
+        return s
+
+    def _step_sched(self, loss_scaler):
+        m, g = self._m, self.param_groups[0]
+        s = self._prepare_sched(loss_scaler)
+        if m._grad_sync is not None:
+            m._grad_sync.wait()
+        gptr = self._flat_grads()
+        sch = self._sched
+        L.check(L.lib().rgbnm_clip_adamw_wd_step_sched(
+            m._flat.data_ptr(), gptr, self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr(), m._wd_flags.data_ptr(),
+            m._flat.numel(), sch._table.data_ptr(), sch._table.numel(), g["base_lr"], g["weight_decay"], g["betas"][0],
+            g["betas"][1], g["eps"], g["max_norm"] if g["max_norm"] else 0.0, self._norm.data_ptr(), s._state.data_ptr(),
+            sch._state.data_ptr(), s._growth_factor, s._backoff_factor, s._growth_interval, s._scale_min, s._scale_max,
+            self._ws.data_ptr(), self._ws.numel(), L.stream()), "clip_adamw_wd_step_sched")
+        self.last_norm = self._norm
+
+
+class DeviceLRSchedule:
+    """A learning-rate schedule as a float64 table on the device: entry k is what param_groups[0]['lr'] holds at the
+    optimizer.step() of iteration k under the host scheduler the table was recorded from.  FusedClipAdamWWD.attach_schedule
+    makes the fused tail look it up (include/rgbnm.h, rgbnm_lr_sched_state: the block counts every call, skipped steps included,
+    as train.py steps its scheduler every iteration); past the last entry the last entry holds.  train.py:149-152, 174-176
+
+        if current_itr < WARMUP: adjust_lr(optimizer, LR * (current_itr + 1) / WARMUP); copy_lr(optimizer, weight_decayer)
+        ...
+        if current_itr >= WARMUP: cosinescheduler.step(); copy_lr(optimizer, weight_decayer)
+
+    become `optimizer.attach_schedule(DeviceLRSchedule.warmup_cosine(LR, WARMUP, max_iters))`, once, before the loop.
+    get_last_lr(), iteration() and state_dict() sync; they are for logging and checkpoints."""
+
+    def __init__(self, values):
+        t = torch.tensor([float(x) for x in values], dtype=torch.float64)
+        if t.numel() < 1:
+            raise ValueError("a DeviceLRSchedule needs at least one learning rate")
+        if not bool(torch.isfinite(t).all()) or bool((t < 0).any()):
+            raise ValueError("learning rates must be finite and not negative")
+        self._values = t
+        self._iter = 0              # until the state block exists
+        self._table = None          # float64 [len] on the device
+        self._state = None          # int32 [8] on the device: rgbnm_lr_sched_state
+
+    @classmethod
+    def from_scheduler(cls, make_scheduler, n_iters, base_lr, warmup=0):
+        """Record n_iters iterations of train.py's loop (train.py:149-152, 174-176) run on the host against a dummy AdamW of
+        learning rate base_lr and the torch scheduler `make_scheduler(optimizer)` returns.  The doubles stored are the ones
+        torch's scheduler leaves in param_groups[0]['lr'] (its own recursion), not a closed form.  As in train.py, current_itr
+        is incremented before it is compared: iteration k runs with current_itr = k + 1."""
+        opt = torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))], lr=base_lr, weight_decay=0)
+        sched = make_scheduler(opt)
+        values, current_itr = [], 0
+        for _ in range(int(n_iters)):
+            current_itr += 1
+            if current_itr < warmup:
+                for g in opt.param_groups:
+                    g["lr"] = base_lr * (current_itr + 1) / warmup
+            values.append(opt.param_groups[0]["lr"])
+            opt.step()
+            if current_itr >= warmup:
+                sched.step()
+        return cls(values)
+
+    @classmethod
+    def warmup_cosine(cls, base_lr, warmup, max_iters):
+        """The reference's schedule: linear warm-up, then CosineAnnealingLR(T_max = max_iters - warmup, eta_min = 0)
+        stepped every iteration (pipeline_utils.py:538)."""
+        return cls.from_scheduler(
+            lambda opt: torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=max_iters - warmup, eta_min=0), max_iters, base_lr,
+            warmup)
+
+    def __len__(self):
+        return self._values.numel()
+
+    def values(self):
+        """The table as Python floats (the host copy)."""
+        return self._values.tolist()
+
+    def _device(self, device):
+        if self._state is None:
+            self._table = self._values.to(device)
+            st = torch.zeros(8, dtype=torch.int32)
+            st[0] = self._iter
+            self._state = st.to(device)
+        return self._state
+
+    def iteration(self):
+        """Calls seen so far, skipped steps included (syncs)."""
+        if self._state is not None:
+            self._iter = int(self._state[0].item())
+        return self._iter
+
+    def get_last_lr(self):
+        """[lr of the latest step] as torch schedulers report it, in full precision (syncs); before the first step, entry 0."""
+        k = min(max(self.iteration() - 1, 0), len(self) - 1)
+        return [float(self._values[k])]
+
+    def state_dict(self):
+        return {"iter": self.iteration(), "table_len": len(self)}
+
+    def load_state_dict(self, state_dict):
+        if int(state_dict["table_len"]) != len(self):
+            raise ValueError(f"the schedule state belongs to a table of {state_dict['table_len']} entries, this one has {len(self)}")
+        self._iter = int(state_dict["iter"])
+        if self._state is not None:
+            self._state[:1].fill_(self._iter)
 
 
 class DeviceLossScaler:

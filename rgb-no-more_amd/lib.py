@@ -141,7 +141,10 @@ PROTOTYPES = {
     "rgbnm_clip_adamw_wd_scaled_workspace": (_sz, []),
     "rgbnm_clip_adamw_wd_step_scaled": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _f, _f, _vp, _vp, _d, _d, _i, _f, _f,
                                              _vp, _sz, _vp]),
-    "rgbnm_vit_workspace": (_sz, [_P(VitCfg)]),
+    "rgbnm_clip_adamw_wd_sched_workspace": (_sz, []),
+    "rgbnm_clip_adamw_wd_step_sched": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _vp, _i, _d, _d, _f, _f, _f, _f, _vp, _vp, _vp, _d, _d, _i,
+                                            _f, _f, _vp, _sz, _vp]),
+    "rgbnm_vit_workspace":(_sz, [_P(VitCfg)]),
     "rgbnm_vit_workspace_ex": (_sz, [_P(VitCfg), _i]),
     "rgbnm_head_bwd_workspace": (_sz, [_vp, _i]),
     "rgbnm_gelu_table_init": (_i, [_vp]),
