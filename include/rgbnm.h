@@ -22,9 +22,11 @@
  *     fp16 through the plain GEMM kernels tuned for 16-bit operands, at the shapes where bf16 takes them: the small-M kernel
  *     (none / tanh / dtanh), the weight-resident and the k-pipelined row-panel kernels (none / residual / GELU with the erf
  *     arithmetic / dGELU), the pipelined and wide weight-gradient kernels, and the rgbnm_gemm_tn_group_* brackets (a queue holds
- *     jobs of one dtype: a job of another dtype runs what is queued first).  The other bf16-tuned kernels (one-launch chains,
- *     fused MLP, attention v2, LayerNorm-chained row-panel epilogues, the bf16 GELU table) are bf16 only and are skipped for
- *     fp16 whatever the option says.  The data stage has fp16 through entries of its own: rgbnm_dct_augment_chain writes it
+ *     jobs of one dtype: a job of another dtype runs what is queued first).  At "f16_tuned" >= 2 fp16 also takes the per-block fused
+ *     kernels where bf16 takes them: attention v2 (rgbnm_attention_fwd / _bwd, N <= 224), the fused MLP forward / backward and the
+ *     LayerNorm-chained row-panel epilogues (rgbnm_vit_block_fwd[_chain] / _bwd, rgbnm_vit_ln_chain; E = 192, >= 8192 rows), with
+ *     the erf arithmetic for GELU.  The one-launch chains and the bf16 GELU table are bf16 only and are skipped for fp16 whatever
+ *     the option says.  The data stage has fp16 through entries of its own: rgbnm_dct_augment_chain writes it
  *     (RGBNM_AUG_OUT_F16) and rgbnm_mixup_any mixes to it; the three rgbnm_dct_augment* entries and rgbnm_mixup keep to fp32 / bf16.
  *   - tensors are dense row-major; "ld*" are row strides in elements.
  */
@@ -71,6 +73,10 @@ int rgbnm_abi_version(void);
  *   "nt_small"     1  at most 512 rows (the classification head) on 32 x 32 tiles with an in-workgroup split of K
  *   "f16_tuned"    0  fp16 on the kernels of nt_small / nt_wres / nt_kpipe / tn_pipe / tn_wide and in the grouped dW launches, as bf16
  *                     (0: fp16 runs the generic tile kernels only, as it did before the option existed: same launches, same bits)
+ *                     levels: 0 off | 1 the plain GEMMs above | 2 level 1 plus attention v2 (attn_v2, attn_persist), the fused MLP
+ *                     (mlp_fuse, mlp_bwd, mlp_dmast, nt_cold) and the LayerNorm-chained epilogues (ln_fuse) in their fp16 instantiations,
+ *                     under the shape conditions of bf16; fp16 GELU is always the erf arithmetic (no table).  Levels 0 and 1 launch
+ *                     what they launched before level 2 existed and give the same bits
  *   "ln_fuse"      1  LayerNorm forward / backward in the row-panel kernel's epilogues (E = 192)
  *   GEMM  dW = dY^T . X (weight gradients)
  *   "tn_pipe"      1  pipelined kernel (csrc/gemm_tn_pipe.hip; 0: the generic one)     "tn_tr"  1  its ds_read_b64_tr_b16 fragments

@@ -460,7 +460,9 @@ int rgbnm_attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B
     if (dtype == DT_F16) return attn_fwd_t<f16, 10>(qkv, out, lse, B, N, heads, scale, st);
     return RGBNM_EINVAL;
   }
-  if (dtype == DT_BF16 && rgbnm_get_option("attn_v2")) return rgbnm_launch_attn2_fwd(qkv, out, lse, B, N, heads, scale, st);
+  // fp16 takes the LDS-DMA kernels from f16_tuned level 2 on (rgbnm.h, rgbnm_set_option)
+  if ((dtype == DT_BF16 || (dtype == DT_F16 && rgbnm_get_option("f16_tuned") >= 2)) && rgbnm_get_option("attn_v2"))
+    return rgbnm_launch_attn2_fwd(dtype, qkv, out, lse, B, N, heads, scale, st);
   if (dtype == DT_BF16) return attn_fwd_t<bf16, 7>(qkv, out, lse, B, N, heads, scale, st);
   if (dtype == DT_F32) return attn_fwd_t<float, 7>(qkv, out, lse, B, N, heads, scale, st);
   if (dtype == DT_F16) return attn_fwd_t<f16, 7>(qkv, out, lse, B, N, heads, scale, st);
@@ -477,8 +479,8 @@ int rgbnm_attention_bwd(int dtype, const void* qkv, const void* out, const void*
     if (dtype == DT_F16) return attn_bwd_t<f16, 10>(qkv, out, dout, lse, dqkv, B, N, heads, scale, st);
     return RGBNM_EINVAL;
   }
-  if (dtype == DT_BF16 && rgbnm_get_option("attn_v2"))
-    return rgbnm_launch_attn2_bwd(qkv, out, dout, lse, dqkv, B, N, heads, scale, st);
+  if ((dtype == DT_BF16 || (dtype == DT_F16 && rgbnm_get_option("f16_tuned") >= 2)) && rgbnm_get_option("attn_v2"))
+    return rgbnm_launch_attn2_bwd(dtype, qkv, out, dout, lse, dqkv, B, N, heads, scale, st);
   if (dtype == DT_BF16) return attn_bwd_t<bf16, 7>(qkv, out, dout, lse, dqkv, B, N, heads, scale, st);
   if (dtype == DT_F32) return attn_bwd_t<float, 7>(qkv, out, dout, lse, dqkv, B, N, heads, scale, st);
   if (dtype == DT_F16) return attn_bwd_t<f16, 7>(qkv, out, dout, lse, dqkv, B, N, heads, scale, st);

@@ -1,4 +1,4 @@
-// bf16 attention, second generation (reference: MultiHeadAttention.forward, models/plainvit.py:445-464).
+// bf16 / fp16 attention, second generation (kernels are templates on the 16-bit element type E) (reference: MultiHeadAttention.forward, models/plainvit.py:445-464).
 // Same math and register orientation as attention.hip (S^T = K.Q^T, a lane owns one query / one key); what changes
 // is the memory system:
 //   * Q/K/V/dO tiles of one (image, head) arrive by LDS-DMA (global_load_lds, 16 B/lane) in their natural
@@ -27,7 +27,8 @@ constexpr int NTHREADS3 = NTHREADS + 64;   // attn3_bwd_kernel: 7 compute waves 
 // LDS-DMA one [N][64] bf16 matrix (row stride ld elements): 28 instructions of 1 KB (8 rows); wave w issues
 // w, w+7, w+14, w+21.  Rows >= N replicate row N-1 (finite data; their probabilities are masked to zero).
 // (All 28 from ONE wave, the DMA wave of attn3_bwd_kernel: tile128.h dma_matrix_all.)
-__device__ __forceinline__ void dma_matrix(const bf16* __restrict__ src, int ld, int N, unsigned char* dst, int w,
+template <typename E>
+__device__ __forceinline__ void dma_matrix(const E* __restrict__ src, int ld, int N, unsigned char* dst, int w,
                                            int lane) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -43,11 +44,12 @@ __device__ __forceinline__ void dma_matrix(const bf16* __restrict__ src, int ld,
 // compiler emits read - wait - MFMA with ONE fragment buffer: an exposed LDS latency per MFMA (36 of attn3_fwd's 80 MFMAs, 50 of
 // attn3_bwd's 196).  row_mma4: one accumulator, the four fragments requested together; row_pair_mma (tile128.h): two accumulators.
 // Same MFMA order per accumulator as the plain loops: same bits.
-__device__ __forceinline__ void row_mma4(f32x16& acc, const unsigned char* arr, unsigned rb, int t, const Frag<bf16> (&x)[4]) {
-  Frag<bf16> f[4];
+template <typename E>
+__device__ __forceinline__ void row_mma4(f32x16& acc, const unsigned char* arr, unsigned rb, int t, const Frag<E> (&x)[4]) {
+  Frag<E> f[4];
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-  for (int c = 0; c < 4; ++c) f[c] = rowfrag_x(arr, rb, t, c);
+  for (int c = 0; c < 4; ++c) f[c] = rowfrag_x<E>(arr, rb, t, c);
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int c = 0; c < 4; ++c) mma(acc, f[c], x[c]);
@@ -55,16 +57,17 @@ __device__ __forceinline__ void row_mma4(f32x16& acc, const unsigned char* arr, 
 }
 
 // MFMA operand with the head dim as reduction axis: lane <-> token row (32t + l31), 32-byte chunk c, half g.
-__device__ __forceinline__ Frag<bf16> rowfrag(const unsigned char* arr, int t, int l31, int c, int g, int fl) {
-  Frag<bf16> f;
-  f.v = *reinterpret_cast<const bf16x8*>(arr + (32 * t + l31) * ROWB + (((2 * c + g) ^ fl) << 4));
+template <typename E>
+__device__ __forceinline__ Frag<E> rowfrag(const unsigned char* arr, int t, int l31, int c, int g, int fl) {
+  Frag<E> f;
+  f.v = *reinterpret_cast<const typename Vec8<E>::type*>(arr + (32 * t + l31) * ROWB + (((2 * c + g) ^ fl) << 4));
   return f;
 }
 
 // Transposed operands (tokens as reduction axis) of tile T, fragment FI, for both 32-wide d tiles:
 // a0 = per-lane LDS address for (dt=0, rd=0); dt=1 flips address bit 6, rd=1 flips bit 5 and adds 8 rows.
-template <int T, int FI>
-__device__ __forceinline__ void tfrag2(unsigned a0, Frag<bf16>& f0, Frag<bf16>& f1) {
+template <int T, int FI, typename E>
+__device__ __forceinline__ void tfrag2(unsigned a0, Frag<E>& f0, Frag<E>& f1) {
   u32x2 x0, x1, y0, y1;
   const unsigned a00 = a0, a01 = (a0 ^ 32u) + 1024u, a10 = a0 ^ 64u, a11 = (a0 ^ 96u) + 1024u;
   asm volatile(
@@ -77,13 +80,13 @@ __device__ __forceinline__ void tfrag2(unsigned a0, Frag<bf16>& f0, Frag<bf16>& 
       : "v"(a00), "v"(a01), "v"(a10), "v"(a11), "i"(T * 4096 + FI * 2048)
       : "memory");
   __builtin_amdgcn_sched_barrier(0);
-  f0.v = pack8(x0, x1);
-  f1.v = pack8(y0, y1);
+  f0.v = pack8_as<E>(x0, x1);
+  f1.v = pack8_as<E>(y0, y1);
 }
 
 // tile128.h tfrag4 for TWO arrays (phase B of backward: dO^T and Q^T): 16 reads, one wait.
-template <int T>
-__device__ __forceinline__ void tfrag8(unsigned a0, unsigned b0, Frag<bf16> (&fa)[4], Frag<bf16> (&fb)[4]) {
+template <int T, typename E>
+__device__ __forceinline__ void tfrag8(unsigned a0, unsigned b0, Frag<E> (&fa)[4], Frag<E> (&fb)[4]) {
   u32x2 r0, r1, r2, r3, r4, r5, r6, r7, q0, q1, q2, q3, q4, q5, q6, q7;
   const unsigned a00 = a0, a01 = (a0 ^ 32u) + 1024u, a10 = a0 ^ 64u, a11 = (a0 ^ 96u) + 1024u;
   const unsigned b00 = b0, b01 = (b0 ^ 32u) + 1024u, b10 = b0 ^ 64u, b11 = (b0 ^ 96u) + 1024u;
@@ -111,11 +114,22 @@ __device__ __forceinline__ void tfrag8(unsigned a0, unsigned b0, Frag<bf16> (&fa
         "i"(T * 4096 + 2048)
       : "memory");
   __builtin_amdgcn_sched_barrier(0);
-  fa[0].v = pack8(r0, r1); fa[1].v = pack8(r2, r3); fa[2].v = pack8(r4, r5); fa[3].v = pack8(r6, r7);
-  fb[0].v = pack8(q0, q1); fb[1].v = pack8(q2, q3); fb[2].v = pack8(q4, q5); fb[3].v = pack8(q6, q7);
+  fa[0].v = pack8_as<E>(r0, r1); fa[1].v = pack8_as<E>(r2, r3); fa[2].v = pack8_as<E>(r4, r5); fa[3].v = pack8_as<E>(r6, r7);
+  fb[0].v = pack8_as<E>(q0, q1); fb[1].v = pack8_as<E>(q2, q3); fb[2].v = pack8_as<E>(q4, q5); fb[3].v = pack8_as<E>(q6, q7);
 }
 
 // ------------------------------------------------------------------------------------------------ forward
+// The forward's probabilities are exp2(s - max) in (0, 1] and are rounded to E for the P . V MFMAs.  In fp16 everything below 2^-14
+// would be a subnormal (absolute spacing 2^-24 instead of 11 significant bits) -- a one-hot row's other 195 keys.  So the fp16
+// kernels form 2^14 exp2(s - max) in (0, 2^14] (the shift rides in the exponent's constant: no instruction more): full precision
+// down to 2^-28, the row sum carries the same factor and the division by it cancels it; only lse takes it out again.  bf16 has
+// fp32's exponent range: shift 0, and the expressions fold to what they were.
+template <typename E> struct PShift { static constexpr float log2 = 0.f; };
+template <> struct PShift<f16> { static constexpr float log2 = 14.f; };      // lse_of: 2^-14 = 1 / 16384
+template <typename E> __device__ __forceinline__ float lse_of(float m, float scale, float sum) {
+  if constexpr (PShift<E>::log2 != 0.f) return m * scale + __logf(sum * (1.f / 16384.f));      // (exact: a power of two)
+  else return m * scale + __logf(sum);
+}
 template <int NTOK, int T> __device__ __forceinline__ bool tile_on(int N) {
   if constexpr (NTOK > 0) return T * 32 < NTOK;
   else return T * 32 < N;
@@ -127,8 +141,8 @@ template <int NTOK, int T> __device__ __forceinline__ bool tile_ragged(int N) {
 
 // NTOK > 0: compile-time token count (196): only the ragged last key tile carries a mask.  The exponent is one FMA +
 // exp2 (log2 e folded into the scale), and 1/sum multiplies the 32 output values instead of the 112 probabilities.
-template <int NTOK>
-__global__ __launch_bounds__(NTHREADS) void attn2_fwd_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out,
+template <int NTOK, typename E>
+__global__ __launch_bounds__(NTHREADS) void attn2_fwd_kernel(const E* __restrict__ qkv, E* __restrict__ out,
                                                              float* __restrict__ lse, int N_rt, int heads, float scale) {
   const int N = NTOK > 0 ? NTOK : N_rt;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -136,9 +150,9 @@ __global__ __launch_bounds__(NTHREADS) void attn2_fwd_kernel(const bf16* __restr
   unsigned char* Vs = smem + ARR;
   const int bh = blockIdx.x, b = bh / heads, h = bh % heads;
   const int inner = heads * HD, ld = 3 * inner;
-  const bf16* Q = qkv + (size_t)b * N * ld + h * HD;
-  const bf16* K = Q + inner;
-  const bf16* V = Q + 2 * inner;
+  const E* Q = qkv + (size_t)b * N * ld + h * HD;
+  const E* K = Q + inner;
+  const E* V = Q + 2 * inner;
   const Geo L = make_geo();
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
@@ -147,9 +161,9 @@ __global__ __launch_bounds__(NTHREADS) void attn2_fwd_kernel(const bf16* __restr
 
   const int q = w * 32 + L.l31;
   const int qc = q < N ? q : N - 1;
-  Frag<bf16> qf[4];
+  Frag<E> qf[4];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) qf[c] = load_frag<bf16>(Q + (size_t)qc * ld + c * 16 + L.g * 8);
+  for (int c = 0; c < 4; ++c) qf[c] = load_frag<E>(Q + (size_t)qc * ld + c * 16 + L.g * 8);
 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -166,7 +180,7 @@ __global__ __launch_bounds__(NTHREADS) void attn2_fwd_kernel(const bf16* __restr
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
-      for (int c = 0; c < 4; ++c) mma(acc, rowfrag(Ks, t, L.l31, c, L.g, L.fl), qf[c]);
+      for (int c = 0; c < 4; ++c) mma(acc, rowfrag<E>(Ks, t, L.l31, c, L.g, L.fl), qf[c]);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         float v = acc[r];
@@ -176,7 +190,7 @@ __global__ __launch_bounds__(NTHREADS) void attn2_fwd_kernel(const bf16* __restr
     }
   });
   m = fmaxf(m, __shfl_xor(m, 32, 64));
-  const float c2 = scale * 1.4426950408889634f, mc2 = m * c2;
+  const float c2 = scale * 1.4426950408889634f, mc2 = m * c2 - PShift<E>::log2;
   float sum = 0.f;
   f32x16 o[2];
 #pragma unroll
@@ -191,7 +205,7 @@ __global__ __launch_bounds__(NTHREADS) void attn2_fwd_kernel(const bf16* __restr
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
-      for (int c = 0; c < 4; ++c) mma(acc, rowfrag(Ks, t, L.l31, c, L.g, L.fl), qf[c]);
+      for (int c = 0; c < 4; ++c) mma(acc, rowfrag<E>(Ks, t, L.l31, c, L.g, L.fl), qf[c]);
       float pr[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -199,27 +213,27 @@ __global__ __launch_bounds__(NTHREADS) void attn2_fwd_kernel(const bf16* __restr
         if (tile_ragged<NTOK, t>(N) && t * 32 + acc_row(r, L.lane) >= N) pr[r] = 0.f;
         sum += pr[r];
       }
-      Frag<bf16> vv[4];
+      Frag<E> vv[4];
       tfrag4<t>(vt, vv);
-      Frag<bf16> pf = pfrag<bf16>(pr, 0);
+      Frag<E> pf = pfrag<E>(pr, 0);
       mma(o[0], vv[0], pf);
       mma(o[1], vv[1], pf);
-      pf = pfrag<bf16>(pr, 1);
+      pf = pfrag<E>(pr, 1);
       mma(o[0], vv[2], pf);
       mma(o[1], vv[3], pf);
     }
   });
   sum += __shfl_xor(sum, 32, 64);
   const float inv = 1.f / sum;
-  if (L.g == 0 && q < N) lse[(size_t)bh * N + q] = m * scale + __logf(sum);
+  if (L.g == 0 && q < N) lse[(size_t)bh * N + q] = lse_of<E>(m, scale, sum);
   if (q < N) {
-    bf16* orow = out + ((size_t)b * N + q) * inner + h * HD;
+    E* orow = out + ((size_t)b * N + q) * inner + h * HD;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
       for (int rq = 0; rq < 4; ++rq) {
         f32x4 v = {o[dt][rq * 4 + 0], o[dt][rq * 4 + 1], o[dt][rq * 4 + 2], o[dt][rq * 4 + 3]};
-        store4<bf16>(orow + dt * 32 + rq * 8 + L.g * 4, v * inv);
+        store4<E>(orow + dt * 32 + rq * 8 + L.g * 4, v * inv);
       }
   }
 }
@@ -231,9 +245,10 @@ __device__ unsigned long long g_attn_prof[768 * 8 * 8];
 #else
 #define APROF(i) do {} while (0)
 #endif
-__global__ __launch_bounds__(NTHREADS) void attn2_bwd_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ out,
-                                                             const bf16* __restrict__ dout,
-                                                             const float* __restrict__ lse, bf16* __restrict__ dqkv,
+template <typename E>
+__global__ __launch_bounds__(NTHREADS) void attn2_bwd_kernel(const E* __restrict__ qkv, const E* __restrict__ out,
+                                                             const E* __restrict__ dout,
+                                                             const float* __restrict__ lse, E* __restrict__ dqkv,
                                                              int N, int heads, float scale) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* Qs = smem;
@@ -244,11 +259,11 @@ __global__ __launch_bounds__(NTHREADS) void attn2_bwd_kernel(const bf16* __restr
   float* D_s = lse_s + NPAD;                                // [NPAD]
   const int bh = blockIdx.x, b = bh / heads, h = bh % heads;
   const int inner = heads * HD, ld = 3 * inner;
-  const bf16* Q = qkv + (size_t)b * N * ld + h * HD;
-  const bf16* K = Q + inner;
-  const bf16* V = Q + 2 * inner;
-  const bf16* O = out + (size_t)b * N * inner + h * HD;
-  const bf16* dO = dout + (size_t)b * N * inner + h * HD;
+  const E* Q = qkv + (size_t)b * N * ld + h * HD;
+  const E* K = Q + inner;
+  const E* V = Q + 2 * inner;
+  const E* O = out + (size_t)b * N * inner + h * HD;
+  const E* dO = dout + (size_t)b * N * inner + h * HD;
   const Geo L = make_geo();
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
@@ -262,9 +277,9 @@ __global__ __launch_bounds__(NTHREADS) void attn2_bwd_kernel(const bf16* __restr
   const int row = w * 32 + L.l31;            // this lane's query (phase A) / key (phase B)
   const int rc = row < N ? row : N - 1;
   // O fragment of this lane's query for D = rowsum(dO * O): issued before the wait so it overlaps the DMA
-  Frag<bf16> of[4];
+  Frag<E> of[4];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) of[c] = load_frag<bf16>(O + (size_t)rc * inner + c * 16 + L.g * 8);
+  for (int c = 0; c < 4; ++c) of[c] = load_frag<E>(O + (size_t)rc * inner + c * 16 + L.g * 8);
 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -273,12 +288,12 @@ __global__ __launch_bounds__(NTHREADS) void attn2_bwd_kernel(const bf16* __restr
 
   // ================= phase A: wave = 32 queries -> dQ, D =================
   if (active) {
-    Frag<bf16> qf[4], gf[4];
+    Frag<E> qf[4], gf[4];
     float Dq = 0.f;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      qf[c] = rowfrag(Qs, w, L.l31, c, L.g, L.fl);
-      gf[c] = rowfrag(Gs, w, L.l31, c, L.g, L.fl);
+      qf[c] = rowfrag<E>(Qs, w, L.l31, c, L.g, L.fl);
+      gf[c] = rowfrag<E>(Gs, w, L.l31, c, L.g, L.fl);
 #pragma unroll
       for (int e = 0; e < 8; ++e) Dq += (float)gf[c].v[e] * (float)of[c].v[e];
     }
@@ -300,8 +315,8 @@ __global__ __launch_bounds__(NTHREADS) void attn2_bwd_kernel(const bf16* __restr
         for (int r = 0; r < 16; ++r) { sa[r] = 0.f; da[r] = 0.f; }
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          mma(sa, rowfrag(Ks, t, L.l31, c, L.g, L.fl), qf[c]);
-          mma(da, rowfrag(Vs, t, L.l31, c, L.g, L.fl), gf[c]);
+          mma(sa, rowfrag<E>(Ks, t, L.l31, c, L.g, L.fl), qf[c]);
+          mma(da, rowfrag<E>(Vs, t, L.l31, c, L.g, L.fl), gf[c]);
         }
         float ds[16];
 #pragma unroll
@@ -310,25 +325,25 @@ __global__ __launch_bounds__(NTHREADS) void attn2_bwd_kernel(const bf16* __restr
           const float p = kk < N ? __expf(sa[r] * scale - lq) : 0.f;
           ds[r] = p * (da[r] - Dq) * scale;
         }
-        Frag<bf16> kk[4];
+        Frag<E> kk[4];
         tfrag4<t>(kt, kk);
-        Frag<bf16> sf = pfrag<bf16>(ds, 0);
+        Frag<E> sf = pfrag<E>(ds, 0);
         mma(dq[0], kk[0], sf);
         mma(dq[1], kk[1], sf);
-        sf = pfrag<bf16>(ds, 1);
+        sf = pfrag<E>(ds, 1);
         mma(dq[0], kk[2], sf);
         mma(dq[1], kk[3], sf);
       }
     });
     APROF(2);
     if (row < N) {
-      bf16* drow = dqkv + ((size_t)b * N + row) * ld + h * HD;
+      E* drow = dqkv + ((size_t)b * N + row) * ld + h * HD;
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
           f32x4 v = {dq[dt][rq * 4 + 0], dq[dt][rq * 4 + 1], dq[dt][rq * 4 + 2], dq[dt][rq * 4 + 3]};
-          store4<bf16>(drow + dt * 32 + rq * 8 + L.g * 4, v);
+          store4<E>(drow + dt * 32 + rq * 8 + L.g * 4, v);
         }
     }
   }
@@ -338,11 +353,11 @@ __global__ __launch_bounds__(NTHREADS) void attn2_bwd_kernel(const bf16* __restr
   if (!active) return;
 
   // ================= phase B: wave = 32 keys -> dK, dV =================
-  Frag<bf16> kf[4], vf[4];
+  Frag<E> kf[4], vf[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    kf[c] = rowfrag(Ks, w, L.l31, c, L.g, L.fl);
-    vf[c] = rowfrag(Vs, w, L.l31, c, L.g, L.fl);
+    kf[c] = rowfrag<E>(Ks, w, L.l31, c, L.g, L.fl);
+    vf[c] = rowfrag<E>(Vs, w, L.l31, c, L.g, L.fl);
   }
   f32x16 dk[2], dv[2];
 #pragma unroll
@@ -358,8 +373,8 @@ __global__ __launch_bounds__(NTHREADS) void attn2_bwd_kernel(const bf16* __restr
       for (int r = 0; r < 16; ++r) { sa[r] = 0.f; da[r] = 0.f; }
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        mma(sa, rowfrag(Qs, t, L.l31, c, L.g, L.fl), kf[c]);   // rows = queries, cols = keys
-        mma(da, rowfrag(Gs, t, L.l31, c, L.g, L.fl), vf[c]);
+        mma(sa, rowfrag<E>(Qs, t, L.l31, c, L.g, L.fl), kf[c]);   // rows = queries, cols = keys
+        mma(da, rowfrag<E>(Gs, t, L.l31, c, L.g, L.fl), vf[c]);
       }
       float pp[16], ds[16];
 #pragma unroll
@@ -369,34 +384,34 @@ __global__ __launch_bounds__(NTHREADS) void attn2_bwd_kernel(const bf16* __restr
         pp[r] = p;
         ds[r] = p * (da[r] - D_s[qq]) * scale;
       }
-      Frag<bf16> gg[4], qq4[4];
+      Frag<E> gg[4], qq4[4];
       tfrag8<t>(gt_, qt_, gg, qq4);
-      Frag<bf16> f = pfrag<bf16>(pp, 0);
+      Frag<E> f = pfrag<E>(pp, 0);
       mma(dv[0], gg[0], f);
       mma(dv[1], gg[1], f);
-      f = pfrag<bf16>(pp, 1);
+      f = pfrag<E>(pp, 1);
       mma(dv[0], gg[2], f);
       mma(dv[1], gg[3], f);
-      f = pfrag<bf16>(ds, 0);
+      f = pfrag<E>(ds, 0);
       mma(dk[0], qq4[0], f);
       mma(dk[1], qq4[1], f);
-      f = pfrag<bf16>(ds, 1);
+      f = pfrag<E>(ds, 1);
       mma(dk[0], qq4[2], f);
       mma(dk[1], qq4[3], f);
     }
   });
   APROF(5);
   if (row < N) {
-    bf16* krow = dqkv + ((size_t)b * N + row) * ld + inner + h * HD;
-    bf16* vrow = krow + inner;
+    E* krow = dqkv + ((size_t)b * N + row) * ld + inner + h * HD;
+    E* vrow = krow + inner;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
       for (int rq = 0; rq < 4; ++rq) {
         f32x4 a = {dk[dt][rq * 4 + 0], dk[dt][rq * 4 + 1], dk[dt][rq * 4 + 2], dk[dt][rq * 4 + 3]};
         f32x4 c = {dv[dt][rq * 4 + 0], dv[dt][rq * 4 + 1], dv[dt][rq * 4 + 2], dv[dt][rq * 4 + 3]};
-        store4<bf16>(krow + dt * 32 + rq * 8 + L.g * 4, a);
-        store4<bf16>(vrow + dt * 32 + rq * 8 + L.g * 4, c);
+        store4<E>(krow + dt * 32 + rq * 8 + L.g * 4, a);
+        store4<E>(vrow + dt * 32 + rq * 8 + L.g * 4, c);
       }
   }
 #ifdef ATTN_PROF
@@ -429,7 +444,8 @@ __global__ __launch_bounds__(NTHREADS) void attn2_bwd_kernel(const bf16* __restr
 // Gradient rows leave the persistent backward as full 128-byte lines, and not from the compute waves: parked in LDS and read back
 // by the DMA wave (tile128.h), which sends them on to global rows (column block of 64 at g0, row stride ld).  Sibling of
 // vit_chain_bwd.hip tiles_write, which has the constant token count and that file's store switches (gstore)
-__device__ __forceinline__ void tiles_write(const u32x4 (&v)[NTILE][4], bf16* __restrict__ g0, size_t ld, int N, int lane) {
+template <typename E>
+__device__ __forceinline__ void tiles_write(const u32x4 (&v)[NTILE][4], E* __restrict__ g0, size_t ld, int N, int lane) {
   const int rl = lane >> 3, seg = lane & 7;
 #pragma unroll
   for (int wv = 0; wv < NTILE; ++wv)
@@ -439,19 +455,20 @@ __device__ __forceinline__ void tiles_write(const u32x4 (&v)[NTILE][4], bf16* __
       if (row < N) *reinterpret_cast<u32x4*>(g0 + (size_t)row * ld + seg * 8) = v[wv][i];
     }
 }
-template <bool PRIVATE>
-__device__ __forceinline__ void tiles_to_global(const unsigned char* src, bf16* __restrict__ g0, size_t ld, int N, int lane) {
+template <bool PRIVATE, typename E>
+__device__ __forceinline__ void tiles_to_global(const unsigned char* src, E* __restrict__ g0, size_t ld, int N, int lane) {
   u32x4 v[NTILE][4];
   tiles_read<PRIVATE>(src, N, lane, v);
   tiles_write(v, g0, ld, N, lane);
 }
 
-template <int NTOK>
-__global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ out,
-                                                             const bf16* __restrict__ dout,
-                                                             const float* __restrict__ lse, bf16* __restrict__ dqkv,
+template <int NTOK, typename E>
+__global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const E* __restrict__ qkv, const E* __restrict__ out,
+                                                             const E* __restrict__ dout,
+                                                             const float* __restrict__ lse, E* __restrict__ dqkv,
                                                              int N_rt, int heads, int nbh, float scale) {
   const int N = NTOK > 0 ? NTOK : N_rt;
+  typedef typename Vec8<E>::type V8;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* Qs = smem;
   unsigned char* Ks = smem + ARR;
@@ -471,12 +488,12 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __rest
   const float c2 = scale * LOG2E;
 
   auto issue_kv = [&](int bh) {             // DMA wave only: 56 instructions
-    const bf16* Q = qkv + (size_t)(bh / heads) * N * ld + (bh % heads) * HD;
+    const E* Q = qkv + (size_t)(bh / heads) * N * ld + (bh % heads) * HD;
     dma_matrix_all(Q + inner, ld, N, Ks, L.lane);
     dma_matrix_all(Q + 2 * inner, ld, N, Vs, L.lane);
   };
   auto issue_qg = [&](int bh) {
-    const bf16* Q = qkv + (size_t)(bh / heads) * N * ld + (bh % heads) * HD;
+    const E* Q = qkv + (size_t)(bh / heads) * N * ld + (bh % heads) * HD;
     dma_matrix_all(Q, ld, N, Qs, L.lane);
     dma_matrix_all(dout + (size_t)(bh / heads) * N * inner + (bh % heads) * HD, inner, N, Gs, L.lane);
   };
@@ -541,7 +558,7 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __rest
     __builtin_amdgcn_s_barrier();                          // start
     for (; bh < nbh; bh += gridDim.x) {
       const int nxt = bh + gridDim.x;
-      bf16* g0 = dqkv + (size_t)(bh / heads) * N * ld + (bh % heads) * HD;
+      E* g0 = dqkv + (size_t)(bh / heads) * N * ld + (bh % heads) * HD;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // Q,dO landed (and the previous pair's stores are done)
       __builtin_amdgcn_s_barrier();                        // mid
       u32x4 tq[NTILE][4];
@@ -573,15 +590,15 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __rest
     APROF3(1);
 
     // ================= phase A: wave = 32 queries -> dQ, D =================
-    Frag<bf16> kf[4], vf[4];
+    Frag<E> kf[4], vf[4];
     if (active) {
       f32x16 dq[2];
-      Frag<bf16> qf[4], gf[4];
+      Frag<E> qf[4], gf[4];
       const int rl = L.lane >> 3, seg = L.lane & 7;
       // D = rowsum(dO * O) straight from the row-major pieces: 8 products per lane, 8 lanes per row
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const bf16x8 gv = __builtin_bit_cast(bf16x8, graw[i]), ov = __builtin_bit_cast(bf16x8, oraw[i]);
+        const V8 gv = __builtin_bit_cast(V8, graw[i]), ov = __builtin_bit_cast(V8, oraw[i]);
         float d = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) d += (float)gv[e] * (float)ov[e];
@@ -596,14 +613,14 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __rest
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
       for (int c = 0; c < 4; ++c)
-        qf[c].v = *reinterpret_cast<const bf16x8*>(stg + L.l31 * STG_PITCH + (2 * c + L.g) * 16);
+        qf[c].v = *reinterpret_cast<const V8*>(stg + L.l31 * STG_PITCH + (2 * c + L.g) * 16);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
       for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4*>(stg + (i * 8 + rl) * STG_PITCH + seg * 16) = graw[i];
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
       for (int c = 0; c < 4; ++c)
-        gf[c].v = *reinterpret_cast<const bf16x8*>(stg + L.l31 * STG_PITCH + (2 * c + L.g) * 16);
+        gf[c].v = *reinterpret_cast<const V8*>(stg + L.l31 * STG_PITCH + (2 * c + L.g) * 16);
       const float Dq = D_s[row];
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       const float lq2 = lq * LOG2E;
@@ -633,21 +650,21 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __rest
             for (int r = 0; r < 16; ++r)
               if (t * 32 + acc_row(r, L.lane) >= N) ds[r] = 0.f;
           }
-          Frag<bf16> kk[4];
+          Frag<E> kk[4];
           tfrag4<t>(kt, kk);
-          Frag<bf16> sf = pfrag<bf16>(ds, 0);
+          Frag<E> sf = pfrag<E>(ds, 0);
           mma(dq[0], kk[0], sf);
           mma(dq[1], kk[1], sf);
-          sf = pfrag<bf16>(ds, 1);
+          sf = pfrag<E>(ds, 1);
           mma(dq[0], kk[2], sf);
           mma(dq[1], kk[3], sf);
         }
       });
-      tile_park_private(stg, dq, scale, L);
+      tile_park_private<E>(stg, dq, scale, L);
 #pragma unroll
       for (int c = 0; c < 4; ++c) {          // own K,V rows for phase B, before the arrays are refilled
-        kf[c] = rowfrag_x(Ks, rb, w, c);
-        vf[c] = rowfrag_x(Vs, rb, w, c);
+        kf[c] = rowfrag_x<E>(Ks, rb, w, c);
+        vf[c] = rowfrag_x<E>(Vs, rb, w, c);
       }
     }
     APROF3(2);
@@ -691,19 +708,19 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __rest
             for (int r = 0; r < 16; ++r)
               if (t * 32 + acc_row(r, L.lane) >= N) { pp[r] = 0.f; ds[r] = 0.f; }
           }
-          Frag<bf16> gg[4];
+          Frag<E> gg[4];
           tfrag4<t>(gt_, gg);
-          Frag<bf16> f = pfrag<bf16>(pp, 0);
+          Frag<E> f = pfrag<E>(pp, 0);
           mma(dv[0], gg[0], f);
           mma(dv[1], gg[1], f);
-          f = pfrag<bf16>(pp, 1);
+          f = pfrag<E>(pp, 1);
           mma(dv[0], gg[2], f);
           mma(dv[1], gg[3], f);
           tfrag4<t>(qt_, gg);
-          f = pfrag<bf16>(ds, 0);
+          f = pfrag<E>(ds, 0);
           mma(dk[0], gg[0], f);
           mma(dk[1], gg[1], f);
-          f = pfrag<bf16>(ds, 1);
+          f = pfrag<E>(ds, 1);
           mma(dk[0], gg[2], f);
           mma(dk[1], gg[3], f);
         }
@@ -713,12 +730,12 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __rest
       // they fly during the two parks and the two barriers instead of after them; the O rows follow after the dV park (all 13
       // loads here, or any of them earlier, and the 256-register budget spills)
       if (nxt < nbh) load_own_qg(nxt);
-      tile_park_private(stg, dk, scale, L);
+      tile_park_private<E>(stg, dk, scale, L);
       APROF3(5);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();          // end: every wave is done with Q,dO, D_s, L2_s; dK tiles parked
       APROF3(6);
-      tile_park_rows(Gs, w, dv, 1.0f);
+      tile_park_rows<E>(Gs, w, dv, 1.0f);
     } else {
       if (nxt < nbh) load_own_qg(nxt);
       __builtin_amdgcn_s_barrier();          // end
@@ -739,11 +756,12 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_bwd_kernel(const bf16* __rest
 // per pair: "K,V of this pair have landed" / "every compute wave has left the previous pair (its buffer is free)".
 // A compute wave's own Q rows come as 4 coalesced loads issued a pair ahead and are turned into fragments through its
 // private LDS tile; the same tile takes the output rows, which leave as whole 128-byte lines.
-template <int NTOK>
-__global__ __launch_bounds__(NTHREADS3) void attn3_fwd_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out,
+template <int NTOK, typename E>
+__global__ __launch_bounds__(NTHREADS3) void attn3_fwd_kernel(const E* __restrict__ qkv, E* __restrict__ out,
                                                              float* __restrict__ lse, int N_rt, int heads, int nbh,
                                                              float scale) {
   const int N = NTOK > 0 ? NTOK : N_rt;
+  typedef typename Vec8<E>::type V8;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int inner = heads * HD, ld = 3 * inner;
   const Geo L = make_geo();
@@ -753,7 +771,7 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_fwd_kernel(const bf16* __rest
 
   if (w == NTILE) {                                     // ---- DMA wave
     auto issue_kv = [&](int p, int buf) {
-      const bf16* Q = qkv + (size_t)(p / heads) * N * ld + (p % heads) * HD;
+      const E* Q = qkv + (size_t)(p / heads) * N * ld + (p % heads) * HD;
       dma_matrix_all(Q + inner, ld, N, smem + buf * 2 * ARR, L.lane);
       dma_matrix_all(Q + 2 * inner, ld, N, smem + buf * 2 * ARR + ARR, L.lane);
     };
@@ -795,7 +813,7 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_fwd_kernel(const bf16* __rest
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // own Q rows (and the previous pair's stores)
     __builtin_amdgcn_s_barrier();
     if (!active) continue;
-    Frag<bf16> qf[4];
+    Frag<E> qf[4];
     {
       const int rl = L.lane >> 3, seg = L.lane & 7;
 #pragma unroll
@@ -803,7 +821,7 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_fwd_kernel(const bf16* __rest
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
       for (int c = 0; c < 4; ++c)
-        qf[c].v = *reinterpret_cast<const bf16x8*>(stg + L.l31 * STG_PITCH + (2 * c + L.g) * 16);
+        qf[c].v = *reinterpret_cast<const V8*>(stg + L.l31 * STG_PITCH + (2 * c + L.g) * 16);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     if (nxt < nbh) load_own(nxt);
@@ -827,7 +845,7 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_fwd_kernel(const bf16* __rest
       }
     });
     m = fmaxf(m, __shfl_xor(m, 32, 64));
-    const float mc2 = m * c2;
+    const float mc2 = m * c2 - PShift<E>::log2;
     float sum = 0.f;
     f32x16 o[2];
 #pragma unroll
@@ -849,21 +867,21 @@ __global__ __launch_bounds__(NTHREADS3) void attn3_fwd_kernel(const bf16* __rest
           if (tile_ragged<NTOK, t>(N) && t * 32 + acc_row(r, L.lane) >= N) pr[r] = 0.f;
           sum += pr[r];
         }
-        Frag<bf16> vv[4];
+        Frag<E> vv[4];
         tfrag4<t>(vt, vv);
-        Frag<bf16> pf = pfrag<bf16>(pr, 0);
+        Frag<E> pf = pfrag<E>(pr, 0);
         mma(o[0], vv[0], pf);
         mma(o[1], vv[1], pf);
-        pf = pfrag<bf16>(pr, 1);
+        pf = pfrag<E>(pr, 1);
         mma(o[0], vv[2], pf);
         mma(o[1], vv[3], pf);
       }
     });
     sum += __shfl_xor(sum, 32, 64);
     const float inv = 1.f / sum;
-    if (L.g == 0 && q < N) lse[(size_t)bh * N + q] = m * scale + __logf(sum);
+    if (L.g == 0 && q < N) lse[(size_t)bh * N + q] = lse_of<E>(m, scale, sum);
     // output rows: private tile -> 4 stores of whole lines
-    tile_park_private(stg, o, inv, L);
+    tile_park_private<E>(stg, o, inv, L);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     {
       const int lane_ = lane_id_here();
@@ -888,14 +906,12 @@ constexpr int SMEM_FWD3 = 4 * ARR + NTILE * STG_WAVE;
 constexpr int SMEM_BWD = 4 * ARR + 2 * NPAD * (int)sizeof(float);
 constexpr int SMEM_BWD3 = SMEM_BWD + NTILE * STG_WAVE;      // + the per-wave store tiles of attn3_bwd_kernel
 
-}  // namespace
-
-int rgbnm_launch_attn2_fwd(const void* qkv, void* out, float* lse, int B, int N, int heads, float scale,
-                           hipStream_t st) {
+template <typename E>
+int launch_attn2_fwd(const void* qkv, void* out, float* lse, int B, int N, int heads, float scale, hipStream_t st) {
   static DevOnce attr;
   if (attr.need()) {
-    if (hipFuncSetAttribute((const void*)attn2_fwd_kernel<196>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_FWD) != hipSuccess ||
-        hipFuncSetAttribute((const void*)attn2_fwd_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_FWD) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)(attn2_fwd_kernel<196, E>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_FWD) != hipSuccess ||
+        hipFuncSetAttribute((const void*)(attn2_fwd_kernel<0, E>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_FWD) != hipSuccess)
       return RGBNM_ELAUNCH;
     attr.done();
   }
@@ -904,34 +920,35 @@ int rgbnm_launch_attn2_fwd(const void* qkv, void* out, float* lse, int B, int N,
   if (rgbnm_get_option("attn_persist") && B * heads >= 256) {
     static DevOnce attr3;
     if (attr3.need()) {
-      if (hipFuncSetAttribute((const void*)attn3_fwd_kernel<196>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_FWD3) != hipSuccess ||
-          hipFuncSetAttribute((const void*)attn3_fwd_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_FWD3) != hipSuccess)
+      if (hipFuncSetAttribute((const void*)(attn3_fwd_kernel<196, E>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_FWD3) != hipSuccess ||
+          hipFuncSetAttribute((const void*)(attn3_fwd_kernel<0, E>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_FWD3) != hipSuccess)
         return RGBNM_ELAUNCH;
       attr3.done();
     }
     const int nbh = B * heads;
     if (N == 196)
-      hipLaunchKernelGGL(attn3_fwd_kernel<196>, dim3(256), dim3(NTHREADS3), SMEM_FWD3, st, (const bf16*)qkv, (bf16*)out, lse, N,
+      hipLaunchKernelGGL((attn3_fwd_kernel<196, E>), dim3(256), dim3(NTHREADS3), SMEM_FWD3, st, (const E*)qkv, (E*)out, lse, N,
                          heads, nbh, scale);
     else
-      hipLaunchKernelGGL(attn3_fwd_kernel<0>, dim3(256), dim3(NTHREADS3), SMEM_FWD3, st, (const bf16*)qkv, (bf16*)out, lse, N,
+      hipLaunchKernelGGL((attn3_fwd_kernel<0, E>), dim3(256), dim3(NTHREADS3), SMEM_FWD3, st, (const E*)qkv, (E*)out, lse, N,
                          heads, nbh, scale);
   } else if (N == 196)
-    hipLaunchKernelGGL(attn2_fwd_kernel<196>, dim3(B * heads), dim3(NTHREADS), SMEM_FWD, st, (const bf16*)qkv, (bf16*)out,
+    hipLaunchKernelGGL((attn2_fwd_kernel<196, E>), dim3(B * heads), dim3(NTHREADS), SMEM_FWD, st, (const E*)qkv, (E*)out,
                        lse, N, heads, scale);
   else
-    hipLaunchKernelGGL(attn2_fwd_kernel<0>, dim3(B * heads), dim3(NTHREADS), SMEM_FWD, st, (const bf16*)qkv, (bf16*)out, lse,
+    hipLaunchKernelGGL((attn2_fwd_kernel<0, E>), dim3(B * heads), dim3(NTHREADS), SMEM_FWD, st, (const E*)qkv, (E*)out, lse,
                        N, heads, scale);
   rgbnm_trace_end(slot, st);
   LAUNCH_CHECK();
   return RGBNM_OK;
 }
 
-int rgbnm_launch_attn2_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B,
-                           int N, int heads, float scale, hipStream_t st) {
+template <typename E>
+int launch_attn2_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int N, int heads,
+                     float scale, hipStream_t st) {
   static DevOnce attr;
   if (attr.need()) {
-    if (hipFuncSetAttribute((const void*)attn2_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BWD) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)attn2_bwd_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BWD) != hipSuccess)
       return RGBNM_ELAUNCH;
     attr.done();
   }
@@ -940,25 +957,42 @@ int rgbnm_launch_attn2_bwd(const void* qkv, const void* out, const void* dout, c
   if (rgbnm_get_option("attn_persist")) {
     static DevOnce attr3;
     if (attr3.need()) {
-      if (hipFuncSetAttribute((const void*)attn3_bwd_kernel<196>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BWD3) != hipSuccess ||
-          hipFuncSetAttribute((const void*)attn3_bwd_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BWD3) != hipSuccess)
+      if (hipFuncSetAttribute((const void*)(attn3_bwd_kernel<196, E>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BWD3) != hipSuccess ||
+          hipFuncSetAttribute((const void*)(attn3_bwd_kernel<0, E>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BWD3) != hipSuccess)
         return RGBNM_ELAUNCH;
       attr3.done();
     }
     const int nbh = B * heads;
     if (N == 196)
-      hipLaunchKernelGGL(attn3_bwd_kernel<196>, dim3(nbh < 256 ? nbh : 256), dim3(NTHREADS3), SMEM_BWD3, st, (const bf16*)qkv,
-                         (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, N, heads, nbh, scale);
+      hipLaunchKernelGGL((attn3_bwd_kernel<196, E>), dim3(nbh < 256 ? nbh : 256), dim3(NTHREADS3), SMEM_BWD3, st, (const E*)qkv,
+                         (const E*)out, (const E*)dout, lse, (E*)dqkv, N, heads, nbh, scale);
     else
-      hipLaunchKernelGGL(attn3_bwd_kernel<0>, dim3(nbh < 256 ? nbh : 256), dim3(NTHREADS3), SMEM_BWD3, st, (const bf16*)qkv,
-                         (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, N, heads, nbh, scale);
+      hipLaunchKernelGGL((attn3_bwd_kernel<0, E>), dim3(nbh < 256 ? nbh : 256), dim3(NTHREADS3), SMEM_BWD3, st, (const E*)qkv,
+                         (const E*)out, (const E*)dout, lse, (E*)dqkv, N, heads, nbh, scale);
   } else {
-    hipLaunchKernelGGL(attn2_bwd_kernel, dim3(B * heads), dim3(NTHREADS), SMEM_BWD, st, (const bf16*)qkv, (const bf16*)out,
-                       (const bf16*)dout, lse, (bf16*)dqkv, N, heads, scale);
+    hipLaunchKernelGGL(attn2_bwd_kernel<E>, dim3(B * heads), dim3(NTHREADS), SMEM_BWD, st, (const E*)qkv, (const E*)out,
+                       (const E*)dout, lse, (E*)dqkv, N, heads, scale);
   }
   rgbnm_trace_end(slot, st);
   LAUNCH_CHECK();
   return RGBNM_OK;
+}
+
+}  // namespace
+
+// dtype: DT_BF16 or DT_F16 (the same byte layout: the two instantiations differ in the MFMA and the conversions only)
+int rgbnm_launch_attn2_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int N, int heads, float scale,
+                           hipStream_t st) {
+  if (dtype == DT_F16) return launch_attn2_fwd<f16>(qkv, out, lse, B, N, heads, scale, st);
+  if (dtype != DT_BF16) return RGBNM_EINVAL;
+  return launch_attn2_fwd<bf16>(qkv, out, lse, B, N, heads, scale, st);
+}
+
+int rgbnm_launch_attn2_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B,
+                           int N, int heads, float scale, hipStream_t st) {
+  if (dtype == DT_F16) return launch_attn2_bwd<f16>(qkv, out, dout, lse, dqkv, B, N, heads, scale, st);
+  if (dtype != DT_BF16) return RGBNM_EINVAL;
+  return launch_attn2_bwd<bf16>(qkv, out, dout, lse, dqkv, B, N, heads, scale, st);
 }
 
 #ifdef ATTN_PROF

@@ -1,5 +1,5 @@
 // Row-panel NT GEMM for the N = 192 Linear layers with a long reduction (fc2: K = 768 + bias + residual; the dX
-// GEMMs of fc1 and qkv: K = 768 / 576), bf16 -- and, for the plain epilogues, fp16 --:   C[M,192] = epi(A[M,K] . W[192,K]^T).
+// GEMMs of fc1 and qkv: K = 768 / 576), bf16 or fp16:   C[M,192] = epi(A[M,K] . W[192,K]^T).
 // These read 58-77 MB of activations to produce 19 MB: HBM-read bound.  One 448-thread workgroup per CU owns ONE
 // contiguous panel of rows (M / 256 = 196 tokens at B = 256: exactly one workgroup per CU, a single balanced round;
 // 7 waves x 32 rows, the last 28 rows are padding) and all 192 output columns, and streams the reduction through a
@@ -53,19 +53,24 @@ static bool use_kp8(int M, int N, int) {
 }
 
 // x = A . W^T + bias + R ; y = LayerNorm(x): fc2 (+ the next block's LN1) and proj (+ LN2) in one launch each.
-int rgbnm_launch_nt_kpipe_res_ln(const void* A, int lda, const void* W, int ldw, const float* bias, const void* R,
+int rgbnm_launch_nt_kpipe_res_ln(int dtype, const void* A, int lda, const void* W, int ldw, const float* bias, const void* R,
                                  int ldr, void* x, int ldc, const float* gamma, const float* beta, void* y, int ldy,
                                  float* mean, float* rstd, float eps, int M, int N, int K, hipStream_t st) {
-  return kp7::launch_res_ln(A, lda, W, ldw, bias, R, ldr, x, ldc, gamma, beta, y, ldy, mean, rstd, eps, M, N, K, st);
+  if (dtype == DT_F16) return kp7::launch_res_ln<f16>(A, lda, W, ldw, bias, R, ldr, x, ldc, gamma, beta, y, ldy, mean, rstd, eps, M, N, K, st);
+  if (dtype != DT_BF16) return 1;
+  return kp7::launch_res_ln<bf16>(A, lda, W, ldw, bias, R, ldr, x, ldc, gamma, beta, y, ldy, mean, rstd, eps, M, N, K, st);
 }
 
 // dx = [dres +] LayerNorm'(A . W^T): the dX GEMM of fc1 / qkv with the LayerNorm backward fused into its epilogue
 // (saves writing and re-reading the [M,192] gradient and one launch).  part: [npanels][2][192] partial dgamma/dbeta;
 // *npanels_out tells the caller how many slices to reduce.  Returns 1 when the shape is not eligible.
-int rgbnm_launch_nt_kpipe_lnbwd(const void* A, int lda, const void* W, int ldw, const void* X, int ldx,
+int rgbnm_launch_nt_kpipe_lnbwd(int dtype, const void* A, int lda, const void* W, int ldw, const void* X, int ldx,
                                 const float* gamma, const float* mean, const float* rstd, const void* dres, int ldr,
                                 void* dx, int ldc, float* part, int* npanels_out, int M, int N, int K, hipStream_t st) {
-  return kp7::launch_lnbwd(A, lda, W, ldw, X, ldx, gamma, mean, rstd, dres, ldr, dx, ldc, part, npanels_out, M, N, K, st);
+  if (dtype == DT_F16)
+    return kp7::launch_lnbwd<f16>(A, lda, W, ldw, X, ldx, gamma, mean, rstd, dres, ldr, dx, ldc, part, npanels_out, M, N, K, st);
+  if (dtype != DT_BF16) return 1;
+  return kp7::launch_lnbwd<bf16>(A, lda, W, ldw, X, ldx, gamma, mean, rstd, dres, ldr, dx, ldc, part, npanels_out, M, N, K, st);
 }
 
 // returns 1 when the shape is not eligible (caller falls back to the tile-per-workgroup kernel)

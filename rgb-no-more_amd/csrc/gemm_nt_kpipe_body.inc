@@ -40,11 +40,12 @@ constexpr int LN_E = 192, LN_GROUPS = NTHREADS / 8, LN_ITERS = BM / LN_GROUPS;  
 // EPI_LNBWD uses the same 8-lane layout through ln_bwd_rows.h, the one implementation it shares with mlp_bwd_kernel (48 more
 // accumulator registers for dgamma / dbeta than the 16-lane form it replaced; measured equal on the whole step, A/B on one box)
 constexpr int RED_OFF = (BM * CP * 2 + 1023) / 1024 * 1024;   // column-reduction scratch behind the staging tile
-typedef rgbnm::LnBwdRows<NTHREADS, BM> LnBwd;                  // EPI_LNBWD: 8 lanes per row, shared with mlp_bwd_kernel (ln_bwd_rows.h)
+template <typename E> using LnBwdT = rgbnm::LnBwdRows<NTHREADS, BM, E>;
+typedef LnBwdT<bf16> LnBwd;                  // EPI_LNBWD: 8 lanes per row, shared with mlp_bwd_kernel (ln_bwd_rows.h)
 constexpr bool LN_OK = BM * CP * 2 <= RED_OFF && RED_OFF + LnBwd::RED_BYTES <= NSTAGE * STAGE;   // LN scratch fits the ring (not kp8)
 
 // (the 16-bit operand pointers are typed bf16 for their 2-byte address arithmetic; the plain epilogues read and write them as the
-// kernel's element type E, bf16 or fp16 -- the LayerNorm epilogues are bf16 only)
+// kernel's element type E, bf16 or fp16, and so do the LayerNorm epilogues)
 struct KpArgs {
   const bf16* A; const bf16* W; bf16* C; const float* bias; const bf16* R;
   int lda, ldw, ldc, ldr;
@@ -128,7 +129,6 @@ __device__ __forceinline__ void ktile_mma(const unsigned char* sA, const unsigne
 
 template <typename E, int EPI>
 __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
-  static_assert(std::is_same<E, bf16>::value || (EPI != EPI_RES_LN && EPI != EPI_LNBWD), "LayerNorm epilogues: bf16 only");
   constexpr bool IS_BF16 = std::is_same<E, bf16>::value;      // the GELU table is a bf16 image: other types take the arithmetic GELU
   using V8 = typename Vec8<E>::type;
   using V4 = typename Vec4<E>::type;
@@ -167,19 +167,19 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
   }
   // EPI_RES_LN: residual rows in the 8-lanes-per-row layout of its LayerNorm pass (gamma / beta: after the loop)
   const int l8 = tid & 7, grp = tid >> 3;
-  bf16x8 lr[LN_ITERS][3];
+  V8 lr[LN_ITERS][3];
   if (EPI == EPI_RES_LN) {
 #pragma unroll
     for (int it = 0; it < LN_ITERS; ++it) {
       const int row = it * LN_GROUPS + grp, rr = m0 + (row < rows ? row : rows - 1);
 #pragma unroll
       for (int v = 0; v < 3; ++v)
-        lr[it][v] = *reinterpret_cast<const bf16x8*>(p.R + (size_t)rr * p.ldr + v * 64 + l8 * 8);
+        lr[it][v] = *reinterpret_cast<const V8*>(p.R + (size_t)rr * p.ldr + v * 64 + l8 * 8);
     }
   }
   // EPI_LNBWD: the LayerNorm input rows and their statistics, also ahead of the loop
-  LnBwd lnb;
-  if (EPI == EPI_LNBWD) lnb.request_x(p.X, p.ldx, p.mean, p.rstd, m0, rows, tid);
+  LnBwdT<E> lnb;
+  if (EPI == EPI_LNBWD) lnb.request_x(reinterpret_cast<const E*>(p.X), p.ldx, p.mean, p.rstd, m0, rows, tid);
   if (BIAS_LDS && w < BN / 64) {
     if (p.bias) __builtin_amdgcn_global_load_lds((glb_ptr)(p.bias + n0 + 64 * w + lane), (lds_ptr)(Bs + 64 * w), 4, 0, 0);
     else Bs[64 * w + lane] = 0.f;
@@ -266,7 +266,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
 
   // ---- pass 1: lane = token (32 w + l31), register quad = 4 consecutive features (+ bias) -> bf16 staging tile
   E* Cs = reinterpret_cast<E*>(smem);
-  bf16* Cs16 = reinterpret_cast<bf16*>(smem);      // the same tile for the (bf16 only) LayerNorm epilogues
 #pragma unroll
   for (int b = 0; b < 6; ++b)
 #pragma unroll
@@ -288,7 +287,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
         bt[v][hf] = *reinterpret_cast<const f32x4*>(p.beta + v * 64 + l8 * 8 + hf * 4);
       }
   }
-  if (EPI == EPI_LNBWD) lnb.request_res(p.R, p.ldr, m0, rows, tid);   // residual gradient rows: requested now (the accumulators are dead)
+  if (EPI == EPI_LNBWD) lnb.request_res(reinterpret_cast<const E*>(p.R), p.ldr, m0, rows, tid);   // residual gradient rows: requested now (the accumulators are dead)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   if (EPI == EPI_RES_LN) {
@@ -303,15 +302,15 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
         float s0 = 0.f, s1 = 0.f;
 #pragma unroll
         for (int v = 0; v < 3; ++v) {
-          const bf16* cp = Cs16 + row * CP + v * 64 + l8 * 8;           // 8-byte aligned (CP * 2 = 392)
-          const bf16x4 c0 = *reinterpret_cast<const bf16x4*>(cp), c1 = *reinterpret_cast<const bf16x4*>(cp + 4);
-          bf16x8 xb;
+          const E* cp = Cs + row * CP + v * 64 + l8 * 8;           // 8-byte aligned (CP * 2 = 392)
+          const V4 c0 = *reinterpret_cast<const V4*>(cp), c1 = *reinterpret_cast<const V4*>(cp + 4);
+          V8 xb;
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
-            xb[i] = (bf16)((float)(i < 4 ? c0[i & 3] : c1[i & 3]) + (float)lr[it][v][i]);   // the residual stream is bf16 ...
+            xb[i] = from_f32<E>((float)(i < 4 ? c0[i & 3] : c1[i & 3]) + (float)lr[it][v][i]);   // the residual stream is 16-bit ...
             xv[v][i] = (float)xb[i];                                                       // ... and LayerNorm sees those values
           }
-          *reinterpret_cast<bf16x8*>(p.C + (size_t)(m0 + row) * p.ldc + v * 64 + l8 * 8) = xb;
+          *reinterpret_cast<V8*>(p.C + (size_t)(m0 + row) * p.ldc + v * 64 + l8 * 8) = xb;
           s0 += xv[v][0] + xv[v][1] + xv[v][2] + xv[v][3];
           s1 += xv[v][4] + xv[v][5] + xv[v][6] + xv[v][7];
         }
@@ -328,11 +327,11 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
         const float rs = rsqrtf(__builtin_fmaf(group8_pair_sum(q0, q1), 1.f / LN_E, p.eps));
 #pragma unroll
         for (int v = 0; v < 3; ++v) {
-          bf16x8 ob;
+          V8 ob;
 #pragma unroll
           for (int i = 0; i < 8; ++i)
-            ob[i] = (bf16)__builtin_fmaf((xv[v][i] - mu) * rs, gm[v][i >> 2][i & 3], bt[v][i >> 2][i & 3]);
-          *reinterpret_cast<bf16x8*>(p.Y2 + (size_t)(m0 + row) * p.ldy2 + v * 64 + l8 * 8) = ob;
+            ob[i] = from_f32<E>(__builtin_fmaf((xv[v][i] - mu) * rs, gm[v][i >> 2][i & 3], bt[v][i >> 2][i & 3]));
+          *reinterpret_cast<V8*>(p.Y2 + (size_t)(m0 + row) * p.ldy2 + v * 64 + l8 * 8) = ob;
         }
         if (l8 == 0) {
           p.mean_o[m0 + row] = mu;
@@ -344,7 +343,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kpipe_kernel(KpArgs p) {
   }
   if (EPI == EPI_LNBWD) {
     // ---- LayerNorm backward on the staged rows + panel sums of dgamma / dbeta (ln_bwd_rows.h)
-    lnb.run(Cs16, CP, p.C, p.ldc, p.gamma, p.R != nullptr, p.part, panel, reinterpret_cast<float*>(smem + RED_OFF), m0, rows, tid);
+    lnb.run(Cs, CP, reinterpret_cast<E*>(p.C), p.ldc, p.gamma, p.R != nullptr, p.part, panel, reinterpret_cast<float*>(smem + RED_OFF), m0, rows, tid);
     return;
   }
   // ---- pass 2: valid rows x 24 vectors of 8 features, coalesced 384-byte rows
@@ -653,6 +652,7 @@ int launch(const KpArgs& p, hipStream_t st) {
 constexpr int WG_PER_CU = NWAVES <= 4 ? 2 : 1;
 
 // x = A . W^T + bias + R ; y = LayerNorm(x): fc2 (+ the next block's LN1) and proj (+ LN2) in one launch each.
+template <typename E>
 int launch_res_ln(const void* A, int lda, const void* W, int ldw, const float* bias, const void* R,
                                  int ldr, void* x, int ldc, const float* gamma, const float* beta, void* y, int ldy,
                                  float* mean, float* rstd, float eps, int M, int N, int K, hipStream_t st) {
@@ -670,7 +670,7 @@ int launch_res_ln(const void* A, int lda, const void* W, int ldw, const float* b
   p.npanels = cdiv(M, rows);
   const double mn = (double)M * N;
   const int slot = rgbnm_trace_begin(TR_NT, 2.0 * mn * K, ((double)M * K + (double)N * K) * 2.0 + mn * 2.0 * 3.0, st);
-  const int rc = launch<bf16, EPI_RES_LN>(p, st);
+  const int rc = launch<E, EPI_RES_LN>(p, st);
   rgbnm_trace_end(slot, st);
   return rc;
 }
@@ -678,6 +678,7 @@ int launch_res_ln(const void* A, int lda, const void* W, int ldw, const float* b
 // dx = [dres +] LayerNorm'(A . W^T): the dX GEMM of fc1 / qkv with the LayerNorm backward fused into its epilogue
 // (saves writing and re-reading the [M,192] gradient and one launch).  part: [npanels][2][192] partial dgamma/dbeta;
 // *npanels_out tells the caller how many slices to reduce.  Returns 1 when the shape is not eligible.
+template <typename E>
 int launch_lnbwd(const void* A, int lda, const void* W, int ldw, const void* X, int ldx,
                                 const float* gamma, const float* mean, const float* rstd, const void* dres, int ldr,
                                 void* dx, int ldc, float* part, int* npanels_out, int M, int N, int K, hipStream_t st) {
@@ -696,7 +697,7 @@ int launch_lnbwd(const void* A, int lda, const void* W, int ldw, const void* X, 
   *npanels_out = p.npanels;
   const double mn = (double)M * N;
   const int slot = rgbnm_trace_begin(TR_NT, 2.0 * mn * K, ((double)M * K + (double)N * K) * 2.0 + mn * 2.0 * (dres ? 3.0 : 2.0), st);
-  const int rc = launch<bf16, EPI_LNBWD>(p, st);
+  const int rc = launch<E, EPI_LNBWD>(p, st);
   rgbnm_trace_end(slot, st);
   return rc;
 }

@@ -25,10 +25,10 @@ int rgbnm_tn_defer_flush(hipStream_t st);
 int rgbnm_launch_tn_pipe(int dtype, const void* dY, int ldy, const void* X, int ldx, float* part, float* bpart, int M, int No,
                          int Ki, int* S_out, hipStream_t st, int smax = 0);
 
-// bf16 attention with LDS-DMA tiles and transpose reads (attention_v2.hip)
-int rgbnm_launch_attn2_fwd(const void* qkv, void* out, float* lse, int B, int N, int heads, float scale,
+// bf16 / fp16 attention with LDS-DMA tiles and transpose reads (attention_v2.hip; dtype: DT_BF16 or DT_F16)
+int rgbnm_launch_attn2_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int N, int heads, float scale,
                            hipStream_t st);
-int rgbnm_launch_attn2_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B,
+int rgbnm_launch_attn2_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B,
                            int N, int heads, float scale, hipStream_t st);
 
 // per-kernel HIP-event tracing (vit.hip); tags: 1 gemm_nt, 2 gemm_tn, 3 attention fwd, 4 attention bwd, 5 / 6 the one-launch encoder
@@ -41,13 +41,13 @@ int rgbnm_launch_nt_wres(int dtype, int epi, const void* A, int lda, const void*
 // Row-panel N = 192 bf16 / fp16 NT GEMM with a pipelined reduction (gemm_nt_kpipe.hip).  Same return convention.
 int rgbnm_launch_nt_kpipe(int dtype, int epi, const void* A, int lda, const void* W, int ldw, void* C, int ldc, const float* bias,
                           const void* R, int ldr, void* C2, int ldc2, int M, int N, int K, hipStream_t st);
-// Linear + bias + residual + LayerNorm of the result in one launch (gemm_nt_kpipe.hip); 1 = not eligible.
-int rgbnm_launch_nt_kpipe_res_ln(const void* A, int lda, const void* W, int ldw, const float* bias, const void* R,
+// Linear + bias + residual + LayerNorm of the result in one launch (gemm_nt_kpipe.hip; dtype: DT_BF16 or DT_F16); 1 = not eligible.
+int rgbnm_launch_nt_kpipe_res_ln(int dtype, const void* A, int lda, const void* W, int ldw, const float* bias, const void* R,
                                  int ldr, void* x, int ldc, const float* gamma, const float* beta, void* y, int ldy,
                                  float* mean, float* rstd, float eps, int M, int N, int K, hipStream_t st);
 // Fused FeedForwardBlock forward (mlp_fused.hip): x_out = x_mid + fc2(gelu(fc1(xn2))) [+ LayerNorm of x_out], saving
 // gelu(u) -> G and gelu'(u) -> GP for the backward; 1 = not eligible (E != 192, hidden != 768, small M).
-int rgbnm_launch_mlp_fwd(const void* X, int ldx, const void* W1, const float* b1, const void* W2, const float* b2,
+int rgbnm_launch_mlp_fwd(int dtype, const void* X, int ldx, const void* W1, const float* b1, const void* W2, const float* b2,
                          const void* R, int ldr, void* G, void* GP, int ldg, void* Y, int ldy, const float* gamma,
                          const float* beta, void* Y2, int ldy2, float* mean, float* rstd, float eps, int M, int E, int H,
                          hipStream_t st);
@@ -57,11 +57,11 @@ int rgbnm_launch_nt_small(int dtype, int epi, const void* A, int lda, const void
                           const void* R, int ldr, int c_f32, int M, int N, int K, hipStream_t st);
 // The backward of the same block's data path in one launch (mlp_fused.hip): du = (dy . W2) * gelu'(u) -> DU (for the dW1 GEMM),
 // dx = dy + LayerNorm'(du . W1) -> DX, panel partial sums of dgamma / dbeta -> part [npanels][2][192]; 1 = not eligible.
-int rgbnm_launch_mlp_bwd(const void* DY, int lddy, const void* W2T, const void* W1T, const void* GP, int ldg, void* DU, int ldu,
+int rgbnm_launch_mlp_bwd(int dtype, const void* DY, int lddy, const void* W2T, const void* W1T, const void* GP, int ldg, void* DU, int ldu,
                          const void* X, int ldx, const float* gamma, const float* mean, const float* rstd, void* DX, int lddx,
                          float* part, int* npanels_out, int M, int E, int H, hipStream_t st);
-// fc1 / qkv dX GEMM with the LayerNorm backward fused into the epilogue (gemm_nt_kpipe.hip); 1 = not eligible.
-int rgbnm_launch_nt_kpipe_lnbwd(const void* A, int lda, const void* W, int ldw, const void* X, int ldx,
+// fc1 / qkv dX GEMM with the LayerNorm backward fused into the epilogue (gemm_nt_kpipe.hip; bf16 / fp16); 1 = not eligible.
+int rgbnm_launch_nt_kpipe_lnbwd(int dtype, const void* A, int lda, const void* W, int ldw, const void* X, int ldx,
                                 const float* gamma, const float* mean, const float* rstd, const void* dres, int ldr,
                                 void* dx, int ldc, float* part, int* npanels_out, int M, int N, int K, hipStream_t st);
 // Batched reduction of split partials (reduce.hip): out[map(i)] (+)= sum_s part[s * stride + i], i < n.

@@ -36,6 +36,10 @@ __device__ __forceinline__ bf16x8 pack8(u32x2 lo, u32x2 hi) {
   u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
   return __builtin_bit_cast(bf16x8, v);
 }
+template <typename E> __device__ __forceinline__ typename Vec8<E>::type pack8_as(u32x2 lo, u32x2 hi) {   // the same bits as 8 x E
+  u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
+  return __builtin_bit_cast(typename Vec8<E>::type, v);
+}
 __device__ __forceinline__ bf16x8 as_bf16x8(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
 
 // ds_read_b64_tr_b16 through the compiler's builtin: an ordinary DS load to the scheduler (it can be requested ahead and waited

@@ -17,18 +17,20 @@
 
 namespace rgbnm {
 
-template <int NT, int BMROWS>
+template <int NT, int BMROWS, typename T = bf16>      // T: the 16-bit element type of the rows (bf16 or fp16; statistics, gamma and the sums are fp32)
 struct LnBwdRows {
+  typedef typename Vec8<T>::type V8;
+  typedef typename Vec4<T>::type V4;
   static constexpr int E = 192;
   static constexpr int GROUPS = NT / 8, ITERS = BMROWS / GROUPS;
   static_assert(BMROWS % GROUPS == 0, "row groups");
   static constexpr int RED_BYTES = GROUPS * (E + 4) * 4;
 
-  bf16x8 lx[ITERS][3], lr[ITERS][3];
+  V8 lx[ITERS][3], lr[ITERS][3];
   float mu[ITERS], rs[ITERS];
 
   // operand rows of the LayerNorm input and their statistics (request these as early as registers allow)
-  __device__ __forceinline__ void request_x(const bf16* __restrict__ X, int ldx, const float* __restrict__ mean,
+  __device__ __forceinline__ void request_x(const T* __restrict__ X, int ldx, const float* __restrict__ mean,
                                             const float* __restrict__ rstd, int m0, int rows, int tid) {
     const int l8 = tid & 7, grp = tid >> 3;
 #pragma unroll
@@ -37,24 +39,24 @@ struct LnBwdRows {
       mu[it] = mean[rr];
       rs[it] = rstd[rr];
 #pragma unroll
-      for (int v = 0; v < 3; ++v) lx[it][v] = *reinterpret_cast<const bf16x8*>(X + (size_t)rr * ldx + v * 64 + l8 * 8);
+      for (int v = 0; v < 3; ++v) lx[it][v] = *reinterpret_cast<const V8*>(X + (size_t)rr * ldx + v * 64 + l8 * 8);
     }
   }
   // residual-gradient rows (R may be null: no residual branch)
-  __device__ __forceinline__ void request_res(const bf16* __restrict__ R, int ldr, int m0, int rows, int tid) {
+  __device__ __forceinline__ void request_res(const T* __restrict__ R, int ldr, int m0, int rows, int tid) {
     const int l8 = tid & 7, grp = tid >> 3;
     if (!R) return;
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
       const int row = it * GROUPS + grp, rr = m0 + (row < rows ? row : rows - 1);
 #pragma unroll
-      for (int v = 0; v < 3; ++v) lr[it][v] = *reinterpret_cast<const bf16x8*>(R + (size_t)rr * ldr + v * 64 + l8 * 8);
+      for (int v = 0; v < 3; ++v) lr[it][v] = *reinterpret_cast<const V8*>(R + (size_t)rr * ldr + v * 64 + l8 * 8);
     }
   }
 
   // Cs: the staged dy rows (bf16, pitch cp elements, 8-byte aligned pieces); every thread of the NT calls this after the
   // barrier that completes the tile.  red: RED_BYTES of LDS scratch that does not overlap Cs.  Contains two __syncthreads.
-  __device__ __forceinline__ void run(const bf16* Cs, int cp, bf16* __restrict__ C, int ldc, const float* __restrict__ gamma,
+  __device__ __forceinline__ void run(const T* Cs, int cp, T* __restrict__ C, int ldc, const float* __restrict__ gamma,
                                       bool has_res, float* __restrict__ part, int panel, float* red, int m0, int rows, int tid) {
     run<false>(Cs, cp, C, ldc, gamma, has_res, part, panel, red, m0, rows, tid, nullptr, [](int) { __syncthreads(); });
   }
@@ -64,9 +66,9 @@ struct LnBwdRows {
   // (iii) SPLIT2: the column sums of a pass are taken by 384 threads -- two per column, even / odd row groups, combined by
   // one lane exchange -- instead of 192 walking all 56 groups (fp32 sums in a different order than the other callers').
   template <bool SPLIT2 = false, typename BarF>
-  __device__ __forceinline__ void run(const bf16* Cs, int cp, bf16* __restrict__ C, int ldc, const float* __restrict__ gamma,
+  __device__ __forceinline__ void run(const T* Cs, int cp, T* __restrict__ C, int ldc, const float* __restrict__ gamma,
                                       bool has_res, float* __restrict__ part, int panel, float* red, int m0, int rows, int tid,
-                                      bf16* wb, BarF&& bar) {
+                                      T* wb, BarF&& bar) {
     const int l8 = tid & 7, grp = tid >> 3;
     f32x4 gm[3][2];
 #pragma unroll
@@ -86,8 +88,8 @@ struct LnBwdRows {
         float s1a = 0.f, s1b = 0.f, s2a = 0.f, s2b = 0.f;
 #pragma unroll
         for (int v = 0; v < 3; ++v) {
-          const bf16* cptr = Cs + row * cp + v * 64 + l8 * 8;
-          const bf16x4 c0 = *reinterpret_cast<const bf16x4*>(cptr), c1 = *reinterpret_cast<const bf16x4*>(cptr + 4);
+          const T* cptr = Cs + row * cp + v * 64 + l8 * 8;
+          const V4 c0 = *reinterpret_cast<const V4*>(cptr), c1 = *reinterpret_cast<const V4*>(cptr + 4);
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             ln_bwd_acc((float)c0[i], (float)lx[it][v][i], mu[it], rs[it], gm[v][0][i], xh[v][i], gv[v][i], s1a, s2a, dg[v][i],
@@ -100,15 +102,15 @@ struct LnBwdRows {
         asm volatile("" : "+v"(c1), "+v"(c2));       // (products: never contracted into the subtractions of ln_bwd_dx, whatever the caller)
 #pragma unroll
         for (int v = 0; v < 3; ++v) {
-          bf16x8 ob;
+          V8 ob;
 #pragma unroll
           for (int i = 0; i < 8; ++i)
-            ob[i] = (bf16)ln_bwd_dx(rs[it], gv[v][i], c1, xh[v][i], c2, has_res ? (float)lr[it][v][i] : 0.f);
-          *reinterpret_cast<bf16x8*>(C + (size_t)(m0 + row) * ldc + v * 64 + l8 * 8) = ob;
+            ob[i] = from_f32<T>(ln_bwd_dx(rs[it], gv[v][i], c1, xh[v][i], c2, has_res ? (float)lr[it][v][i] : 0.f));
+          *reinterpret_cast<V8*>(C + (size_t)(m0 + row) * ldc + v * 64 + l8 * 8) = ob;
           if (wb) {
-            bf16* wp = wb + row * cp + v * 64 + l8 * 8;                 // 8-byte aligned pieces, as they were read
-            *reinterpret_cast<bf16x4*>(wp) = bf16x4{ob[0], ob[1], ob[2], ob[3]};
-            *reinterpret_cast<bf16x4*>(wp + 4) = bf16x4{ob[4], ob[5], ob[6], ob[7]};
+            T* wp = wb + row * cp + v * 64 + l8 * 8;                 // 8-byte aligned pieces, as they were read
+            *reinterpret_cast<V4*>(wp) = V4{ob[0], ob[1], ob[2], ob[3]};
+            *reinterpret_cast<V4*>(wp + 4) = V4{ob[4], ob[5], ob[6], ob[7]};
           }
         }
       }

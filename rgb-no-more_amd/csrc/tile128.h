@@ -53,9 +53,10 @@ template <> struct TileLoop<0> {
 // folded into one offset rb = l31 * ROWB + ((g ^ fswz(l31)) << 4): chunk c of the row is at rb ^ (c << 5) because
 // (2c + g) ^ fl = 2c ^ (g ^ fl).  rb is re-derived (made opaque) at the start of each phase so the per-array, per-chunk addresses
 // are not kept in registers -- or spilled -- across the whole persistent loop.
-__device__ __forceinline__ Frag<bf16> rowfrag_x(const unsigned char* arr, unsigned rb, int t, int c) {
-  Frag<bf16> f;
-  f.v = *reinterpret_cast<const bf16x8*>(arr + (rb ^ (unsigned)(c << 5)) + t * 32 * ROWB);
+template <typename E = bf16>
+__device__ __forceinline__ Frag<E> rowfrag_x(const unsigned char* arr, unsigned rb, int t, int c) {
+  Frag<E> f;
+  f.v = *reinterpret_cast<const typename Vec8<E>::type*>(arr + (rb ^ (unsigned)(c << 5)) + t * 32 * ROWB);
   return f;
 }
 
@@ -64,24 +65,25 @@ __device__ __forceinline__ Frag<bf16> rowfrag_x(const unsigned char* arr, unsign
 // on (into registers an earlier MFMA has read -- the sixteen the transposed fragments of the tile's second half take afterwards).
 // Left alone the compiler emits read - wait - MFMA eight times with ONE fragment buffer: an exposed LDS latency per MFMA (50 of
 // attn3_bwd's 196; 336 per block and wave of the chain backward).  Same MFMA order per accumulator as the plain loop: same bits.
+template <typename E>
 __device__ __forceinline__ void row_pair_mma(f32x16& sa, f32x16& da, const unsigned char* arrS, const unsigned char* arrD, unsigned rb,
-                                             int t, const Frag<bf16> (&xs)[4], const Frag<bf16> (&xd)[4]) {
+                                             int t, const Frag<E> (&xs)[4], const Frag<E> (&xd)[4]) {
 #define T128_SB __builtin_amdgcn_sched_barrier(0)
-  Frag<bf16> fs[4], fd[4];
+  Frag<E> fs[4], fd[4];
   T128_SB;
-  fs[0] = rowfrag_x(arrS, rb, t, 0);
-  fd[0] = rowfrag_x(arrD, rb, t, 0);
-  fs[1] = rowfrag_x(arrS, rb, t, 1);
-  fd[1] = rowfrag_x(arrD, rb, t, 1);
+  fs[0] = rowfrag_x<E>(arrS, rb, t, 0);
+  fd[0] = rowfrag_x<E>(arrD, rb, t, 0);
+  fs[1] = rowfrag_x<E>(arrS, rb, t, 1);
+  fd[1] = rowfrag_x<E>(arrD, rb, t, 1);
   T128_SB;
   mma(sa, fs[0], xs[0]); T128_SB;
-  fs[2] = rowfrag_x(arrS, rb, t, 2); T128_SB;
+  fs[2] = rowfrag_x<E>(arrS, rb, t, 2); T128_SB;
   mma(da, fd[0], xd[0]); T128_SB;
-  fd[2] = rowfrag_x(arrD, rb, t, 2); T128_SB;
+  fd[2] = rowfrag_x<E>(arrD, rb, t, 2); T128_SB;
   mma(sa, fs[1], xs[1]); T128_SB;
-  fs[3] = rowfrag_x(arrS, rb, t, 3); T128_SB;
+  fs[3] = rowfrag_x<E>(arrS, rb, t, 3); T128_SB;
   mma(da, fd[1], xd[1]); T128_SB;
-  fd[3] = rowfrag_x(arrD, rb, t, 3); T128_SB;
+  fd[3] = rowfrag_x<E>(arrD, rb, t, 3); T128_SB;
   mma(sa, fs[2], xs[2]);
   mma(da, fd[2], xd[2]);
   mma(sa, fs[3], xs[3]);
@@ -93,8 +95,8 @@ __device__ __forceinline__ void row_pair_mma(f32x16& sa, f32x16& da, const unsig
 // Transposed operands (tokens as reduction axis) of tile T of ONE array, both fragments (FI = 0, 1) x both 32-wide d tiles:
 // 8 transpose reads, one wait.  a0 = array address + Geo::tr0, the per-lane address for (fi=0, dt=0, rd=0); dt=1 flips address
 // bit 6, rd=1 flips bit 5 and adds 8 rows, fi=1 adds 16 rows.
-template <int T>
-__device__ __forceinline__ void tfrag4(unsigned a0, Frag<bf16> (&f)[4]) {
+template <int T, typename E>
+__device__ __forceinline__ void tfrag4(unsigned a0, Frag<E> (&f)[4]) {
   u32x2 r0, r1, r2, r3, r4, r5, r6, r7;
   const unsigned a00 = a0, a01 = (a0 ^ 32u) + 1024u, a10 = a0 ^ 64u, a11 = (a0 ^ 96u) + 1024u;
   asm volatile(
@@ -111,20 +113,20 @@ __device__ __forceinline__ void tfrag4(unsigned a0, Frag<bf16> (&f)[4]) {
       : "v"(a00), "v"(a01), "v"(a10), "v"(a11), "i"(T * 4096), "i"(T * 4096 + 2048)
       : "memory");
   __builtin_amdgcn_sched_barrier(0);
-  f[0].v = pack8(r0, r1);   // fi=0, dt=0
-  f[1].v = pack8(r2, r3);   // fi=0, dt=1
-  f[2].v = pack8(r4, r5);   // fi=1, dt=0
-  f[3].v = pack8(r6, r7);   // fi=1, dt=1
+  f[0].v = pack8_as<E>(r0, r1);   // fi=0, dt=0
+  f[1].v = pack8_as<E>(r2, r3);   // fi=0, dt=1
+  f[2].v = pack8_as<E>(r4, r5);   // fi=1, dt=0
+  f[3].v = pack8_as<E>(r6, r7);   // fi=1, dt=1
 }
 // The same through the compiler's builtin (lds_common.h tr_read): the reads can be requested ahead and waited for where they are
 // used; the asm form above waits on the spot.  a0 = Geo::tr0 relative to smem
-template <int T>
-__device__ __forceinline__ void tfrag4_b(const unsigned char* smem, unsigned a0, Frag<bf16> (&f)[4]) {
+template <int T, typename E>
+__device__ __forceinline__ void tfrag4_b(const unsigned char* smem, unsigned a0, Frag<E> (&f)[4]) {
   const unsigned a00 = a0, a01 = (a0 ^ 32u) + 1024u, a10 = a0 ^ 64u, a11 = (a0 ^ 96u) + 1024u;
-  f[0].v = pack8(tr_read(smem, a00 + T * 4096), tr_read(smem, a01 + T * 4096));
-  f[1].v = pack8(tr_read(smem, a10 + T * 4096), tr_read(smem, a11 + T * 4096));
-  f[2].v = pack8(tr_read(smem, a00 + T * 4096 + 2048), tr_read(smem, a01 + T * 4096 + 2048));
-  f[3].v = pack8(tr_read(smem, a10 + T * 4096 + 2048), tr_read(smem, a11 + T * 4096 + 2048));
+  f[0].v = pack8_as<E>(tr_read(smem, a00 + T * 4096), tr_read(smem, a01 + T * 4096));
+  f[1].v = pack8_as<E>(tr_read(smem, a10 + T * 4096), tr_read(smem, a11 + T * 4096));
+  f[2].v = pack8_as<E>(tr_read(smem, a00 + T * 4096 + 2048), tr_read(smem, a01 + T * 4096 + 2048));
+  f[3].v = pack8_as<E>(tr_read(smem, a10 + T * 4096 + 2048), tr_read(smem, a11 + T * 4096 + 2048));
 }
 
 // Between a wave's accesses to ITS OWN LDS tile (write the fragment layout, read row pieces back, overwrite with the next tile) no
@@ -135,7 +137,8 @@ __device__ __forceinline__ void own_tile_fence() { asm volatile("" ::: "memory")
 
 // LDS-DMA of one [N][64] bf16 matrix (row stride ld elements) into an array by ONE wave: 28 instructions of 1 KB (8 rows).
 // Rows >= N replicate row N - 1 (finite data; their probabilities are masked to zero).
-__device__ __forceinline__ void dma_matrix_all(const bf16* __restrict__ src, int ld, int N, unsigned char* dst, int lane) {
+template <typename E>
+__device__ __forceinline__ void dma_matrix_all(const E* __restrict__ src, int ld, int N, unsigned char* dst, int lane) {
 #pragma unroll 4
   for (int i = 0; i < 28; ++i) {
     const int row = 8 * i + (lane >> 3), pc = lane & 7;
@@ -154,16 +157,18 @@ __device__ __forceinline__ void dma_matrix_all(const bf16* __restrict__ src, int
 // and the DMA wave reads them back as 16 B per lane, 8 lanes per row, and issues every global store (whole lines).
 constexpr int STG_PITCH = 144;
 constexpr int STG_WAVE = 32 * STG_PITCH;       // 4.5 KB per wave
+template <typename E = bf16>
 __device__ __forceinline__ void tile_park_private(unsigned char* stg, const f32x16 (&acc)[2], float mul, const Geo& L) {
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
     for (int rq = 0; rq < 4; ++rq) {
       f32x4 v = {acc[dt][rq * 4 + 0], acc[dt][rq * 4 + 1], acc[dt][rq * 4 + 2], acc[dt][rq * 4 + 3]};
-      store4<bf16>(reinterpret_cast<bf16*>(stg + L.l31 * STG_PITCH) + dt * 32 + rq * 8 + L.g * 4, v * mul);
+      store4<E>(reinterpret_cast<E*>(stg + L.l31 * STG_PITCH) + dt * 32 + rq * 8 + L.g * 4, v * mul);
     }
 }
 // rows w*32 .. w*32+31 of a 128-byte-pitch array; 16-byte chunk c of row r sits at chunk c ^ (r & 7)
+template <typename E = bf16>
 __device__ __forceinline__ void tile_park_rows(unsigned char* arr, int w, const f32x16 (&acc)[2], float mul) {
   // one opaque base offset, chunk selected by XOR with a constant: the 8 swizzled addresses are loop invariants that the
   // compiler otherwise hoists to the kernel prologue and then SPILLS (each reload a serialised scratch round trip)
@@ -174,7 +179,7 @@ __device__ __forceinline__ void tile_park_rows(unsigned char* arr, int w, const 
 #pragma unroll
     for (int rq = 0; rq < 4; ++rq) {
       f32x4 v = {acc[dt][rq * 4 + 0], acc[dt][rq * 4 + 1], acc[dt][rq * 4 + 2], acc[dt][rq * 4 + 3]};
-      store4<bf16>(reinterpret_cast<bf16*>(arr + (off0 ^ (unsigned)((dt * 4 + rq) << 4))), v * mul);
+      store4<E>(reinterpret_cast<E*>(arr + (off0 ^ (unsigned)((dt * 4 + rq) << 4))), v * mul);
     }
 }
 // DMA wave: the parked tiles of the NT compute waves whose rows start below N (private tiles, or rows of an array) -> registers;

@@ -113,15 +113,18 @@ const char* rgbnm_strerror(int code) {
   }
 }
 
+// The per-block fused kernels (LayerNorm-chained epilogues, fused MLP) take bf16, and fp16 from f16_tuned level 2 on (rgbnm.h)
+static bool fused_dtype(int dt) { return dt == RGBNM_DT_BF16 || (dt == RGBNM_DT_F16 && rgbnm_get_option("f16_tuned") >= 2); }
+
 // dx = dres + LayerNorm'(A . W^T) in one launch (gemm_nt_kpipe.hip) + two jobs for the batched reduction.
 // false: not eligible (fp32, E != 192, small M, option ln_fuse = 0) -> the caller runs GEMM and LayerNorm separately.
 static bool fused_dx_lnbwd(int dt, const void* A, int lda, const void* Wt, int ldw, const void* x, const float* gamma,
                            const float* mean, const float* rstd, const void* dres, void* dx, float* dgamma,
                            float* dbeta, int M, int E, int K, void* ws, size_t ws_bytes, hipStream_t st) {
-  if (dt != RGBNM_DT_BF16 || E != 192 || !rgbnm_get_option("ln_fuse") || !rgbnm_get_option("nt_kpipe")) return false;
+  if (!fused_dtype(dt) || E != 192 || !rgbnm_get_option("ln_fuse") || !rgbnm_get_option("nt_kpipe")) return false;
   if (ws_bytes < (size_t)cdiv(M, cdiv(M, 512)) * 2 * E * sizeof(float)) return false;    // up to 512 row panels
   int npanels = 0;
-  const int rc = rgbnm_launch_nt_kpipe_lnbwd(A, lda, Wt, ldw, x, E, gamma, mean, rstd, dres, E, dx, E, (float*)ws,
+  const int rc = rgbnm_launch_nt_kpipe_lnbwd(dt, A, lda, Wt, ldw, x, E, gamma, mean, rstd, dres, E, dx, E, (float*)ws,
                                              &npanels, M, E, K, st);
   if (rc != RGBNM_OK) return false;
   RgbnmReduceJob j;
@@ -137,10 +140,10 @@ static bool fused_dx_lnbwd(int dt, const void* A, int lda, const void* Wt, int l
 static bool fused_mlp_bwd(int dt, const void* dy, const void* w2t, const void* w1t, const void* gp, void* du, const void* x,
                           const float* gamma, const float* mean, const float* rstd, void* dx, float* dgamma, float* dbeta,
                           int M, int E, void* ws, size_t ws_bytes, hipStream_t st) {
-  if (dt != RGBNM_DT_BF16 || E != 192 || !rgbnm_get_option("mlp_bwd") || !rgbnm_get_option("ln_fuse")) return false;
+  if (!fused_dtype(dt) || E != 192 || !rgbnm_get_option("mlp_bwd") || !rgbnm_get_option("ln_fuse")) return false;
   if (ws_bytes < (size_t)cdiv(M, cdiv(M, 256)) * 2 * E * sizeof(float)) return false;
   int npanels = 0;
-  const int rc = rgbnm_launch_mlp_bwd(dy, E, w2t, w1t, gp, 4 * E, du, 4 * E, x, E, gamma, mean, rstd, dx, E, (float*)ws,
+  const int rc = rgbnm_launch_mlp_bwd(dt, dy, E, w2t, w1t, gp, 4 * E, du, 4 * E, x, E, gamma, mean, rstd, dx, E, (float*)ws,
                                       &npanels, M, E, 4 * E, st);
   if (rc != RGBNM_OK) return false;
   RgbnmReduceJob j;
@@ -180,7 +183,7 @@ size_t rgbnm_vit_workspace_ex(const rgbnm_vit_cfg* c, int n_classes) {
 
 int rgbnm_vit_ln_chain(const rgbnm_vit_cfg* c) {
   if (!c) return 0;
-  return c->dtype == RGBNM_DT_BF16 && c->E == 192 && c->B * c->N >= 8192 && rgbnm_get_option("ln_fuse") &&
+  return fused_dtype(c->dtype) && c->E == 192 && c->B * c->N >= 8192 && rgbnm_get_option("ln_fuse") &&
          rgbnm_get_option("nt_kpipe");
 }
 
@@ -196,7 +199,7 @@ int rgbnm_vit_block_fwd_chain(const rgbnm_vit_cfg* c, const rgbnm_block_params* 
                     3 * I, E, 0, st));
   TRY(rgbnm_attention_fwd(dt, a->qkv, a->attn, a->lse, c->B, c->N, c->heads, c->attn_scale, st));
   // x_mid = x_in + proj(attn) ; xn2 = LN2(x_mid): one launch when chaining is on
-  if (!chain || rgbnm_launch_nt_kpipe_res_ln(a->attn, I, p->wproj, I, p->bproj, a->x_in, E, a->x_mid, E, p->ln2_g,
+  if (!chain || rgbnm_launch_nt_kpipe_res_ln(dt, a->attn, I, p->wproj, I, p->bproj, a->x_in, E, a->x_mid, E, p->ln2_g,
                                              p->ln2_b, a->xn2, E, a->mean2, a->rstd2, c->ln_eps, M, E, I,
                                              (hipStream_t)st) != RGBNM_OK) {
     TRY(rgbnm_gemm_nt(dt, RGBNM_EPI_RES, a->attn, I, p->wproj, I, a->x_mid, E, p->bproj, a->x_in, E, 0, 0, 0, 0, M, E,
@@ -206,8 +209,8 @@ int rgbnm_vit_block_fwd_chain(const rgbnm_vit_cfg* c, const rgbnm_block_params* 
   const bool to_next = chain && next_p && next_a;
   if (to_next && next_a->x_in != a->x_out) return RGBNM_EINVAL;
   // the whole FeedForwardBlock (+ residual [+ the next block's LN1]) in one launch when eligible (mlp_fused.hip)
-  if (dt == RGBNM_DT_BF16 && rgbnm_get_option("mlp_fuse")) {
-    const int rc = rgbnm_launch_mlp_fwd(a->xn2, E, p->w1, p->b1, p->w2, p->b2, a->x_mid, E, a->gl, a->u, 4 * E, a->x_out, E,
+  if (fused_dtype(dt) && rgbnm_get_option("mlp_fuse")) {
+    const int rc = rgbnm_launch_mlp_fwd(dt, a->xn2, E, p->w1, p->b1, p->w2, p->b2, a->x_mid, E, a->gl, a->u, 4 * E, a->x_out, E,
                                         to_next ? next_p->ln1_g : nullptr, to_next ? next_p->ln1_b : nullptr,
                                         to_next ? next_a->xn1 : nullptr, E, to_next ? next_a->mean1 : nullptr,
                                         to_next ? next_a->rstd1 : nullptr, c->ln_eps, M, E, 4 * E, (hipStream_t)st);
@@ -217,7 +220,7 @@ int rgbnm_vit_block_fwd_chain(const rgbnm_vit_cfg* c, const rgbnm_block_params* 
                     E, 0, st));
   // x_out = x_mid + fc2(gl) [; next block's xn1 = LN1(x_out)]
   if (to_next) {
-    const int rc = rgbnm_launch_nt_kpipe_res_ln(a->gl, 4 * E, p->w2, 4 * E, p->b2, a->x_mid, E, a->x_out, E,
+    const int rc = rgbnm_launch_nt_kpipe_res_ln(dt, a->gl, 4 * E, p->w2, 4 * E, p->b2, a->x_mid, E, a->x_out, E,
                                                 next_p->ln1_g, next_p->ln1_b, next_a->xn1, E, next_a->mean1,
                                                 next_a->rstd1, c->ln_eps, M, E, 4 * E, (hipStream_t)st);
     if (rc != RGBNM_OK) return rc < 0 ? rc : RGBNM_EINVAL;    // rgbnm_vit_ln_chain() promised eligibility

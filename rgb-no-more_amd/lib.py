@@ -248,7 +248,12 @@ def check(rc, what=""):
 
 
 def set_option(name, value):
-    """Set a runtime option of the library (include/rgbnm.h, rgbnm_set_option), e.g. set_option("f16_tuned", 1)."""
+    """Set a runtime option of the library (include/rgbnm.h, rgbnm_set_option), e.g. set_option("f16_tuned", 1).
+
+    "f16_tuned" has levels: 0 (default) fp16 on the generic kernels; 1 fp16 on the tuned plain GEMMs (small-M, weight-resident,
+    row-panel, pipelined / grouped weight gradients); 2 level 1 plus the per-block fused kernels in fp16 -- attention v2, the fused
+    MLP forward / backward and the LayerNorm-chained row-panel epilogues -- under the shape conditions of bf16.  The one-launch
+    encoder and the GELU table stay bf16 only."""
     check(lib().rgbnm_set_option(name.encode(), int(value)), f"option {name}")
 
 

@@ -163,6 +163,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "captured_step.json"))
+    ap.add_argument("--f16-tuned", type=int, default=1, choices=(1, 2), help="level of the option f16_tuned for the fp16 configuration")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
     assert a.rounds >= 6 and a.steps > LR_WARMUP
@@ -172,10 +173,10 @@ def main():
     lib = L.lib()
     tuned0 = lib.rgbnm_get_option(b"f16_tuned")
     res = {"arch": "vitti", "batch": a.batch, "steps_per_block": a.steps, "warmup": a.warmup, "rounds": a.rounds,
-           "source_hash": L.source_hash(),
+           "source_hash": L.source_hash(), "f16_tuned": a.f16_tuned,
            "loops": {"a": "HIP graph of forward -> loss -> backward, then host warm-up / CosineAnnealingLR and FusedClipAdamWWD.step",
                      "b": "CapturedTrainStep.replay(): one HIP graph with the tail and the device schedule inside"}}
-    for name, cdt, scaler, tuned in (("bf16", torch.bfloat16, False, tuned0), ("fp16_tuned_device_scaler", torch.float16, True, 1)):
+    for name, cdt, scaler, tuned in (("bf16", torch.bfloat16, False, tuned0), ("fp16_tuned_device_scaler", torch.float16, True, a.f16_tuned)):
         lib.rgbnm_set_option(b"f16_tuned", tuned)
         res[name] = measure(cdt, scaler, a, dev)
         o = res[name]

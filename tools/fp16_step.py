@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Time the training step of the ViT (JPEG-Ti / JPEG-S) or of SwinV2-T in its four compute configurations, in one process,
-alternating:
+"""Time the training step of the ViT (JPEG-Ti / JPEG-S) or of SwinV2-T in its compute configurations, in one process,
+alternating (--configs picks them; default: the first four, what profiles/fp16_tuned_step.json holds):
 
   fp16          autocast(float16) with the library's defaults: fp16 activations on the generic kernels
   fp16_tuned    autocast(float16) with the option f16_tuned = 1: the plain GEMMs (small-M, weight-resident, row-panel, pipelined and
@@ -9,6 +9,11 @@ alternating:
                 gradient bracket and the held reductions, group_dw_backward): the kernel set fp16 runs
   bf16          bf16 with every option at its default (what bench.py times; SwinV2-T: group_dw_backward + hold_reductions on,
                 drop_path_rate 0.2, as bench.py --arch swinv2t)
+  fp16_fused    autocast(float16) with f16_tuned = 2: fp16_tuned plus attention v2, the fused MLP and the LayerNorm-chained epilogues
+                in fp16 -- the whole per-block tuned path
+  bf16_nochain  bf16 with fwd_chain = bwd_chain = 0: the kernel set of fp16_fused, in bf16
+  fp16_fused_noattn / _nomlp / _noln   fp16_fused with one family switched off (attn_v2 | mlp_fuse + mlp_bwd | ln_fuse; the fused
+                MLP backward needs ln_fuse and goes with it): the per-family A/B
 
 A step is what bench.py times, launched eagerly: augment (DCT-domain, fp32 output for fp16 and bf16_generic, bf16 for bf16),
 lazy mixup, forward, soft-target loss, backward, fused clip + AdamW + weight decay.  Per arch, every configuration runs WARMUP
@@ -39,14 +44,23 @@ ARCH = {"vitti": (192, 3), "vits": (384, 6), "swinv2t": (96, 3)}
 BF16_ONLY_OPTS = ("fwd_chain", "bwd_chain", "nt_kpipe", "nt_wres", "nt_small", "tn_pipe", "tn_wide", "mlp_fuse", "mlp_bwd",
                   "attn_v2", "ln_fuse")
 CONFIGS = ("fp16", "fp16_tuned", "bf16_generic", "bf16")
-F16_CONFIGS = ("fp16", "fp16_tuned")
+# name -> (f16_tuned level, options switched off on top of the defaults)
+EXTRA = {"fp16_fused": (2, ()), "bf16_nochain": (0, ("fwd_chain", "bwd_chain")), "fp16_fused_noattn": (2, ("attn_v2",)),
+         "fp16_fused_nomlp": (2, ("mlp_fuse", "mlp_bwd")), "fp16_fused_noln": (2, ("ln_fuse",))}
+F16_CONFIGS = ("fp16", "fp16_tuned") + tuple(k for k in EXTRA if k.startswith("fp16"))
+TUNED_SETS = ("bf16", "bf16_nochain", "fp16_tuned") + tuple(k for k in EXTRA if k.startswith("fp16"))
 
 
-def set_opts(defaults, off, f16_tuned=0):
+def set_opts(defaults, off, f16_tuned=0, also_off=()):
     lib = L.lib()
     lib.rgbnm_set_option(b"f16_tuned", f16_tuned)
     for k, v in defaults.items():
-        lib.rgbnm_set_option(k.encode(), 0 if (off and k in BF16_ONLY_OPTS) else v)
+        lib.rgbnm_set_option(k.encode(), 0 if ((off and k in BF16_ONLY_OPTS) or k in also_off) else v)
+
+
+def set_cfg(defaults, cfg):
+    level, also_off = EXTRA.get(cfg, (int(cfg == "fp16_tuned"), ()))
+    set_opts(defaults, cfg == "bf16_generic", level, also_off)
 
 
 def swin_model(dev, drop_path_rate):
@@ -64,7 +78,7 @@ def swin_logit_error(cfg, defaults):
                       strict=False)
     y = torch.from_numpy(detfill.normalish((256, 1, 32, 32, 8, 8), 171)).cuda()
     c = torch.from_numpy(detfill.normalish((256, 2, 16, 16, 8, 8), 172)).cuda()
-    set_opts(defaults, cfg == "bf16_generic", int(cfg == "fp16_tuned"))
+    set_cfg(defaults, cfg)
     m.train()
     with torch.autocast("cuda", dtype=torch.float16 if cfg in F16_CONFIGS else torch.bfloat16):
         out = m(y, c)
@@ -81,7 +95,7 @@ def logit_error(cfg, defaults):
     m.load_state_dict({k: torch.from_numpy(v) for k, v in detfill.fill_state_dict(shapes, base_seed=1).items()})
     y = torch.from_numpy(detfill.normalish((256, 1, 28, 28, 8, 8), 71)).cuda()
     c = torch.from_numpy(detfill.normalish((256, 2, 14, 14, 8, 8), 72)).cuda()
-    set_opts(defaults, cfg == "bf16_generic", int(cfg == "fp16_tuned"))
+    set_cfg(defaults, cfg)
     m.train()
     with torch.autocast("cuda", dtype=torch.float16 if cfg in F16_CONFIGS else torch.bfloat16):
         out = m(y, c)
@@ -91,21 +105,26 @@ def logit_error(cfg, defaults):
 
 
 def main():
+    global CONFIGS
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--arch", nargs="+", default=["vitti", "vits"], choices=list(ARCH))
+    ap.add_argument("--configs", nargs="+", default=list(CONFIGS), choices=list(CONFIGS) + list(EXTRA))
     a = ap.parse_args()
+    CONFIGS = tuple(a.configs)
     assert torch.cuda.is_available(), "needs the GPU"
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     lib = L.lib()
     defaults = {k: lib.rgbnm_get_option(k.encode()) for k in BF16_ONLY_OPTS}
+    res_configs = list(CONFIGS)
     print(f"bf16_generic: options switched off: {', '.join(BF16_ONLY_OPTS)}", file=sys.stderr)
     B = a.batch
-    res = {"batch": B, "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "bf16_only_options_off": list(BF16_ONLY_OPTS)}
+    res = {"batch": B, "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "bf16_only_options_off": list(BF16_ONLY_OPTS),
+           "configs": res_configs}
     for arch in a.arch:
         emb, heads = ARCH[arch]
         torch.manual_seed(0)
@@ -130,9 +149,9 @@ def main():
             legs[cfg] = (aug, CT.FastParamSampler(aug, seed=1234), mix, cdt)
 
         def configure(cfg):
-            set_opts(defaults, cfg == "bf16_generic", int(cfg == "fp16_tuned"))
+            set_cfg(defaults, cfg)
             if swin:                            # the backward-wide bracket and the held reductions: on the tuned kernel sets only
-                model.group_dw_backward = model.hold_reductions = cfg in ("bf16", "fp16_tuned")
+                model.group_dw_backward = model.hold_reductions = cfg in TUNED_SETS
 
         def step(cfg):
             aug, sampler, mix, cdt = legs[cfg]
@@ -175,10 +194,10 @@ def main():
         model.load_state_dict(state)
         out = {cfg: {"step_ms_median": float(np.median(v)), "step_ms_min": float(min(v)), "step_ms_max": float(max(v)),
                      "nonfinite_blocks": nonfinite[cfg]} for cfg, v in ms.items()}
-        out["fp16_over_bf16_generic"] = out["fp16"]["step_ms_median"] / out["bf16_generic"]["step_ms_median"]
-        out["fp16_over_bf16"] = out["fp16"]["step_ms_median"] / out["bf16"]["step_ms_median"]
-        out["fp16_tuned_over_fp16"] = out["fp16_tuned"]["step_ms_median"] / out["fp16"]["step_ms_median"]
-        out["fp16_tuned_over_bf16"] = out["fp16_tuned"]["step_ms_median"] / out["bf16"]["step_ms_median"]
+        for num, den in (("fp16", "bf16_generic"), ("fp16", "bf16"), ("fp16_tuned", "fp16"), ("fp16_tuned", "bf16"),
+                         ("fp16_fused", "fp16_tuned"), ("fp16_fused", "bf16_nochain"), ("fp16_fused", "bf16")):
+            if num in ms and den in ms:
+                out[f"{num}_over_{den}"] = out[num]["step_ms_median"] / out[den]["step_ms_median"]
         res[arch] = out
         print(f"{arch}: " + ", ".join(f"{k} {v['step_ms_median']:.3f} ms" for k, v in out.items() if isinstance(v, dict)), file=sys.stderr)
         del model, opt

@@ -51,15 +51,16 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--arch", nargs="+", default=["vitti", "swinv2t"], choices=list(ARCH))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "loss_scale_step.json"))
+    ap.add_argument("--f16-tuned", type=int, default=1, choices=(1, 2), help="level of the option f16_tuned")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     lib = L.lib()
     tuned0 = lib.rgbnm_get_option(b"f16_tuned")
-    lib.rgbnm_set_option(b"f16_tuned", 1)
+    lib.rgbnm_set_option(b"f16_tuned", a.f16_tuned)
     B = a.batch
-    res = {"batch": B, "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "dtype": "float16", "f16_tuned": 1,
+    res = {"batch": B, "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "dtype": "float16", "f16_tuned": a.f16_tuned,
            "source_hash": L.source_hash()}
     for arch in a.arch:
         emb, heads = ARCH[arch]
