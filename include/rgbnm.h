@@ -103,7 +103,7 @@ int rgbnm_set_option(const char* name, int value);
 int rgbnm_get_option(const char* name);
 /* With option "trace" = (1 << tag) the launchers bracket kernels of that class with HIP events recorded on the launch
  * stream (tags: 1 gemm_nt, 2 gemm_tn, 3 attention fwd, 4 attention bwd, 5 one-launch encoder forward, 6 one-launch encoder backward,
- * 7 augment stage, 8 sub-block embed, 9 clip + AdamW + WeightDecay).  collect() synchronises those events and
+ * 7 augment stage, 8 sub-block embed, 9 clip + AdamW + WeightDecay, 10 the four GEMM stages of rgbnm_dct_dft_ops).  collect() synchronises those events and
  * returns their summed elapsed ms plus the algorithmic FLOPs / bytes of the bracketed launches, then forgets them. */
 int rgbnm_trace_collect(int tag, double* ms_total, double* flops_total, double* bytes_total, int* count);
 /* Create the events of the next n_events / 2 bracketed launches NOW (call outside a timed region: the runtime grows its signal
@@ -365,6 +365,28 @@ int rgbnm_dct_augment_chain(const int16_t* Y, const int16_t* C, const long long*
                             const rgbnm_aug_op* ops_dev, const rgbnm_aug_op* ops_host, const float* conv16,
                             const float* filters, void* outY, void* outC, int out_code, int size, int B, int Hy, int Wy,
                             int Hc, int Wc, int entry_clamp, int nops, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The DFT-plane operations of RandAugment_dct -- Rotate, ShearX, ShearY (utils/dct_ops.py:367-434, 957-1013) -- for a list of
+ * samples of a batch, in place, as four launches per call (csrc/dft_ops.hip).  Y [B,1,S,S,8,8] and C [B,2,S/2,S/2,8,8] (NULL:
+ * luma only) int16; S even, 2..32.  Each plane is zero-padded to Hp x Hp blocks (S <= Hp_y <= 48, S/2 <= Hp_c <= 48; margins
+ * (Hp - Hb) / 2, the larger one behind when the difference is odd), turned by rot90s exact quarter turns (0..3, counter-clockwise,
+ * of the PADDED grid), block-shifted, taken to the DFT plane F = L.X.L^H with L = conv (interleaved complex64 [N][N], N = 8 Hp:
+ * dct_ops.generate_conversion_matrix_dft(8, Hp)), resampled G[p] = F[map[p]] (map[p] = -1 or anything outside 0..N*N-1: zero) with
+ * map number map_y / map_c of maps_y [nmaps][Ny*Ny] / maps_c [nmaps][Nc*Nc], taken back, un-shifted, cropped, rounded half to even
+ * and stored as int16; clamp = 1 then clamps to [-1024, 1016] (the reference's per-op clamp, custom_transforms.py:1019-1020).
+ * The twelve real products per plane run on the exact f32-input MFMA; a sample's result does not depend on the other jobs and is
+ * the same from run to run.  Samples not listed are not touched.  The jobs are needed on the device (kernels) and on the host
+ * (validated before launch).  workspace: rgbnm_dct_dft_workspace(njobs, Hp_y, Hp_c) bytes.
+ * RGBNM_EINVAL with nothing launched and no buffer touched: S odd or outside 2..32, B <= 0, Hp below the plane's grid or above 48,
+ * njobs < 0, only one of jobs_dev / jobs_host, a sample outside 0..B-1 or listed twice, rot90s outside 0..3, a map index outside
+ * 0..nmaps-1, clamp outside 0..1, a NULL Y / conv_y / maps_y (conv_c / maps_c with C), a workspace that is NULL or too small.
+ * njobs == 0 returns 0 without a launch. */
+typedef struct rgbnm_dft_job { int sample; int rot90s; int map_y; int map_c; } rgbnm_dft_job;
+size_t rgbnm_dct_dft_workspace(int njobs, int Hp_y, int Hp_c);
+int rgbnm_dct_dft_ops(int16_t* Y, int16_t* C, int B, int S, int Hp_y, int Hp_c, const rgbnm_dft_job* jobs_dev,
+                      const rgbnm_dft_job* jobs_host, int njobs, const float* conv_y, const float* conv_c,
+                      const int32_t* maps_y, const int32_t* maps_c, int nmaps, int clamp, void* workspace, size_t workspace_bytes,
+                      void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Train-step tail

@@ -26,8 +26,9 @@ OPS = {"Identity": 0, "AutoContrast": 1, "Posterize": 2, "SolarizeAdd": 3, "Colo
        "MidfreqAug": 7, "Cutout": 8, "TranslateX": 9, "TranslateY": 10, "Rotate90": 11, "AutoSaturation": 12,
        "Grayscale": 13, "ChromaDrop": 14, "Sharpness": 15, "Invert": 16, "Solarize": 17, "FreqEnhance": 18, "Equalize": 19}
 CHROMA_OPS = {"Grayscale", "Color", "AutoSaturation", "ChromaDrop"}
-# The reference's DFT-plane ops (utils/dct_ops.py:367-434, 957-1013): in no DCT op list of utils/configs.py; they run as device tensor
-# ops between kernel passes (dct_ops.rotate_block / shear_block) and only through RandAugment_dct, not through the fused transform
+# The reference's DFT-plane ops (utils/dct_ops.py:367-434, 957-1013): in no DCT op list of utils/configs.py.  RandAugment_dct runs them
+# between kernel passes, as device tensor ops (dct_ops.rotate_block / shear_block) or with dft_kernel=True as one batched
+# rgbnm_dct_dft_ops call per pass; the fused transform takes them with dft_ops=True (the chain is cut at their positions)
 DFT_OPS = {"Rotate", "ShearX", "ShearY"}
 # default vitti list (utils/configs.py:93)
 VITTI_OPS = ("AutoContrast,Posterize,SolarizeAdd,Color,Contrast,Brightness,MidfreqAug,Cutout,TranslateX,TranslateY,"
@@ -420,6 +421,64 @@ class RandomFlip_DCT(torch.nn.Module):
         return _pack(*_run_chain(Y, C, Y.shape[2], [_whole(Y)] * B, flips, ops, 0, torch.int16), single, batched)
 
 
+class _DftPlaneRunner:
+    """Operands and scratch of rgbnm_dct_dft_ops (csrc/dft_ops.hip) for one module: per (grid, pad, device) the conversion
+    matrices and a bank of gather maps (dct_ops.dft_gather_map, one per distinct affine matrix, stacked for the call), the
+    workspace, and the pinned ring the job records travel through."""
+    MAX_MAPS = 32
+
+    def __init__(self):
+        self.banks, self._ws = {}, None
+
+    def _bank(self, S, pad, dev):
+        key = (S, pad, str(dev))
+        bk = self.banks.get(key)
+        if bk is None:
+            Hy, Hc = dops.padded_blocks(S, pad), dops.padded_blocks(S // 2, pad)
+            conv = [torch.view_as_real(dops.generate_conversion_matrix_dft(8, h, dev)).contiguous() for h in (Hy, Hc)]
+            bk = self.banks[key] = dict(Hy=Hy, Hc=Hc, conv=conv, keys={}, maps=([], []), stack=None)
+        return bk
+
+    def run(self, Y, CbCr, jobs, pad, clamp):
+        """jobs: [(sample, name, magnitude)], every sample at most once.  Works in place on Y (B,1,S,S,8,8) and CbCr (B,2,S/2,S/2,8,8)
+        or None, int16 contiguous device tensors."""
+        if not jobs:
+            return
+        L.require_cuda(Y, CbCr)
+        B, S, dev = Y.shape[0], Y.shape[2], Y.device
+        bk = self._bank(S, pad, dev)
+        arr = (L.DftJob * len(jobs))()
+        for n, (b, name, mag) in enumerate(jobs):
+            if name == "Rotate":
+                rot, mat = dops.rotate_plan(mag)
+            elif name == "ShearX":
+                rot, mat = dops.shear_plan(deg_x=mag)
+            elif name == "ShearY":
+                rot, mat = dops.shear_plan(deg_y=mag)
+            else:
+                raise ValueError(f"{name} is not a DFT-plane operation")
+            k = tuple(mat)
+            if k not in bk["keys"]:
+                if len(bk["keys"]) >= self.MAX_MAPS:      # more distinct matrices than a training run ever draws: start over
+                    self.banks.pop((S, pad, str(dev)))
+                    return self.run(Y, CbCr, jobs, pad, clamp)
+                bk["keys"][k] = len(bk["keys"])
+                for maps, h in zip(bk["maps"], (bk["Hy"], bk["Hc"])):
+                    maps.append(dops.dft_gather_map(mat, 8 * h, dev))
+                bk["stack"] = None
+            arr[n].sample, arr[n].rot90s, arr[n].map_y, arr[n].map_c = int(b), rot, bk["keys"][k], bk["keys"][k]
+        if bk["stack"] is None:
+            bk["stack"] = tuple(torch.stack(m).contiguous() for m in bk["maps"])
+        wsb = L.lib().rgbnm_dct_dft_workspace(len(jobs), bk["Hy"], bk["Hc"])
+        if self._ws is None or self._ws.numel() < wsb or self._ws.device != dev:
+            self._ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
+        jdev = _params_to_device(self, np.frombuffer(bytes(arr), dtype=np.uint8), dev)
+        L.check(L.lib().rgbnm_dct_dft_ops(Y.data_ptr(), L.ptr(CbCr), B, S, bk["Hy"], bk["Hc"], jdev.data_ptr(), C.cast(arr, C.c_void_p),
+                                          len(jobs), bk["conv"][0].data_ptr(), bk["conv"][1].data_ptr(), bk["stack"][0].data_ptr(),
+                                          bk["stack"][1].data_ptr(), len(bk["keys"]), int(clamp), self._ws.data_ptr(),
+                                          self._ws.numel(), L.stream()), "dct_dft_ops")
+
+
 # ops_list=None for the FUSED transform and datasets.get_transform(fused=...): the reference's own default
 # (custom_transforms.py:1060-1062) minus the DFT-plane Rotate / ShearX / ShearY, which only the class below runs
 DEFAULT_OPS = ("AutoContrast", "Equalize", "Invert", "Posterize", "Solarize", "SolarizeAdd", "Color", "Contrast",
@@ -433,12 +492,17 @@ class RandAugment_dct(torch.nn.Module):
     """custom_transforms.py:1024-1138: clamp, then num_ops operations drawn from ops_list at magnitude bin `magnitude`
     (random sign for the signed ones; chroma / grayscale mutual exclusion), clamp after every op.
     `Rotate` / `ShearX` / `ShearY` (the reference's default list has them, no DCT list of utils/configs.py does) resample the DFT plane
-    of the padded image (`pad`, default sqrt(2) as in the reference) as device tensor ops between the kernel passes; their
-    torchvision sampling is restated, not pinned (dct_ops.py, oracle/dft_np.py)."""
+    of the padded image (`pad`, default sqrt(2) as in the reference) between the kernel passes: as per-sample device tensor ops, or
+    with dft_kernel=True as one batched kernel call per pass (same result up to rounding ties); their torchvision sampling is
+    restated, not pinned (dct_ops.py, oracle/dft_np.py)."""
 
-    def __init__(self, num_ops: int = 2, magnitude: int = 10, num_magnitude_bins: int = 11, pad=2 ** 0.5, ops_list=None):
+    def __init__(self, num_ops: int = 2, magnitude: int = 10, num_magnitude_bins: int = 11, pad=2 ** 0.5, ops_list=None,
+                 dft_kernel=False):
         super().__init__()
         self.num_ops, self.magnitude, self.num_magnitude_bins, self.pad = num_ops, magnitude, num_magnitude_bins, pad
+        # True: the DFT-plane ops of a pass run as ONE rgbnm_dct_dft_ops call (csrc/dft_ops.hip) instead of per-sample tensor ops
+        self.dft_kernel = bool(dft_kernel)
+        self._dft = _DftPlaneRunner()
         if ops_list is None:
             ops_list = REFERENCE_DEFAULT_OPS
         bad = [o for o in ops_list if o not in OPS and o not in DFT_OPS]
@@ -446,8 +510,9 @@ class RandAugment_dct(torch.nn.Module):
             raise NotImplementedError(f"operations {bad} are not implemented on the HIP path")
         self.ops_list = list(ops_list)
 
-    def forward(self, coeff, ops=None):
-        """ops: explicit [(name, magnitude, aux), ...] applied to every sample (parity tests)."""
+    def forward(self, coeff, ops=None, per_sample_ops=None):
+        """ops: explicit [(name, magnitude, aux), ...] applied to every sample (parity tests); per_sample_ops: one such list per
+        sample (what the sampling below would have drawn; tools/dft_ops_step.py times both paths on the same draws)."""
         if len(self.ops_list) == 0:
             return coeff
         Y, C, single, batched = _unpack(coeff)
@@ -455,8 +520,13 @@ class RandAugment_dct(torch.nn.Module):
         if Y.shape[2] != Y.shape[3]:
             raise NotImplementedError("RandAugment_dct on the HIP path works on the square grids after the crop/resize stage")
         meta = magnitude_table(self.num_magnitude_bins, (S, S))
-        chosen = [list(ops)] * B if ops is not None else \
-            [sample_ops(self.ops_list, self.num_ops, self.magnitude, meta, S) for _ in range(B)]
+        if per_sample_ops is not None:
+            if ops is not None or len(per_sample_ops) != B:
+                raise ValueError("per_sample_ops: one op list per sample, and not together with ops")
+            chosen = [list(c) for c in per_sample_ops]
+        else:
+            chosen = [list(ops)] * B if ops is not None else \
+                [sample_ops(self.ops_list, self.num_ops, self.magnitude, meta, S) for _ in range(B)]
         # the kernel chains AUG_MAX_OPS operations per pass; longer chains run as further passes over the int16 result -- the entry
         # clamp of a later pass is the identity on what the previous pass's per-op clamp left
         n = max([len(c) for c in chosen] + [1])
@@ -471,6 +541,10 @@ class RandAugment_dct(torch.nn.Module):
             kern = [[c[k]] if k < len(c) and c[k][0] not in DFT_OPS else [] for c in chosen]
             if k == 0 or any(kern):
                 Y, C = _run_chain(Y, C, S, [_whole(Y)] * B, None, kern, 1 if k == 0 else 0, torch.int16)
+            if self.dft_kernel:      # clamp=0: what rotate_block / shear_block return, like the tensor path below
+                self._dft.run(Y, C, [(b, c[k][0], c[k][1]) for b, c in enumerate(chosen) if k < len(c) and c[k][0] in DFT_OPS],
+                              self.pad, 0)
+                continue
             for b, c in enumerate(chosen):
                 if k < len(c) and c[k][0] in DFT_OPS:
                     name, mag = c[k][0], c[k][1]
@@ -521,7 +595,7 @@ class TrainTransform_DCT(torch.nn.Module):
     """Batched device version of get_transform('imagenet_dct', 'train') (datasets.py:354-361)."""
 
     def __init__(self, size=28, scale=(0.05, 1.0), flip_p=0.5, num_ops=2, magnitude=3, num_magnitude_bins=11,
-                 ops_list=None, out_dtype=torch.float32, eval_mode=False, size_resize=32):
+                 ops_list=None, out_dtype=torch.float32, eval_mode=False, size_resize=32, dft_ops=False, dft_pad=2 ** 0.5):
         super().__init__()
         if size not in (28, 32):
             raise NotImplementedError("HIP augment path covers 28x28-block (imagenet_dct) and 32x32-block "
@@ -534,10 +608,14 @@ class TrainTransform_DCT(torch.nn.Module):
         self.size, self.flip_p, self.num_ops, self.magnitude = size, flip_p, num_ops, magnitude
         self.num_magnitude_bins = num_magnitude_bins
         self.ops_list = list(VITTI_OPS if ops_list is None else ops_list)
-        bad = [o for o in self.ops_list if o not in OPS]
+        # dft_ops=True: ops_list (and explicit params) may name the DFT-plane Rotate / ShearX / ShearY; a sample's chain is cut at
+        # each of them: kernel pass (int16) -> rgbnm_dct_dft_ops with the reference's per-op clamp -> kernel pass ... -> ToRange
+        self.dft_ops, self.dft_pad = bool(dft_ops), dft_pad
+        bad = [o for o in self.ops_list if o not in OPS and not (self.dft_ops and o in DFT_OPS)]
         if bad:
             raise NotImplementedError(f"operations {bad} are not in the fused transform's kernels (the DFT-plane Rotate / ShearX / "
-                                      "ShearY run through the per-transform class RandAugment_dct)")
+                                      "ShearY need dft_ops=True, or the per-transform class RandAugment_dct)")
+        self._dft = _DftPlaneRunner()
         self.out_dtype = out_dtype
         self.eval_mode = eval_mode
         self.rrc = RandomResizedCrop_DCT(size, scale=scale, ratio=(1, 1))
@@ -609,13 +687,43 @@ class TrainTransform_DCT(torch.nn.Module):
     def forward(self, Yq, CbCrq, quant, params=None, entry_flags=None):
         """Yq (B,1,Hy,Wy,8,8) int16, CbCrq (B,2,Hc,Wc,8,8) int16 or None, quant (B,3,8,8) int16 -- device tensors.
         entry_flags: rgbnm_dct_augment_ex's `entry_clamp` argument (default: clamp before the ops unless eval_mode)."""
+        if params is None:
+            params = self.sample_params(Yq.shape[0], Yq.shape[2], Yq.shape[3])
+        if not any(o[0] in DFT_OPS for p in params for o in p["ops"]):
+            return self._pass(Yq, CbCrq, quant, params, entry_flags, self.out_dtype)
+        if not self.dft_ops:
+            raise NotImplementedError("the DFT-plane Rotate / ShearX / ShearY need TrainTransform_DCT(dft_ops=True)")
+        # every chain is cut at its DFT-plane ops: segs[b] = kernel ops before the first, between ..., after the last; cuts[b] the
+        # DFT-plane ops themselves.  Round r runs segment r of every sample as one kernel pass (the first one with the crop / resize /
+        # flip stage and the entry clamp, the last one with ToRange), then cut r of the samples that have one as one batched call
+        segs, cuts = [], []
+        for p in params:
+            sg, ct = [[]], []
+            for o in p["ops"]:
+                if o[0] in DFT_OPS:
+                    ct.append(o)
+                    sg.append([])
+                else:
+                    sg[-1].append(o)
+            segs.append(sg)
+            cuts.append(ct)
+        rounds = max(len(c) for c in cuts)
+        S, B = self.size, len(params)
+        Y, Cc = self._pass(Yq, CbCrq, quant, [dict(p, ops=sg[0]) for p, sg in zip(params, segs)], entry_flags, torch.int16)
+        for r in range(rounds):
+            self._dft.run(Y, Cc, [(b, c[r][0], c[r][1]) for b, c in enumerate(cuts) if r < len(c)], self.dft_pad, 1)
+            nxt = [dict(box=(0, 0, S, S), flip=False, ops=sg[r + 1] if r + 1 < len(sg) else []) for sg in segs]
+            # | 2: de-quantised already; no entry clamp: every op and every DFT-plane call has clamped what it wrote
+            Y, Cc = self._pass(Y, Cc, self._unit_quant(B, Y.device), nxt, 2, self.out_dtype if r == rounds - 1 else torch.int16)
+        return Y, Cc
+
+    def _pass(self, Yq, CbCrq, quant, params, entry_flags, out_dtype):
+        """One launch pair of the augment kernels: crop / resize / flip, the kernel ops of params, output in out_dtype."""
         L.require_cuda(Yq, CbCrq, quant)
         if Yq.dtype != torch.int16 or quant.dtype != torch.int16 or (CbCrq is not None and CbCrq.dtype != torch.int16):
             raise TypeError("coefficients and quantisation tables must be int16 (dct_manip.read_coefficients layout)")
         B, _, Hy, Wy, _, _ = Yq.shape
         Hc, Wc = (CbCrq.shape[2], CbCrq.shape[3]) if CbCrq is not None else (Hy // 2, Wy // 2)
-        if params is None:
-            params = self.sample_params(B, Hy, Wy)
         dev = Yq.device
         ops = None
         if max([len(p["ops"]) for p in params] + [0]) > 2:
@@ -631,9 +739,9 @@ class TrainTransform_DCT(torch.nn.Module):
         wsb = L.lib().rgbnm_dct_augment_workspace_ex(B, S)
         if self._ws is None or self._ws.numel() < wsb or self._ws.device != dev:
             self._ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
-        oy = torch.empty(B, 1, S, S, 8, 8, device=dev, dtype=self.out_dtype)
-        oc = torch.empty(B, 2, S // 2, S // 2, 8, 8, device=dev, dtype=self.out_dtype)
-        odt = L.aug_out_code(self.out_dtype)      # 2: raw int16, no ToRange (rgbnm.h)
+        oy = torch.empty(B, 1, S, S, 8, 8, device=dev, dtype=out_dtype)
+        oc = torch.empty(B, 2, S // 2, S // 2, 8, 8, device=dev, dtype=out_dtype)
+        odt = L.aug_out_code(out_dtype)      # 2: raw int16, no ToRange (rgbnm.h)
         entry = (0 if self.eval_mode else 1) if entry_flags is None else entry_flags
         if ops is None and odt != L.AUG_OUT_F16:
             rc = L.lib().rgbnm_dct_augment_ex(Yq.data_ptr(), L.ptr(CbCrq), quant.data_ptr(), pdev.data_ptr(),
@@ -675,6 +783,9 @@ class FastParamSampler:
         self.rng = np.random.default_rng(seed)
         meta = magnitude_table(t.num_magnitude_bins, (t.size, t.size))
         names = list(t.ops_list)
+        if any(n in DFT_OPS for n in names):
+            raise NotImplementedError("FastParamSampler / apply_packed pack kernel ops only; the DFT-plane Rotate / ShearX / ShearY go "
+                                      "through TrainTransform_DCT(dft_ops=True).sample_params and its forward")
         self.names = names
         enc = np.zeros((len(names), 2, 5), dtype=np.float64)        # [op][sign] -> (id, fmag, a0, a1, a2)
         self.signed = np.zeros(len(names), dtype=bool)

@@ -112,8 +112,9 @@ def midfreq_filter(intensity, KH=8, KW=8):
 
 # ----------------------------------------------------------------------------------------------------------------
 # DFT-plane Rotate / ShearX / ShearY of RandAugment_dct (utils/dct_ops.py:210-232, 303-434, 957-1013,
-# utils/dct_torch_utils.py:232-321).  In no DCT op list of utils/configs.py, so not on the timed path: device TENSOR ops (complex
-# matrix products through the library, index arithmetic for the nearest-neighbour resampling), no kernel of this repo.  The
+# utils/dct_torch_utils.py:232-321).  In no DCT op list of utils/configs.py, so not on the timed path.  Below: the device TENSOR path
+# (complex matrix products through the library, index arithmetic for the nearest-neighbour resampling) and the operands of the
+# batched kernels that compute the same thing (csrc/dft_ops.hip: conversion matrix, dft_gather_map, rotate_plan / shear_plan).  The
 # reference resamples with torchvision's rotate / affine; torchvision is not installed here, so the sampling below restates its
 # published tensor path (affine grid in fp32 + grid_sample nearest / zeros / align_corners=False) and the row is PARITY UNPINNED
 # (oracle/dft_np.py says the same; tests compare the two restatements and pin what can be pinned structurally).
@@ -197,12 +198,11 @@ def _inverse_affine_matrix(angle, shear):
     return [d, -b, 0.0, -c, a, 0.0]
 
 
-def _resample_nearest(plane, matrix):
-    """torchvision's tensor path for rotate / affine with NEAREST, expand=False, fill 0 on a (C,H,W) fp32 plane: affine grid in
+def _nearest_source(H, W, matrix, dev):
+    """The index math of torchvision's tensor path for rotate / affine with NEAREST, expand=False on an H x W plane: affine grid in
     fp32 (_gen_affine_grid), then grid_sample(mode='nearest', padding_mode='zeros', align_corners=False) as explicit index math
-    (source index = round-half-even(((g + 1) * size - 1) / 2))."""
-    C, H, W = plane.shape
-    dev = plane.device
+    (source index = round-half-even(((g + 1) * size - 1) / 2)).  Returns (iy, ix, ok): source row / column per output position
+    (int64, unclamped) and whether it lies inside the plane."""
     theta = torch.tensor(matrix, dtype=torch.float32, device=dev).reshape(2, 3)
     base = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
     base[..., 0] = torch.linspace(-W * 0.5 + 0.5, W * 0.5 + 0.5 - 1, steps=W, device=dev)
@@ -213,9 +213,40 @@ def _resample_nearest(plane, matrix):
     ix = torch.round(((grid[..., 0] + 1) * W - 1) / 2).long()
     iy = torch.round(((grid[..., 1] + 1) * H - 1) / 2).long()
     ok = (ix >= 0) & (ix < W) & (iy >= 0) & (iy < H)
+    return iy, ix, ok
+
+
+def _resample_nearest(plane, matrix):
+    """torchvision's tensor path for rotate / affine with NEAREST, expand=False, fill 0 on a (C,H,W) fp32 plane (_nearest_source)."""
+    C, H, W = plane.shape
+    iy, ix, ok = _nearest_source(H, W, matrix, plane.device)
     src = (iy.clamp(0, H - 1) * W + ix.clamp(0, W - 1)).view(-1)
     out = plane.reshape(C, -1)[:, src].view(C, H, W)
     return out * ok.to(plane.dtype)
+
+
+_GATHER_MAPS = {}            # (matrix, N, device) -> int32 (N, N); insertion ordered, at most _GATHER_MAPS_MAX entries
+_GATHER_MAPS_MAX = 32        # training uses at most six matrices per grid (Rotate +-, ShearX +-, ShearY +- at one magnitude)
+
+
+def dft_gather_map(matrix, N, device="cpu"):
+    """fftshift, _resample_nearest and ifftshift of an N x N DFT plane composed into ONE gather: G.view(-1)[p] = F.view(-1)[map[p]],
+    or 0 where map[p] == -1 (the sample falls outside the plane).  int32 (N, N), built on `device` from the fp32 tensor expressions
+    of _nearest_source, so its source indices are those of the tensor path there; cached per (matrix, N, device).  The operand of
+    rgbnm_dct_dft_ops (csrc/dft_ops.hip)."""
+    key = (tuple(float(v) for v in matrix), int(N), str(device))
+    m = _GATHER_MAPS.get(key)
+    if m is None:
+        iy, ix, ok = _nearest_source(N, N, matrix, device)
+        h = N // 2
+        # the sampler works on the fftshift-ed plane sh[a, b] = F[(a + h) % N, (b + h) % N] (N is even: 8 Hp)
+        src = ((iy + h) % N) * N + (ix + h) % N
+        src = torch.where(ok, src, torch.full_like(src, -1))
+        m = torch.fft.ifftshift(src, dim=(-2, -1)).to(torch.int32).contiguous()
+        while len(_GATHER_MAPS) >= _GATHER_MAPS_MAX:
+            _GATHER_MAPS.pop(next(iter(_GATHER_MAPS)))
+        _GATHER_MAPS[key] = m
+    return m
 
 
 def _dft_plane_op(coeff, matrix, pad, rot90s=0):
@@ -245,18 +276,35 @@ def _dft_plane_op(coeff, matrix, pad, rot90s=0):
     return dec.to(dt)
 
 
-def rotate_block(coeff, degrees=45, pad=False):
-    """utils/dct_ops.py:367-434 on a device tensor (C,H,W,KH,KW): counter-clockwise; quarter turns exactly, the remainder in
-    (-45, 45] on the DFT plane."""
+def rotate_plan(degrees):
+    """rotate_block's split of an angle (utils/dct_ops.py:367-434): (exact quarter turns 0..3, inverse affine matrix of the
+    remainder in (-45, 45])."""
     sign = degrees / abs(degrees) if degrees != 0 else 1
     rem = sign * (abs(degrees) % 360)
     shifted = (rem + 360 + 45) % 360
     rot90s = shifted // 90
     left = -((rot90s * 90) - (shifted - 45))
     # dct_torch_utils.py:247 negates the angle, torchvision's rotate negates it again for its inverse matrix: +left here
-    return _dft_plane_op(coeff, _inverse_affine_matrix(left, [0.0, 0.0]), pad, rot90s=int(rot90s))
+    return int(rot90s), _inverse_affine_matrix(left, [0.0, 0.0])
+
+
+def shear_plan(deg_x=0, deg_y=0):
+    """shear_block's (quarter turns, inverse affine matrix)."""
+    return 0, _inverse_affine_matrix(0.0, [deg_x, deg_y])
+
+
+def padded_blocks(H, pad):
+    """Block count of the padded grid _dft_plane_op works on."""
+    return int(H * pad // 1) if pad else H
+
+
+def rotate_block(coeff, degrees=45, pad=False):
+    """utils/dct_ops.py:367-434 on a device tensor (C,H,W,KH,KW): counter-clockwise; quarter turns exactly, the remainder in
+    (-45, 45] on the DFT plane."""
+    rot90s, matrix = rotate_plan(degrees)
+    return _dft_plane_op(coeff, matrix, pad, rot90s=rot90s)
 
 
 def shear_block(coeff, deg_x=0, deg_y=0, pad=False):
     """utils/dct_ops.py:957-1013 on a device tensor."""
-    return _dft_plane_op(coeff, _inverse_affine_matrix(0.0, [deg_x, deg_y]), pad)
+    return _dft_plane_op(coeff, shear_plan(deg_x, deg_y)[1], pad)

@@ -84,6 +84,11 @@ class ChainBwdBlock(C.Structure):
                                    "rstd2", "u", "dy", "du", "dx_mid", "dqkv", "dx", "part2", "part1")]
 
 
+class DftJob(C.Structure):
+    """rgbnm_dft_job: one sample of a rgbnm_dct_dft_ops call."""
+    _fields_ = [("sample", _i), ("rot90s", _i), ("map_y", _i), ("map_c", _i)]
+
+
 ABI_VERSION = 3      # include/rgbnm.h RGBNM_ABI_VERSION this binding was written against
 
 _P = C.POINTER
@@ -128,6 +133,8 @@ PROTOTYPES = {
                                       _i, _vp, _sz, _vp]),
     "rgbnm_dct_augment_chain": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
                                      _i, _vp, _sz, _vp]),
+    "rgbnm_dct_dft_workspace": (_sz, [_i, _i, _i]),
+    "rgbnm_dct_dft_ops": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "rgbnm_softxent": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "rgbnm_softxent_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "rgbnm_softxent_grad": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
