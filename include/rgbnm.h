@@ -388,6 +388,30 @@ int rgbnm_dct_dft_ops(int16_t* Y, int16_t* C, int B, int S, int Hp_y, int Hp_c, 
                       const int32_t* maps_y, const int32_t* maps_c, int nmaps, int clamp, void* workspace, size_t workspace_bytes,
                       void* stream);
 
+/* RGB (or gray) pixels to quantised DCT coefficients and back (csrc/pixel_dct.hip): what the reference gets from libjpeg (IJG 9,
+ * 4:2:0) through dct_manip.quantize_at_quality / decode_coeff (dct_manip.cpp:315-375, 485-576), for a batch on the device.  One
+ * launch per call, no allocation, no copy, no synchronisation: a call can be captured into a HIP graph.
+ * Layouts: pixels uint8 [B,C,H,W]; Y int16 [B,1,H/8,W/8,8,8]; CbCr int16 [B,2,H/16,W/16,8,8] -- the read_coefficients layout.
+ * C = 3 needs H and W divisible by 16, C = 1 (Y only, CbCr unused) by 8: libjpeg's edge replication is not done.
+ * quant_host: int16 [C][64] in HOST memory, natural order; it travels in the kernel arguments.  With C = 3 table 0 is luma's and
+ * table 1 serves BOTH chroma planes, as in libjpeg's component setup (decode_coeff copies two tables, dct_manip.cpp:180-187);
+ * table 2 is read only for the entry check.
+ * rgbnm_pixels_to_dct.  Luma is integer arithmetic and equals libjpeg bit for bit: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16,
+ * minus 128, the "islow" forward DCT (13-bit constants, 2 pass-1 bits: 8 x the DCT), then sign(c) (|c| + 4 q) / (8 q).  Chroma is
+ * the low 8 x 8 of the 16 x 16-point DCT of the MCU's integer Cb / Cr samples, in fp32, divided by the table entry and rounded half
+ * away from zero: within 1 of libjpeg, whose fixed-point 16-point routine is up to 0.08 off the exact value.
+ * rgbnm_dct_to_pixels (CbCr == NULL: one channel).  Dequantise; 8 x 8 inverse DCT for luma, the 8 -> 16 scaled inverse DCT for chroma,
+ * in fp32; every plane sample is floor(x + 0.5) clamped to [0, 255]; then libjpeg's fixed-point YCbCr -> RGB (16-bit scale, + 32768
+ * before the shift), clamped: within 3 of libjpeg wherever the exact samples of all three planes lie in [-128, 383].  Outside that
+ * range libjpeg's range-limit table wraps around; this call saturates.
+ * RGBNM_EINVAL with nothing launched: B, H or W <= 0, C not 1 or 3, H or W not divisible as above, B C H W >= 2^31, a NULL
+ * pixels / quant_host / Y (CbCr with C = 3 in rgbnm_pixels_to_dct), pixels not 4-byte or Y / CbCr not 16-byte aligned, a table entry
+ * below 1 in rgbnm_pixels_to_dct.  RGBNM_ELAUNCH if the launch failed. */
+int rgbnm_pixels_to_dct(const uint8_t* pixels, int B, int C, int H, int W, const int16_t* quant_host, int16_t* Y, int16_t* CbCr,
+                        void* stream);
+int rgbnm_dct_to_pixels(const int16_t* Y, const int16_t* CbCr, int B, int H, int W, const int16_t* quant_host, uint8_t* pixels,
+                        void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Train-step tail
  * ------------------------------------------------------------------------------------------- */

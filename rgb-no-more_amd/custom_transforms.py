@@ -766,6 +766,34 @@ def EvalTransform_DCT(**kw):
     return TrainTransform_DCT(eval_mode=True, **kw)
 
 
+class ycbcr_to_rgb(torch.nn.Module):
+    """custom_transforms.py:1140-1171: fp32 (de-quantised) coefficients (Y, cbcr) -> uint8 RGB through the JPEG decoder, here
+    dct_manip.decode_coeff on the device.  One sample (1,H,W,8,8) / (2,H/2,W/2,8,8) or a batch with a leading dimension."""
+
+    def forward(self, coeff):
+        from . import dct_manip as dm
+        Y, cbcr = coeff
+        assert Y.dtype == torch.float32 and cbcr.dtype == torch.float32, \
+            f"Y and CbCr dtype should be torch.float32. Current:{Y.dtype}, {cbcr.dtype}"
+        L.require_cuda(Y, cbcr)
+        # the reference's statements: halves against a table of twos, torch's round (half to even), then the int16 clamp
+        halves = [(x / 2).round().to(torch.int16).clamp(min=-1024, max=1016).contiguous() for x in (Y, cbcr)]
+        return dm.decode_coeff(None, torch.full((3, 8, 8), 2, dtype=torch.int16), halves[0], halves[1])
+
+
+class rgb_to_dct(torch.nn.Module):
+    """custom_transforms.py:1174-1196: uint8 RGB (3,H,W) or a batch (B,3,H,W) on the device -> (Y, cbcr) int16 at quality 100 (the
+    all-ones table: the coefficients are de-quantised as they stand), through dct_manip.quantize_at_quality."""
+
+    def forward(self, img):
+        from . import dct_manip as dm
+        if not torch.is_tensor(img):
+            raise TypeError(f"rgb_to_dct takes a uint8 tensor on the device, got {type(img).__name__}: convert a PIL image first, "
+                            "e.g. torchvision.transforms.functional.pil_to_tensor(img).cuda()")
+        _, _, Y, cbcr = dm.quantize_at_quality(img, 100)
+        return (Y, cbcr)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # Vectorised parameter sampling (numpy) with the same distributions as `sample_params`: the per-sample Python loop
 # costs ~50 us/sample, far more than the GPU spends on the sample; this one is ~0.1 ms per 256-sample batch.

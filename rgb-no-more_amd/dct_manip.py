@@ -7,6 +7,9 @@ return contract (dct_manip/dct_manip.cpp:152-178), implemented by the host C lib
 
 `read_coefficients_batch` decodes many same-shaped files with a pthread pool into pinned batch tensors ready for one
 H2D copy (replaces per-sample tensors + default collate, datasets.py:274-297,542-546).
+
+`quantize_at_quality` and `decode_coeff` (dct_manip.cpp:315-375, 485-576) run on DEVICE tensors, one HIP launch per call
+(csrc/pixel_dct.hip), for one image or a batch; there is no CPU fallback.
 """
 import ctypes as C
 import os
@@ -208,3 +211,102 @@ def read_coefficients_batch_crop(paths, boxes, threads=8, grid=(64, 64), pin_mem
             raise ValueError("crop box outside the coefficient grid (or not even)")
         _raise_batch(paths, status, bad)
     return Yp[:ny], Cp[:ncc], quant[:n], y_off, c_off
+
+
+# ---- pixels <-> coefficients on the device (csrc/pixel_dct.hip) --------------------------------------------------------------
+# ITU-T T.81 Annex K, natural order
+_LUMA_TABLE = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+               14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+               49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+_CHROMA_TABLE = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+                 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+
+
+def quality_tables(quality, channels=3, baseline=True):
+    """int16 (channels,8,8) CPU tensor: the standard tables at `quality` (1..100) as libjpeg's jpeg_set_quality scales them; the
+    chroma table twice for three channels."""
+    from . import lib as L
+    q = int(quality)
+    if not 1 <= q <= 100:
+        raise L.RgbnmError(f"quality must be in 1..100, got {quality}")
+    if channels not in (1, 3):
+        raise L.RgbnmError(f"1 or 3 channels, got {channels}")
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    top = 255 if baseline else 32767
+    base = torch.tensor([_LUMA_TABLE, _CHROMA_TABLE, _CHROMA_TABLE][:channels], dtype=torch.int64)
+    return ((base * s + 50) // 100).clamp(1, top).to(torch.int16).reshape(channels, 8, 8)
+
+
+def _host_table(quant, channels):
+    """The table as a contiguous int16 CPU tensor (a device tensor is copied back: that synchronises and cannot be captured)."""
+    from . import lib as L
+    if not torch.is_tensor(quant) or quant.dtype != torch.int16 or tuple(quant.shape[-2:]) != (8, 8) or quant.numel() < 64 * channels:
+        raise L.RgbnmError(f"quant must be an int16 tensor ({channels},8,8)")
+    return quant.detach().cpu().reshape(-1, 8, 8)[:channels].contiguous()
+
+
+def quantize_at_quality(pixels, quality, baseline=True):
+    """(dim, quant, Y, CbCr|None) of uint8 pixels (C,H,W) or a batch (B,C,H,W) on a HIP device -- reference:
+    dct_manip.quantize_at_quality (dct_manip.cpp:315-375), i.e. libjpeg at 4:2:0 without the entropy coder.
+    dim int32 [[H,W],[H/2,W/2],[H/2,W/2]] ([[H,W]] for one channel) and quant int16 (C,8,8) are CPU tensors; Y int16
+    ([B,]1,H/8,W/8,8,8) and CbCr int16 ([B,]2,H/16,W/16,8,8) are on the device.  C = 3 needs H and W divisible by 16, C = 1 by 8.
+    Luma equals libjpeg bit for bit, chroma is within 1 of it."""
+    from . import lib as L
+    if not torch.is_tensor(pixels):
+        raise TypeError(f"pixels must be a uint8 tensor on the device, got {type(pixels).__name__}")
+    if pixels.dtype != torch.uint8:
+        raise L.RgbnmError(f"pixels must be uint8, got {pixels.dtype}")
+    if pixels.dim() not in (3, 4):
+        raise L.RgbnmError(f"pixels must be (C,H,W) or (B,C,H,W), got {tuple(pixels.shape)}")
+    batched = pixels.dim() == 4
+    B = pixels.shape[0] if batched else 1
+    Cn, H, W = (int(v) for v in pixels.shape[-3:])
+    if Cn not in (1, 3):
+        raise L.RgbnmError(f"1 (gray) or 3 (RGB) channels, got {Cn}")
+    mod = 16 if Cn == 3 else 8
+    if B < 1 or H < mod or W < mod or H % mod or W % mod:
+        raise L.RgbnmError(f"height and width must be multiples of {mod} for {Cn} channel(s) (no edge replication), got {H} x {W}")
+    quant = quality_tables(quality, Cn, baseline)
+    L.require_cuda(pixels)
+    lead = (B,) if batched else ()
+    Y = torch.empty(lead + (1, H // 8, W // 8, 8, 8), dtype=torch.int16, device=pixels.device)
+    CbCr = torch.empty(lead + (2, H // 16, W // 16, 8, 8), dtype=torch.int16, device=pixels.device) if Cn == 3 else None
+    with torch.cuda.device(pixels.device):
+        L.check(L.lib().rgbnm_pixels_to_dct(pixels.data_ptr(), B, Cn, H, W, quant.data_ptr(), Y.data_ptr(), L.ptr(CbCr), L.stream()),
+                "pixels_to_dct")
+    dim = torch.tensor([[H, W], [H // 2, W // 2], [H // 2, W // 2]][:Cn], dtype=torch.int32)
+    return dim, quant, Y, CbCr
+
+
+def decode_coeff(dim, quant, Y, CbCr=None, quality=-1):
+    """uint8 pixels (C,H,W) or (B,C,H,W) on the device from int16 coefficients Y ([B,]1,Hb,Wb,8,8) and CbCr ([B,]2,Hb/2,Wb/2,8,8)
+    or None (one channel) -- reference: dct_manip.decode_coeff (dct_manip.cpp:485-576).  quant int16 (C,8,8), best on the CPU (a
+    device table is copied back first); quality > 0 replaces it by the standard tables, as in the reference.  dim is checked
+    against the grids when given (None: inferred).  Within 3 of libjpeg wherever the exact plane samples lie in [-128, 383];
+    outside that range libjpeg wraps around and this call saturates."""
+    from . import lib as L
+    if Y.dtype != torch.int16 or (CbCr is not None and CbCr.dtype != torch.int16):
+        raise L.RgbnmError("coefficients must be int16")
+    if Y.dim() not in (5, 6) or tuple(Y.shape[-2:]) != (8, 8) or Y.shape[-5] != 1:
+        raise L.RgbnmError(f"Y must be ([B,]1,Hb,Wb,8,8), got {tuple(Y.shape)}")
+    batched = Y.dim() == 6
+    B = Y.shape[0] if batched else 1
+    Hb, Wb = int(Y.shape[-4]), int(Y.shape[-3])
+    Cn = 1 if CbCr is None else 3
+    if CbCr is not None:
+        want = ((B,) if batched else ()) + (2, Hb // 2, Wb // 2, 8, 8)
+        if Hb % 2 or Wb % 2 or tuple(CbCr.shape) != want:
+            raise L.RgbnmError(f"CbCr must be {want} for Y {tuple(Y.shape)} (even luma grid, 4:2:0), got {tuple(CbCr.shape)}")
+    if B < 1 or Hb < 1 or Wb < 1:
+        raise L.RgbnmError(f"empty coefficient grid {tuple(Y.shape)}")
+    H, W = 8 * Hb, 8 * Wb
+    if dim is not None and [int(v) for v in torch.as_tensor(dim).reshape(-1)[:2]] != [H, W]:
+        raise L.RgbnmError(f"dim says {[int(v) for v in torch.as_tensor(dim).reshape(-1)[:2]]}, the luma grid is {H} x {W} "
+                           "(sizes that need edge replication are not supported)")
+    table = quality_tables(quality, Cn) if quality > 0 else _host_table(quant, Cn)
+    L.require_cuda(Y, CbCr)
+    out = torch.empty(((B,) if batched else ()) + (Cn, H, W), dtype=torch.uint8, device=Y.device)
+    with torch.cuda.device(Y.device):
+        L.check(L.lib().rgbnm_dct_to_pixels(Y.data_ptr(), L.ptr(CbCr), B, H, W, table.data_ptr(), out.data_ptr(), L.stream()),
+                "dct_to_pixels")
+    return out

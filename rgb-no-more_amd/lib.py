@@ -135,6 +135,8 @@ PROTOTYPES = {
                                      _i, _vp, _sz, _vp]),
     "rgbnm_dct_dft_workspace": (_sz, [_i, _i, _i]),
     "rgbnm_dct_dft_ops": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "rgbnm_pixels_to_dct": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "rgbnm_dct_to_pixels": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "rgbnm_softxent": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "rgbnm_softxent_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "rgbnm_softxent_grad": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
