@@ -281,9 +281,34 @@ __global__ void mixup_target_kernel(const long long* __restrict__ lab, float* __
 }
 
 // ------------------------------------------------------------------------------------------------
+// The train-step tail: two launches, a norm launch (sum of squares of the gradients, NORM_BLOCKS partial sums) and an update
+// launch (clip coefficient from the partial sums, AdamW, weight decay).  One norm body and one update body serve three modes:
+//   plain  (rgbnm_clip_adamw_wd_step)        lr, wd_factor and the bias corrections are arguments, computed on the host.
+//   scaled (rgbnm_clip_adamw_wd_step_scaled) under a loss scale kept on the device: GradScaler.unscale_, the inf / NaN check, the
+//          skipped step, torch._amp_update_scale_ and pipeline_utils.clip_gradscaler inside the two launches, no host sync.
+//   sched  (rgbnm_clip_adamw_wd_step_sched)  scaled, with lr and wd_factor looked up on the device too: no argument of the two
+//          launches changes from step to step, so a captured call replays.
+// The workspace carries, behind the NORM_BLOCKS partial sums, what one thread of the norm launch read from the state blocks, so
+// that the update launch (whose workgroup 0 rewrites them) never reads a scale, a step or an iter that has already been replaced:
+//   scaled and sched:
+//   [NORM_BLOCKS + 0] inv = (float)(1.0 / (double)scale)      [+ 1] step (int bits)      [+ 2] bc1, [+ 3] bc2_sqrt of step + 1
+//   [NORM_BLOCKS + 4] scale
+//   sched only:
+//   [NORM_BLOCKS + 5] lr = (float)lr_table[k]     [+ 6] wd_factor = (float)((lr_table[k] / base_lr) * weight_decay)
+//   [NORM_BLOCKS + 7] iter (int bits), k = min(iter, table_len - 1)
+// Bias corrections: an fp64 pow on the device, once per step (the host cannot know how many steps were skipped); the expressions
+// are those of rgbnm_clip_adamw_wd_step's host code.  wd_factor is one fp64 divide, one fp64 multiply and one rounding to fp32 --
+// FusedClipAdamWWD.step's host expression followed by the double -> float of its call; there is no sum next to the product, so
+// -ffp-contract=fast has nothing to fuse.
 constexpr int NORM_BLOCKS = 256;
+constexpr int SCALED_WS_FLOATS = NORM_BLOCKS + 5;
+constexpr int SCHED_WS_FLOATS = NORM_BLOCKS + 8;
 
-__global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g, long long n, float* __restrict__ part) {
+enum TailMode { TAIL_PLAIN, TAIL_SCALED, TAIL_SCHED };
+
+// part[blockIdx.x] = this workgroup's share of sum (g inv)^2 (UNSCALE) or sum g^2
+template <bool UNSCALE>
+__device__ __forceinline__ void sqnorm_body(const float* __restrict__ g, long long n, float* __restrict__ part, float inv) {
   __shared__ float red[4];
   float a = 0.f;
   // four strides per turn with their loads issued together (one workgroup per CU: a load per turn was 22 exposed latencies);
@@ -298,83 +323,9 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u)
-      if (i + u * STRIDE < n) a += v[u][0] * v[u][0] + v[u][1] * v[u][1] + v[u][2] * v[u][2] + v[u][3] * v[u][3];
-  }
-  a = wave_sum(a);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-struct AdamArgs {
-  float* p; const float* g; float* m; float* v; const unsigned char* wd_flag; const float* part; float* norm_out;
-  long long n;
-  float lr, beta1, beta2, eps, bc1, bc2_sqrt, wd_factor, max_norm;
-};
-
-__global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a) {
-  __shared__ float red[4];
-  __shared__ float coef_s;
-  {
-    float t = a.part[threadIdx.x];   // NORM_BLOCKS == blockDim.x
-    t = wave_sum(t);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const float total = sqrtf(red[0] + red[1] + red[2] + red[3]);
-      float c = a.max_norm > 0.f ? a.max_norm / (total + 1e-6f) : 1.f;
-      coef_s = c < 1.f ? c : 1.f;
-      if (blockIdx.x == 0 && a.norm_out) a.norm_out[0] = total;
-    }
-    __syncthreads();
-  }
-  const float coef = coef_s;
-  const float step = a.lr / a.bc1;
-  for (long long chunk = blockIdx.x; chunk * 256 < a.n; chunk += gridDim.x) {
-    const long long i = chunk * 256 + threadIdx.x;
-    const float g = a.g[i] * coef;
-    const float m = a.beta1 * a.m[i] + (1.f - a.beta1) * g;
-    const float v = a.beta2 * a.v[i] + (1.f - a.beta2) * g * g;
-    a.m[i] = m;
-    a.v[i] = v;
-    float p = a.p[i];
-    p -= step * (m / (sqrtf(v) / a.bc2_sqrt + a.eps));
-    if (a.wd_flag[chunk]) p -= a.wd_factor * p;
-    a.p[i] = p;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// The same tail under a loss scale kept on the device (rgbnm_clip_adamw_wd_step_scaled): GradScaler.unscale_, the inf / NaN
-// check, the skipped step, torch._amp_update_scale_ and pipeline_utils.clip_gradscaler inside the two launches, no host sync.
-// The workspace carries, behind the NORM_BLOCKS partial sums, what the first launch read from the state block, so that the
-// second launch (whose workgroup 0 rewrites the state) never reads a scale or a step that has already been replaced:
-//   [NORM_BLOCKS + 0] inv = (float)(1.0 / (double)scale)      [+ 1] step (int bits)      [+ 2] bc1, [+ 3] bc2_sqrt of step + 1
-//   [NORM_BLOCKS + 4] scale
-// Bias corrections: an fp64 pow on the device, once per step, by one thread of the first launch (the host cannot know how many
-// steps were skipped); the expressions are those of rgbnm_clip_adamw_wd_step's host code.
-constexpr int SCALED_WS_FLOATS = NORM_BLOCKS + 5;
-
-__global__ __launch_bounds__(256) void sqnorm_unscale_kernel(const float* __restrict__ g, long long n, float* __restrict__ part,
-                                                             const rgbnm_loss_scale_state* __restrict__ state, float beta1,
-                                                             float beta2) {
-  __shared__ float red[4];
-  const float scale = state->scale;
-  const float inv = (float)(1.0 / (double)scale);
-  float a = 0.f;
-  // sqnorm_kernel's loop on g * inv: the same four strides per turn, the same order of additions
-  constexpr long long STRIDE = (long long)NORM_BLOCKS * 256 * 4;
-  for (long long i = (blockIdx.x * 256LL + threadIdx.x) * 4; i < n; i += 4 * STRIDE) {
-    f32x4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const long long j = i + u * STRIDE;
-      v[u] = j < n ? *reinterpret_cast<const f32x4*>(g + j) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
       if (i + u * STRIDE < n) {
-        const float x0 = v[u][0] * inv, x1 = v[u][1] * inv, x2 = v[u][2] * inv, x3 = v[u][3] * inv;
+        float x0 = v[u][0], x1 = v[u][1], x2 = v[u][2], x3 = v[u][3];
+        if constexpr (UNSCALE) { x0 *= inv; x1 *= inv; x2 *= inv; x3 *= inv; }
         a += x0 * x0 + x1 * x1 + x2 * x2 + x3 * x3;
       }
   }
@@ -382,135 +333,43 @@ __global__ __launch_bounds__(256) void sqnorm_unscale_kernel(const float* __rest
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
   __syncthreads();
   if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    const int step = state->step;
-    const double t = (double)step + 1.0;
-    part[NORM_BLOCKS] = inv;
-    reinterpret_cast<int*>(part)[NORM_BLOCKS + 1] = step;
-    part[NORM_BLOCKS + 2] = (float)(1.0 - pow((double)beta1, t));
-    part[NORM_BLOCKS + 3] = (float)sqrt(1.0 - pow((double)beta2, t));
-    part[NORM_BLOCKS + 4] = scale;
-  }
 }
 
-struct ScaledArgs {
-  float* p; const float* g; float* m; float* v; const unsigned char* wd_flag; const float* part; float* norm_out;
-  rgbnm_loss_scale_state* state;
-  long long n;
-  double growth, backoff;
-  float lr, beta1, beta2, eps, wd_factor, max_norm, scale_min, scale_max;
-  int growth_interval;
-};
-
-__global__ __launch_bounds__(256) void adamw_scaled_kernel(ScaledArgs a) {
-  __shared__ float red[4];
-  __shared__ float coef_s;
-  __shared__ int finite_s;
-  {
-    float t = a.part[threadIdx.x];   // NORM_BLOCKS == blockDim.x
-    t = wave_sum(t);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const float total = sqrtf(red[0] + red[1] + red[2] + red[3]);
-      float c = a.max_norm > 0.f ? a.max_norm / (total + 1e-6f) : 1.f;
-      coef_s = c < 1.f ? c : 1.f;
-      finite_s = isfinite(total) ? 1 : 0;
-      if (blockIdx.x == 0 && a.norm_out) a.norm_out[0] = total;
-    }
-    __syncthreads();
-  }
-  const bool finite = finite_s != 0;
-  if (finite) {
-    const float coef = coef_s;
-    const float inv = a.part[NORM_BLOCKS], bc1 = a.part[NORM_BLOCKS + 2], bc2_sqrt = a.part[NORM_BLOCKS + 3];
-    const float step = a.lr / bc1;
-    for (long long chunk = blockIdx.x; chunk * 256 < a.n; chunk += gridDim.x) {
-      const long long i = chunk * 256 + threadIdx.x;
-      const float gu = a.g[i] * inv;               // unscale_ first,
-      const float g = gu * coef;                   // then the clip: two roundings
-      const float m = a.beta1 * a.m[i] + (1.f - a.beta1) * g;
-      const float v = a.beta2 * a.v[i] + (1.f - a.beta2) * g * g;
-      a.m[i] = m;
-      a.v[i] = v;
-      float p = a.p[i];
-      p -= step * (m / (sqrtf(v) / bc2_sqrt + a.eps));
-      if (a.wd_flag[chunk]) p -= a.wd_factor * p;
-      a.p[i] = p;
-    }
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {       // torch._amp_update_scale_, then clip_gradscaler (pipeline_utils.py:399-409)
-    rgbnm_loss_scale_state* st = a.state;
-    float scale = a.part[NORM_BLOCKS + 4];
-    int tracker = st->growth_tracker;
-    if (!finite) {
-      scale = (float)((double)scale * a.backoff);
-      tracker = 0;
-      st->skipped = st->skipped + 1;
-    } else {
-      st->step = reinterpret_cast<const int*>(a.part)[NORM_BLOCKS + 1] + 1;
-      if (++tracker == a.growth_interval) {
-        const float grown = (float)((double)scale * a.growth);
-        if (isfinite(grown)) scale = grown;
-        tracker = 0;
-      }
-    }
-    if (scale > a.scale_max) scale = a.scale_max;
-    if (scale < a.scale_min) scale = a.scale_min;
-    st->scale = scale;
-    st->growth_tracker = tracker;
-    st->found_inf = finite ? 0.f : 1.f;
-  }
+// the five workspace words of the scaled and sched modes (one thread of the norm launch)
+__device__ __forceinline__ void write_scale_words(float* __restrict__ part, const rgbnm_loss_scale_state* __restrict__ state,
+                                                  float scale, float inv, float beta1, float beta2) {
+  const int step = state->step;
+  const double t = (double)step + 1.0;
+  part[NORM_BLOCKS] = inv;
+  reinterpret_cast<int*>(part)[NORM_BLOCKS + 1] = step;
+  part[NORM_BLOCKS + 2] = (float)(1.0 - pow((double)beta1, t));
+  part[NORM_BLOCKS + 3] = (float)sqrt(1.0 - pow((double)beta2, t));
+  part[NORM_BLOCKS + 4] = scale;
 }
 
-// ------------------------------------------------------------------------------------------------
-// The scaled tail with the learning-rate schedule on the device too (rgbnm_clip_adamw_wd_step_sched): no argument of the two
-// launches changes from step to step, so a captured call replays.  The pair stands beside the scaled pair (whose kernels, names
-// and bits stay) and repeats its arithmetic statement for statement; what differs is where lr and wd_factor come from.  The
-// workspace carries, behind the scaled entry's five words:
-//   [NORM_BLOCKS + 5] lr = (float)lr_table[k]     [+ 6] wd_factor = (float)((lr_table[k] / base_lr) * weight_decay)
-//   [NORM_BLOCKS + 7] iter (int bits), k = min(iter, table_len - 1)
-// wd_factor is one fp64 divide, one fp64 multiply and one rounding to fp32 -- FusedClipAdamWWD.step's host expression followed by
-// the double -> float of its call; there is no sum next to the product, so -ffp-contract=fast has nothing to fuse.
-constexpr int SCHED_WS_FLOATS = NORM_BLOCKS + 8;
+__global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g, long long n, float* __restrict__ part) {
+  sqnorm_body<false>(g, n, part, 1.f);
+}
+
+__global__ __launch_bounds__(256) void sqnorm_unscale_kernel(const float* __restrict__ g, long long n, float* __restrict__ part,
+                                                             const rgbnm_loss_scale_state* __restrict__ state, float beta1,
+                                                             float beta2) {
+  const float scale = state->scale;
+  const float inv = (float)(1.0 / (double)scale);
+  sqnorm_body<true>(g, n, part, inv);
+  if (blockIdx.x == 0 && threadIdx.x == 0) write_scale_words(part, state, scale, inv, beta1, beta2);
+}
 
 __global__ __launch_bounds__(256) void sqnorm_unscale_sched_kernel(const float* __restrict__ g, long long n, float* __restrict__ part,
                                                                    const rgbnm_loss_scale_state* __restrict__ state,
                                                                    const rgbnm_lr_sched_state* __restrict__ sched,
                                                                    const double* __restrict__ lr_table, int table_len,
                                                                    double base_lr, double weight_decay, float beta1, float beta2) {
-  __shared__ float red[4];
   const float scale = state->scale;
   const float inv = (float)(1.0 / (double)scale);
-  float a = 0.f;
-  // sqnorm_unscale_kernel's loop: the same four strides per turn, the same order of additions
-  constexpr long long STRIDE = (long long)NORM_BLOCKS * 256 * 4;
-  for (long long i = (blockIdx.x * 256LL + threadIdx.x) * 4; i < n; i += 4 * STRIDE) {
-    f32x4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const long long j = i + u * STRIDE;
-      v[u] = j < n ? *reinterpret_cast<const f32x4*>(g + j) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (i + u * STRIDE < n) {
-        const float x0 = v[u][0] * inv, x1 = v[u][1] * inv, x2 = v[u][2] * inv, x3 = v[u][3] * inv;
-        a += x0 * x0 + x1 * x1 + x2 * x2 + x3 * x3;
-      }
-  }
-  a = wave_sum(a);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  sqnorm_body<true>(g, n, part, inv);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    const int step = state->step;
-    const double t = (double)step + 1.0;
-    part[NORM_BLOCKS] = inv;
-    reinterpret_cast<int*>(part)[NORM_BLOCKS + 1] = step;
-    part[NORM_BLOCKS + 2] = (float)(1.0 - pow((double)beta1, t));
-    part[NORM_BLOCKS + 3] = (float)sqrt(1.0 - pow((double)beta2, t));
-    part[NORM_BLOCKS + 4] = scale;
+    write_scale_words(part, state, scale, inv, beta1, beta2);
     const int iter = sched->iter;
     const int k = iter < 0 ? 0 : (iter < table_len ? iter : table_len - 1);     // an iter below 0 is not ours: stay in the table
     const double lr_d = lr_table[k];
@@ -521,20 +380,26 @@ __global__ __launch_bounds__(256) void sqnorm_unscale_sched_kernel(const float* 
   }
 }
 
-struct SchedArgs {
+// One argument block for the three modes; the marked fields are read only in the modes named.
+struct TailArgs {
   float* p; const float* g; float* m; float* v; const unsigned char* wd_flag; const float* part; float* norm_out;
-  rgbnm_loss_scale_state* state;
-  rgbnm_lr_sched_state* sched;
+  rgbnm_loss_scale_state* state;                     // scaled, sched
+  rgbnm_lr_sched_state* sched;                       // sched
   long long n;
-  double growth, backoff;
-  float beta1, beta2, eps, max_norm, scale_min, scale_max;
-  int growth_interval;
+  double growth, backoff;                            // scaled, sched
+  float beta1, beta2, eps, max_norm;
+  float scale_min, scale_max;                        // scaled, sched
+  int growth_interval;                               // scaled, sched
+  float lr, wd_factor;                               // plain, scaled (sched: from the table, through the workspace)
+  float bc1, bc2_sqrt;                               // plain (scaled, sched: from the state block's step, through the workspace)
 };
 
-__global__ __launch_bounds__(256) void adamw_sched_kernel(SchedArgs a) {
+template <TailMode MODE>
+__device__ __forceinline__ void adamw_body(const TailArgs& a) {
+  constexpr bool SCALED = MODE != TAIL_PLAIN;
   __shared__ float red[4];
   __shared__ float coef_s;
-  __shared__ int finite_s;
+  __shared__ int finite_s;           // (scaled modes only)
   {
     float t = a.part[threadIdx.x];   // NORM_BLOCKS == blockDim.x
     t = wave_sum(t);
@@ -544,21 +409,25 @@ __global__ __launch_bounds__(256) void adamw_sched_kernel(SchedArgs a) {
       const float total = sqrtf(red[0] + red[1] + red[2] + red[3]);
       float c = a.max_norm > 0.f ? a.max_norm / (total + 1e-6f) : 1.f;
       coef_s = c < 1.f ? c : 1.f;
-      finite_s = isfinite(total) ? 1 : 0;
+      if constexpr (SCALED) finite_s = isfinite(total) ? 1 : 0;
       if (blockIdx.x == 0 && a.norm_out) a.norm_out[0] = total;
     }
     __syncthreads();
   }
-  const bool finite = finite_s != 0;
-  const float lr = a.part[NORM_BLOCKS + 5], wd_factor = a.part[NORM_BLOCKS + 6];
+  bool finite = true;                // a non-finite norm skips the step under a loss scale; the plain step has no such check
+  if constexpr (SCALED) finite = finite_s != 0;
+  float lr = a.lr, wd_factor = a.wd_factor;
+  if constexpr (MODE == TAIL_SCHED) { lr = a.part[NORM_BLOCKS + 5]; wd_factor = a.part[NORM_BLOCKS + 6]; }
   if (finite) {
     const float coef = coef_s;
-    const float inv = a.part[NORM_BLOCKS], bc1 = a.part[NORM_BLOCKS + 2], bc2_sqrt = a.part[NORM_BLOCKS + 3];
+    float inv = 1.f, bc1 = a.bc1, bc2_sqrt = a.bc2_sqrt;
+    if constexpr (SCALED) { inv = a.part[NORM_BLOCKS]; bc1 = a.part[NORM_BLOCKS + 2]; bc2_sqrt = a.part[NORM_BLOCKS + 3]; }
     const float step = lr / bc1;
     for (long long chunk = blockIdx.x; chunk * 256 < a.n; chunk += gridDim.x) {
       const long long i = chunk * 256 + threadIdx.x;
-      const float gu = a.g[i] * inv;               // unscale_ first,
-      const float g = gu * coef;                   // then the clip: two roundings
+      float g = a.g[i];
+      if constexpr (SCALED) g = g * inv;           // unscale_ first, then the clip: two roundings
+      g = g * coef;
       const float m = a.beta1 * a.m[i] + (1.f - a.beta1) * g;
       const float v = a.beta2 * a.v[i] + (1.f - a.beta2) * g * g;
       a.m[i] = m;
@@ -569,32 +438,115 @@ __global__ __launch_bounds__(256) void adamw_sched_kernel(SchedArgs a) {
       a.p[i] = p;
     }
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {       // adamw_scaled_kernel's state update, then the schedule's
-    rgbnm_loss_scale_state* st = a.state;
-    float scale = a.part[NORM_BLOCKS + 4];
-    int tracker = st->growth_tracker;
-    if (!finite) {
-      scale = (float)((double)scale * a.backoff);
-      tracker = 0;
-      st->skipped = st->skipped + 1;
-    } else {
-      st->step = reinterpret_cast<const int*>(a.part)[NORM_BLOCKS + 1] + 1;
-      if (++tracker == a.growth_interval) {
-        const float grown = (float)((double)scale * a.growth);
-        if (isfinite(grown)) scale = grown;
+  if constexpr (SCALED) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {     // torch._amp_update_scale_, then clip_gradscaler (pipeline_utils.py:399-409)
+      rgbnm_loss_scale_state* st = a.state;
+      float scale = a.part[NORM_BLOCKS + 4];
+      int tracker = st->growth_tracker;
+      if (!finite) {
+        scale = (float)((double)scale * a.backoff);
         tracker = 0;
+        st->skipped = st->skipped + 1;
+      } else {
+        st->step = reinterpret_cast<const int*>(a.part)[NORM_BLOCKS + 1] + 1;
+        if (++tracker == a.growth_interval) {
+          const float grown = (float)((double)scale * a.growth);
+          if (isfinite(grown)) scale = grown;
+          tracker = 0;
+        }
+      }
+      if (scale > a.scale_max) scale = a.scale_max;
+      if (scale < a.scale_min) scale = a.scale_min;
+      st->scale = scale;
+      st->growth_tracker = tracker;
+      st->found_inf = finite ? 0.f : 1.f;
+      if constexpr (MODE == TAIL_SCHED) {
+        rgbnm_lr_sched_state* sc = a.sched;        // the scheduler steps every iteration, skipped or not (train.py:174-176)
+        sc->iter = reinterpret_cast<const int*>(a.part)[NORM_BLOCKS + 7] + 1;
+        sc->lr = lr;
+        sc->wd_factor = wd_factor;
       }
     }
-    if (scale > a.scale_max) scale = a.scale_max;
-    if (scale < a.scale_min) scale = a.scale_min;
-    st->scale = scale;
-    st->growth_tracker = tracker;
-    st->found_inf = finite ? 0.f : 1.f;
-    rgbnm_lr_sched_state* sc = a.sched;            // the scheduler steps every iteration, skipped or not (train.py:174-176)
-    sc->iter = reinterpret_cast<const int*>(a.part)[NORM_BLOCKS + 7] + 1;
-    sc->lr = lr;
-    sc->wd_factor = wd_factor;
   }
+}
+
+__global__ __launch_bounds__(256) void adamw_kernel(TailArgs a) { adamw_body<TAIL_PLAIN>(a); }
+__global__ __launch_bounds__(256) void adamw_scaled_kernel(TailArgs a) { adamw_body<TAIL_SCALED>(a); }
+__global__ __launch_bounds__(256) void adamw_sched_kernel(TailArgs a) { adamw_body<TAIL_SCHED>(a); }
+
+// ------------------------------------------------------------------------------------------------
+// Host launchers shared by the entries below; every entry checks its own arguments first.
+
+TailArgs tail_args(float* p, const float* g, float* m, float* v, const unsigned char* wd_flag, long long n, float beta1, float beta2,
+                   float eps, float max_norm, float* norm_out, void* workspace) {
+  TailArgs a = {};
+  a.p = p; a.g = g; a.m = m; a.v = v; a.wd_flag = wd_flag; a.part = (const float*)workspace; a.norm_out = norm_out; a.n = n;
+  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.max_norm = max_norm;
+  return a;
+}
+
+void set_loss_scale(TailArgs& a, rgbnm_loss_scale_state* state, double growth, double backoff, int growth_interval, float scale_min,
+                    float scale_max) {
+  a.state = state; a.growth = growth; a.backoff = backoff; a.growth_interval = growth_interval;
+  a.scale_min = scale_min; a.scale_max = scale_max;
+}
+
+// the two launches of the tail; the schedule's table arguments are read in sched mode only
+int launch_tail(TailMode mode, const TailArgs& a, hipStream_t st, const double* lr_table = nullptr, int table_len = 0,
+                double base_lr = 0.0, double weight_decay = 0.0) {
+  float* part = const_cast<float*>(a.part);
+  // algorithmic bytes (SURVEY.md 8d): 28 B per parameter (p, g, m, v read; p, m, v written) + the gradient once more for the norm
+  const int tslot = rgbnm_trace_begin(TR_OPT, 0.0, 32.0 * (double)a.n, st);
+  const dim3 nblk(NORM_BLOCKS), blk(256);
+  if (mode == TAIL_PLAIN) hipLaunchKernelGGL(sqnorm_kernel, nblk, blk, 0, st, a.g, a.n, part);
+  else if (mode == TAIL_SCALED) hipLaunchKernelGGL(sqnorm_unscale_kernel, nblk, blk, 0, st, a.g, a.n, part, a.state, a.beta1, a.beta2);
+  else hipLaunchKernelGGL(sqnorm_unscale_sched_kernel, nblk, blk, 0, st, a.g, a.n, part, a.state, a.sched, lr_table, table_len,
+                          base_lr, weight_decay, a.beta1, a.beta2);
+  LAUNCH_CHECK();
+  void (*update)(TailArgs) = mode == TAIL_PLAIN ? adamw_kernel : mode == TAIL_SCALED ? adamw_scaled_kernel : adamw_sched_kernel;
+  hipLaunchKernelGGL(update, dim3((unsigned)min(4096LL, a.n / 256)), blk, 0, st, a);
+  rgbnm_trace_end(tslot, st);
+  LAUNCH_CHECK();
+  return RGBNM_OK;
+}
+
+// mix_lam == null: soft or hard targets as given; else hard labels mixed by roll-by-one on the fly
+int launch_softxent_loss(const float* logits, const float* soft, const long long* hard, const float* mix_lam, float* loss_rows,
+                         float* row_stats, float* loss, unsigned* ticket, int B, int C, void* stream) {
+  hipLaunchKernelGGL(softxent_loss_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, soft, hard, loss_rows, row_stats,
+                     loss, ticket, C, mix_lam);
+  LAUNCH_CHECK();
+  return RGBNM_OK;
+}
+
+int launch_softxent_grad(int dl_dtype, const float* logits, const float* soft, const long long* hard, const float* mix_lam,
+                         const float* row_stats, const float* gout_dev, void* dlogits, int B, int C, float grad_scale, void* stream) {
+#define SG(T) hipLaunchKernelGGL((softxent_grad_kernel<T>), dim3(B), dim3(256), 0, (hipStream_t)stream, logits, soft, hard, row_stats, gout_dev, (T*)dlogits, C, grad_scale, mix_lam)
+  if (dl_dtype == DT_BF16) SG(bf16);
+  else if (dl_dtype == DT_F32) SG(float);
+  else if (dl_dtype == DT_F16) SG(f16);
+  else return RGBNM_EINVAL;
+#undef SG
+  LAUNCH_CHECK();
+  return RGBNM_OK;
+}
+
+// every (in, out) pair mixup_kernel is built for; rgbnm_mixup refuses the fp16 ones before it comes here
+int launch_mixup(int in_dtype, int out_dtype, const void* in, void* out, const float* lam_dev, int B, long long per_sample,
+                 void* stream) {
+  if (!in || !out || !lam_dev || B <= 0 || per_sample <= 0 || (per_sample & 3)) return RGBNM_EINVAL;
+  const long long n = (long long)B * per_sample;
+  const dim3 grid((unsigned)min(4096LL, cdivl(n, 1024))), blk(256);
+#define MX(TI, TO) hipLaunchKernelGGL((mixup_kernel<TI, TO>), grid, blk, 0, (hipStream_t)stream, (const TI*)in, (TO*)out, lam_dev, B, per_sample)
+  if (in_dtype == DT_F32 && out_dtype == DT_F32) MX(float, float);
+  else if (in_dtype == DT_F32 && out_dtype == DT_BF16) MX(float, bf16);
+  else if (in_dtype == DT_BF16 && out_dtype == DT_BF16) MX(bf16, bf16);
+  else if (in_dtype == DT_F32 && out_dtype == DT_F16) MX(float, f16);
+  else if (in_dtype == DT_F16 && out_dtype == DT_F16) MX(f16, f16);
+  else return RGBNM_EINVAL;
+#undef MX
+  LAUNCH_CHECK();
+  return RGBNM_OK;
 }
 
 }  // namespace
@@ -650,81 +602,36 @@ int rgbnm_softxent(int dl_dtype, const float* logits, const float* soft_target, 
 int rgbnm_softxent_loss(const float* logits, const float* soft_target, const long long* hard_target, float* loss_rows,
                         float* row_stats, float* loss, unsigned* ticket, int B, int C, void* stream) {
   if (!logits || (!soft_target && !hard_target) || !loss_rows || !row_stats || !loss || !ticket || B <= 0 || C <= 0) return RGBNM_EINVAL;
-  hipLaunchKernelGGL(softxent_loss_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, soft_target, hard_target, loss_rows,
-                     row_stats, loss, ticket, C);
-  LAUNCH_CHECK();
-  return RGBNM_OK;
+  return launch_softxent_loss(logits, soft_target, hard_target, nullptr, loss_rows, row_stats, loss, ticket, B, C, stream);
 }
 
 int rgbnm_softxent_grad(int dl_dtype, const float* logits, const float* soft_target, const long long* hard_target,
                         const float* row_stats, const float* gout_dev, void* dlogits, int B, int C, float grad_scale, void* stream) {
   if (!logits || (!soft_target && !hard_target) || !row_stats || !dlogits || B <= 0 || C <= 0) return RGBNM_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  if (dl_dtype == DT_BF16)
-    hipLaunchKernelGGL((softxent_grad_kernel<bf16>), dim3(B), dim3(256), 0, st, logits, soft_target, hard_target, row_stats, gout_dev, (bf16*)dlogits, C, grad_scale);
-  else if (dl_dtype == DT_F32)
-    hipLaunchKernelGGL((softxent_grad_kernel<float>), dim3(B), dim3(256), 0, st, logits, soft_target, hard_target, row_stats, gout_dev, (float*)dlogits, C, grad_scale);
-  else if (dl_dtype == DT_F16)
-    hipLaunchKernelGGL((softxent_grad_kernel<f16>), dim3(B), dim3(256), 0, st, logits, soft_target, hard_target, row_stats, gout_dev, (f16*)dlogits, C, grad_scale);
-  else return RGBNM_EINVAL;
-  LAUNCH_CHECK();
-  return RGBNM_OK;
+  return launch_softxent_grad(dl_dtype, logits, soft_target, hard_target, nullptr, row_stats, gout_dev, dlogits, B, C, grad_scale, stream);
 }
 
 int rgbnm_softxent_loss_mix(const float* logits, const long long* labels, const float* mix_lam, float* loss_rows, float* row_stats,
                             float* loss, unsigned* ticket, int B, int C, void* stream) {
   if (!logits || !labels || !mix_lam || !loss_rows || !row_stats || !loss || !ticket || B <= 0 || C <= 0) return RGBNM_EINVAL;
-  hipLaunchKernelGGL(softxent_loss_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, (const float*)nullptr, labels, loss_rows,
-                     row_stats, loss, ticket, C, mix_lam);
-  LAUNCH_CHECK();
-  return RGBNM_OK;
+  return launch_softxent_loss(logits, nullptr, labels, mix_lam, loss_rows, row_stats, loss, ticket, B, C, stream);
 }
 
 int rgbnm_softxent_grad_mix(int dl_dtype, const float* logits, const long long* labels, const float* mix_lam, const float* row_stats,
                             const float* gout_dev, void* dlogits, int B, int C, float grad_scale, void* stream) {
   if (!logits || !labels || !mix_lam || !row_stats || !dlogits || B <= 0 || C <= 0) return RGBNM_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  if (dl_dtype == DT_BF16)
-    hipLaunchKernelGGL((softxent_grad_kernel<bf16>), dim3(B), dim3(256), 0, st, logits, (const float*)nullptr, labels, row_stats, gout_dev, (bf16*)dlogits, C, grad_scale, mix_lam);
-  else if (dl_dtype == DT_F32)
-    hipLaunchKernelGGL((softxent_grad_kernel<float>), dim3(B), dim3(256), 0, st, logits, (const float*)nullptr, labels, row_stats, gout_dev, (float*)dlogits, C, grad_scale, mix_lam);
-  else if (dl_dtype == DT_F16)
-    hipLaunchKernelGGL((softxent_grad_kernel<f16>), dim3(B), dim3(256), 0, st, logits, (const float*)nullptr, labels, row_stats, gout_dev, (f16*)dlogits, C, grad_scale, mix_lam);
-  else return RGBNM_EINVAL;
-  LAUNCH_CHECK();
-  return RGBNM_OK;
+  return launch_softxent_grad(dl_dtype, logits, nullptr, labels, mix_lam, row_stats, gout_dev, dlogits, B, C, grad_scale, stream);
 }
 
 int rgbnm_mixup(int in_dtype, int out_dtype, const void* in, void* out, const float* lam_dev, int B,
                 long long per_sample, void* stream) {
-  if (!in || !out || !lam_dev || B <= 0 || per_sample <= 0 || (per_sample & 3)) return RGBNM_EINVAL;
-  const long long n = (long long)B * per_sample;
-  const dim3 grid((unsigned)min(4096LL, cdivl(n, 1024))), blk(256);
-  hipStream_t st = (hipStream_t)stream;
-#define MX(TI, TO) hipLaunchKernelGGL((mixup_kernel<TI, TO>), grid, blk, 0, st, (const TI*)in, (TO*)out, lam_dev, B, per_sample)
-  if (in_dtype == DT_F32 && out_dtype == DT_F32) MX(float, float);
-  else if (in_dtype == DT_F32 && out_dtype == DT_BF16) MX(float, bf16);
-  else if (in_dtype == DT_BF16 && out_dtype == DT_BF16) MX(bf16, bf16);
-  else return RGBNM_EINVAL;
-#undef MX
-  LAUNCH_CHECK();
-  return RGBNM_OK;
+  if (in_dtype == DT_F16 || out_dtype == DT_F16) return RGBNM_EINVAL;      // (the fp16 pairs came later, as rgbnm_mixup_any)
+  return launch_mixup(in_dtype, out_dtype, in, out, lam_dev, B, per_sample, stream);
 }
 
 int rgbnm_mixup_any(int in_dtype, int out_dtype, const void* in, void* out, const float* lam_dev, int B,
                     long long per_sample, void* stream) {
-  if (out_dtype != DT_F16) return in_dtype == DT_F16 ? RGBNM_EINVAL : rgbnm_mixup(in_dtype, out_dtype, in, out, lam_dev, B, per_sample, stream);
-  if (!in || !out || !lam_dev || B <= 0 || per_sample <= 0 || (per_sample & 3)) return RGBNM_EINVAL;
-  const long long n = (long long)B * per_sample;
-  const dim3 grid((unsigned)min(4096LL, cdivl(n, 1024))), blk(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (in_dtype == DT_F32)
-    hipLaunchKernelGGL((mixup_kernel<float, f16>), grid, blk, 0, st, (const float*)in, (f16*)out, lam_dev, B, per_sample);
-  else if (in_dtype == DT_F16)
-    hipLaunchKernelGGL((mixup_kernel<f16, f16>), grid, blk, 0, st, (const f16*)in, (f16*)out, lam_dev, B, per_sample);
-  else return RGBNM_EINVAL;
-  LAUNCH_CHECK();
-  return RGBNM_OK;
+  return launch_mixup(in_dtype, out_dtype, in, out, lam_dev, B, per_sample, stream);
 }
 
 int rgbnm_mixup_target(const long long* labels, float* target, const float* lam_dev, int B, int C, void* stream) {
@@ -742,23 +649,11 @@ int rgbnm_clip_adamw_wd_step(float* p, const float* g, float* m, float* v, const
                              float max_norm, float* norm_out, void* workspace, size_t workspace_bytes, void* stream) {
   if (!p || !g || !m || !v || !wd_flag_per_256 || !workspace || n <= 0 || (n & 255) || step < 1) return RGBNM_EINVAL;
   if (workspace_bytes < NORM_BLOCKS * sizeof(float)) return RGBNM_EWORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  float* part = (float*)workspace;
-  // algorithmic bytes (SURVEY.md 8d): 28 B per parameter (p, g, m, v read; p, m, v written) + the gradient once more for the norm
-  const int tslot = rgbnm_trace_begin(TR_OPT, 0.0, 32.0 * (double)n, st);
-  hipLaunchKernelGGL(sqnorm_kernel, dim3(NORM_BLOCKS), dim3(256), 0, st, g, n, part);
-  LAUNCH_CHECK();
-  AdamArgs a;
-  a.p = p; a.g = g; a.m = m; a.v = v; a.wd_flag = wd_flag_per_256; a.part = part; a.norm_out = norm_out; a.n = n;
-  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+  TailArgs a = tail_args(p, g, m, v, wd_flag_per_256, n, beta1, beta2, eps, max_norm, norm_out, workspace);
+  a.lr = lr; a.wd_factor = wd_factor;
   a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
   a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-  a.wd_factor = wd_factor; a.max_norm = max_norm;
-  const int grid = (int)min(4096LL, n / 256);
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, st, a);
-  rgbnm_trace_end(tslot, st);
-  LAUNCH_CHECK();
-  return RGBNM_OK;
+  return launch_tail(TAIL_PLAIN, a, (hipStream_t)stream);
 }
 
 size_t rgbnm_clip_adamw_wd_scaled_workspace(void) { return SCALED_WS_FLOATS * sizeof(float); }
@@ -771,21 +666,10 @@ int rgbnm_clip_adamw_wd_step_scaled(float* p, const float* g, float* m, float* v
   if (!p || !g || !m || !v || !wd_flag_per_256 || !state || !workspace || n <= 0 || (n & 255)) return RGBNM_EINVAL;
   if (growth_interval < 1 || !(growth_factor > 0.0) || !(backoff_factor > 0.0) || !(scale_min <= scale_max)) return RGBNM_EINVAL;
   if (workspace_bytes < SCALED_WS_FLOATS * sizeof(float)) return RGBNM_EWORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  float* part = (float*)workspace;
-  const int tslot = rgbnm_trace_begin(TR_OPT, 0.0, 32.0 * (double)n, st);      // the bytes of rgbnm_clip_adamw_wd_step
-  hipLaunchKernelGGL(sqnorm_unscale_kernel, dim3(NORM_BLOCKS), dim3(256), 0, st, g, n, part, state, beta1, beta2);
-  LAUNCH_CHECK();
-  ScaledArgs a;
-  a.p = p; a.g = g; a.m = m; a.v = v; a.wd_flag = wd_flag_per_256; a.part = part; a.norm_out = norm_out; a.state = state; a.n = n;
-  a.growth = growth_factor; a.backoff = backoff_factor;
-  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd_factor = wd_factor; a.max_norm = max_norm;
-  a.scale_min = scale_min; a.scale_max = scale_max; a.growth_interval = growth_interval;
-  const int grid = (int)min(4096LL, n / 256);
-  hipLaunchKernelGGL(adamw_scaled_kernel, dim3(grid), dim3(256), 0, st, a);
-  rgbnm_trace_end(tslot, st);
-  LAUNCH_CHECK();
-  return RGBNM_OK;
+  TailArgs a = tail_args(p, g, m, v, wd_flag_per_256, n, beta1, beta2, eps, max_norm, norm_out, workspace);
+  a.lr = lr; a.wd_factor = wd_factor;
+  set_loss_scale(a, state, growth_factor, backoff_factor, growth_interval, scale_min, scale_max);
+  return launch_tail(TAIL_SCALED, a, (hipStream_t)stream);
 }
 
 size_t rgbnm_clip_adamw_wd_sched_workspace(void) { return SCHED_WS_FLOATS * sizeof(float); }
@@ -800,23 +684,10 @@ int rgbnm_clip_adamw_wd_step_sched(float* p, const float* g, float* m, float* v,
   if (growth_interval < 1 || !(growth_factor > 0.0) || !(backoff_factor > 0.0) || !(scale_min <= scale_max)) return RGBNM_EINVAL;
   if (!lr_table || !sched || table_len < 1 || !(base_lr > 0.0) || !(weight_decay >= 0.0)) return RGBNM_EINVAL;
   if (workspace_bytes < SCHED_WS_FLOATS * sizeof(float)) return RGBNM_EWORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  float* part = (float*)workspace;
-  const int tslot = rgbnm_trace_begin(TR_OPT, 0.0, 32.0 * (double)n, st);      // the bytes of rgbnm_clip_adamw_wd_step
-  hipLaunchKernelGGL(sqnorm_unscale_sched_kernel, dim3(NORM_BLOCKS), dim3(256), 0, st, g, n, part, state, sched, lr_table,
-                     table_len, base_lr, weight_decay, beta1, beta2);
-  LAUNCH_CHECK();
-  SchedArgs a;
-  a.p = p; a.g = g; a.m = m; a.v = v; a.wd_flag = wd_flag_per_256; a.part = part; a.norm_out = norm_out; a.state = state;
-  a.sched = sched; a.n = n;
-  a.growth = growth_factor; a.backoff = backoff_factor;
-  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.max_norm = max_norm;
-  a.scale_min = scale_min; a.scale_max = scale_max; a.growth_interval = growth_interval;
-  const int grid = (int)min(4096LL, n / 256);
-  hipLaunchKernelGGL(adamw_sched_kernel, dim3(grid), dim3(256), 0, st, a);
-  rgbnm_trace_end(tslot, st);
-  LAUNCH_CHECK();
-  return RGBNM_OK;
+  TailArgs a = tail_args(p, g, m, v, wd_flag_per_256, n, beta1, beta2, eps, max_norm, norm_out, workspace);
+  set_loss_scale(a, state, growth_factor, backoff_factor, growth_interval, scale_min, scale_max);
+  a.sched = sched;
+  return launch_tail(TAIL_SCHED, a, (hipStream_t)stream, lr_table, table_len, base_lr, weight_decay);
 }
 
 }  // extern "C"

@@ -113,6 +113,12 @@ class FusedClipAdamWWD(Optimizer):
             if self._sched is None:    # (with a schedule attached the block stays the truth: a captured step goes on counting there)
                 self._dev_step = None
 
+    def _hand_step_to(self, s):
+        """Make DeviceLossScaler `s`'s state block the holder of the Adam step count (syncs if another block held it, uploads)."""
+        self._read_back_step()                         # (another scaler's count, if there was one)
+        s._set_device_step(self._step)
+        self._dev_step = s
+
     def state_dict(self):
         self._ensure()
         self._read_back_step()
@@ -203,9 +209,7 @@ class FusedClipAdamWWD(Optimizer):
             s = loss_scaler
             state = s._device_state(m._flat.device)
             if self._dev_step is not s:
-                self._read_back_step()                 # (another scaler's count, if there was one)
-                s._set_device_step(self._step)
-                self._dev_step = s
+                self._hand_step_to(s)
             L.check(L.lib().rgbnm_clip_adamw_wd_step_scaled(
                 m._flat.data_ptr(), gptr, self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr(),
                 m._wd_flags.data_ptr(), m._flat.numel(), g["lr"], g["betas"][0], g["betas"][1], g["eps"],
@@ -223,9 +227,7 @@ class FusedClipAdamWWD(Optimizer):
                 raise RuntimeError("the first step() with an attached schedule (or after a change of loss scaler) uploads the "
                                    "Adam step count and cannot be captured: take one eager step first")
             s._device_state(self._m._flat.device)
-            self._read_back_step()                     # (another scaler's count, if there was one)
-            s._set_device_step(self._step)
-            self._dev_step = s
+            self._hand_step_to(s)
         return s
 
     def _step_sched(self, loss_scaler):

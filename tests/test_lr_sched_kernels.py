@@ -2,8 +2,9 @@
 conventions of test_loss_scale_kernels.py: guarded p / m / v / flags / workspace / norm_out and both state blocks, NaN behind the
 gradients, a workspace of exactly the size asked for, the device kernels counted by name.
 
-The reference is the scaled entry itself.  The new entry performs rgbnm_clip_adamw_wd_step_scaled's arithmetic on an (lr,
-wd_factor) pair formed on the device by the IEEE operations the host performs for that entry today -- fp32(lr_d) and
+The reference is the scaled entry itself.  Both kernel pairs are instances of one norm body and one update body (the sched
+instance differs in where lr and wd_factor come from), so this entry performs rgbnm_clip_adamw_wd_step_scaled's arithmetic on an (lr,
+wd_factor) pair formed on the device by the IEEE operations the host performs for that entry -- fp32(lr_d) and
 fp32((lr_d / base_lr) * weight_decay), one fp64 divide, one fp64 multiply, one rounding -- so a twin set of buffers stepped by the
 scaled entry with those two floats (formed here in numpy float64) must hold the same BITS after every call: p, m, v, norm_out and
 the whole loss-scale block.  No tolerance anywhere in that comparison.
