@@ -30,6 +30,8 @@ are that file's constants, measured there on the per-operation kernels and NOT r
   of the GEMM element itself) is propagated through it in fp64:
       row i:  rstd (|g_i delta_i| + mean_j |g_j delta_j| + |xh_i| mean_j |g_j delta_j xh_j|),
   and the same delta enters the dgamma / dbeta sums: sum_t delta_tj |xh_tj| and sum_t delta_tj.
+- logit error (logit=True, the cases built with make_params(offset=...) only): logit_err below, through the softmax and through
+  P = exp(S - lse) / dS of the backward; derived in tests/regime_ref.py.  Every other case keeps the bounds it had.
 - table GELU: the table holds the library's own GELU arithmetic for every bf16 input, so the GELU terms apply unchanged; the
   documented exception (bf16-denormal pre-activations) is excluded by the inputs: no |pre| below 2^-120 (asserted, no mask).
 """
@@ -91,10 +93,19 @@ def _n(shape, seed, scale=1.0):
     return torch.from_numpy(detfill.normalish(tuple(shape), seed)) * scale
 
 
-def make_params(depth, seed=1, e=E, heads=HEADS):
+def offset_k0(scale):
+    """b of the large-|lse| regime (tests/regime_ref.py): the smallest power of two with 32 b scale >= 90 (90 <= 32 b scale <= 180)."""
+    b = 2.0 ** math.ceil(math.log2(90.0 / (32.0 * scale)))
+    assert 90.0 <= 32.0 * b * scale <= 180.0
+    return b
+
+
+def make_params(depth, seed=1, e=E, heads=HEADS, offset=None):
     """Block parameters on the CPU: bf16 weights (de-interleaved qkv), fp32 biases and LayerNorm parameters.  Regimes, each block:
     head 0's q and k rows x 4 (logit spread >> ln 196: near one-hot attention rows); fc1 biases 0..7 = -24, 8..15 = +10 (the GELU
-    table's negative and positive tails -- measured ends on the MI355X: -16 and 4 --; the rest sits in its window)."""
+    table's negative and positive tails -- measured ends on the MI355X: -16 and 4 --; the rest sits in its window).
+    offset (None, +1 or -1): row d = 0 of every head's q and k weight is zero and the biases there are 32 and +-b (offset_k0), so
+    q[:, 0] = 32 and k[:, 0] = +-b in every head, exactly: every logit, and lse, carries 32 b scale = +-90 .. 180 scaled units."""
     out = []
     for i in range(depth):
         s = 1000 * seed + 40 * i
@@ -102,11 +113,18 @@ def make_params(depth, seed=1, e=E, heads=HEADS):
         wqkv = _n((3 * inner, e), s + 5, sw)
         wqkv[0:64] *= 4.0
         wqkv[inner:inner + 64] *= 4.0
+        bqkv = _n((3 * inner,), s + 6, 0.2)
+        if offset is not None:
+            d0 = torch.arange(heads) * 64
+            wqkv[d0] = 0.0
+            wqkv[inner + d0] = 0.0
+            bqkv[d0] = 32.0
+            bqkv[inner + d0] = offset * offset_k0(1.0 / math.sqrt(e))
         b1 = _n((hid,), s + 10, 0.2)
         b1[0:8] = -24.0
         b1[8:16] = 10.0
         out.append(dict(ln1_g=1 + _n((e,), s + 1, 0.2), ln1_b=_n((e,), s + 2, 0.2), ln2_g=1 + _n((e,), s + 3, 0.2),
-                        ln2_b=_n((e,), s + 4, 0.2), wqkv=wqkv.to(BF16), bqkv=_n((3 * inner,), s + 6, 0.2),
+                        ln2_b=_n((e,), s + 4, 0.2), wqkv=wqkv.to(BF16), bqkv=bqkv,
                         wproj=_n((e, inner), s + 7, 0.07 * math.sqrt(E / inner)).to(BF16), bproj=_n((e,), s + 8, 0.2),
                         w1=_n((hid, e), s + 9, sw).to(BF16), b1=b1, w2=_n((e, hid), s + 11, 0.04 * math.sqrt(E / e)).to(BF16),
                         b2=_n((e,), s + 12, 0.2)))
@@ -169,21 +187,39 @@ def _flat(t):                                       # [B, H, N, 64] -> [B * N, I
     return t.permute(0, 2, 1, 3).reshape(-1, t.shape[1] * 64)
 
 
-def attn_fwd(qkv, B, scale=SCALE):
-    """qkv [B * N, 3 I] fp64 -> dict(out, outmag [B * N, I]; lse, lsemag [B, H, N]; pmax [B, H, N])."""
+LOGIT_C = 64        # fp32 roundings a term of the 64-term score accumulation can meet (tests/regime_ref.py, C_D)
+
+
+def logit_err(S, A, lse):
+    """|error| of a kernel's scaled logit, per element (tests/regime_ref.py derives it): LOGIT_C u scale |q|.|k| + 4 u (|S| + |lse|);
+    A = scale |q| |k|^T.  At unit-scale logits it is far below u_P; with a common offset of +-100 .. 150 it is the error."""
+    return LOGIT_C * U * A + 4 * U * (S.abs() + lse.abs()[..., None])
+
+
+def attn_fwd(qkv, B, scale=SCALE, logit=False):
+    """qkv [B * N, 3 I] fp64 -> dict(out, outmag [B * N, I]; lse, lsemag [B, H, N]; pmax [B, H, N]).  logit: also the logit error
+    through the softmax, out_logit = (P o e)|v| + (sum_j P e) P|v| and lse_logit = sum_j P e."""
     q, k, v = _heads(qkv, B, 3)
     S = (q @ k.transpose(-1, -2)) * scale
     lse = torch.logsumexp(S, -1)
     P = torch.exp(S - lse[..., None])
-    lmag = (scale * (q.abs() @ k.abs().transpose(-1, -2))).amax(-1) * 64 + lse.abs() + 1
-    return dict(out=_flat(P @ v), outmag=_flat(P @ v.abs()), lse=lse, lsemag=lmag, pmax=P.amax(-1))
+    A = scale * (q.abs() @ k.abs().transpose(-1, -2))
+    lmag = A.amax(-1) * 64 + lse.abs() + 1
+    r = dict(out=_flat(P @ v), outmag=_flat(P @ v.abs()), lse=lse, lsemag=lmag, pmax=P.amax(-1), out_logit=None, lse_logit=None)
+    if logit:
+        Pe = P * logit_err(S, A, lse)
+        spe = Pe.sum(-1, keepdim=True)
+        r["out_logit"], r["lse_logit"] = _flat(Pe @ v.abs() + spe * (P @ v.abs())), spe[..., 0]
+    return r
 
 
-def attn_bwd(qkv, attn, dattn, lse, B, scale=SCALE, delta=None):
+def attn_bwd(qkv, attn, dattn, lse, B, scale=SCALE, delta=None, logit=False):
     """From the STORED qkv, attention output, its gradient and lse [B, H, N]: dict(dq, dk, dv: (ref, mag, prop) each [B * N, I]).
-    delta (|error| of every dattn element, or None): the backward is linear in dattn, so prop = the same sums on |delta|."""
+    delta (|error| of every dattn element, or None): the backward is linear in dattn, so prop = the same sums on |delta|.
+    logit: out["logit"] = the logit error through P = exp(S - lse) and dS = P (dP - D), summed like the gradients."""
     q, k, v = _heads(qkv, B, 3)
-    P = torch.exp((q @ k.transpose(-1, -2)) * scale - lse[..., None])
+    S = (q @ k.transpose(-1, -2)) * scale
+    P = torch.exp(S - lse[..., None])
     dO, O = _heads(dattn, B)[0], _heads(attn, B)[0]
     D = (dO * O).sum(-1, keepdim=True)
     dS = P * (dO @ v.transpose(-1, -2) - D)
@@ -195,6 +231,12 @@ def attn_bwd(qkv, attn, dattn, lse, B, scale=SCALE, delta=None):
                dv=[_flat(Pt @ dO), _flat(Pt @ dO.abs()), None])
     tok = lambda t: _flat(t.abs().sum(2, keepdim=True).expand_as(t))           # noqa: E731  (sums over the image's tokens)
     out["under"] = dict(dq=scale * tok(k), dk=scale * tok(q), dv=tok(dO))
+    out["logit"] = None
+    if logit:
+        Pe = P * logit_err(S, scale * (q.abs() @ k.abs().transpose(-1, -2)), lse)
+        EdS = Pe * (dO @ v.transpose(-1, -2) - D).abs()
+        out["logit"] = dict(dq=_flat(scale * EdS @ k.abs()), dk=_flat(scale * EdS.transpose(-1, -2) @ q.abs()),
+                            dv=_flat(Pe.transpose(-1, -2) @ dO.abs()))
     if delta is not None:
         dl = _heads(delta, B)[0]
         pdS = P * (dl @ v.abs().transpose(-1, -2) + (dl * O.abs()).sum(-1, keepdim=True))
@@ -316,15 +358,16 @@ def check_gelu(worst, where, xn2, w1, b1, gl, u, B=None, f=None):
     return pre
 
 
-def check_attn_fwd(worst, where, qkv, attn, lse, B, scale=SCALE):
-    r = attn_fwd(d64(qkv), B, scale)
-    _chk(worst, "attn", attn, r["out"], r["outmag"], ATTN_C["out"] * u_p(attn.dtype), where, B=B, tile=(NTOK, 64))
+def check_attn_fwd(worst, where, qkv, attn, lse, B, scale=SCALE, logit=False):
+    r = attn_fwd(d64(qkv), B, scale, logit)
+    _chk(worst, "attn", attn, r["out"], r["outmag"], ATTN_C["out"] * u_p(attn.dtype), where, extra=r["out_logit"], B=B, tile=(NTOK, 64))
     # lse = mx * scale + __logf(sum) (vit_chain.hip:697; attention_v2.hip alike): LSE_ULPS above
-    _cb(worst, "lse", lse.reshape(r["lse"].shape), r["lse"], r["lsemag"], F32, LSE_ULPS, ATTN_C["lse"] * U, where + " lse")
+    _cb(worst, "lse", lse.reshape(r["lse"].shape), r["lse"], r["lsemag"], F32, LSE_ULPS, ATTN_C["lse"] * U, where + " lse",
+        extra=r["lse_logit"])
     return r
 
 
-def check_block_fwd(worst, where, P, A, B, inter=False, nxt=None, f=None):
+def check_block_fwd(worst, where, P, A, B, inter=False, nxt=None, f=None, logit=False):
     """Stages 1 - 7 (8 with nxt = (next block's parameters, its xn1 / mean1 / rstd1 dict)) of one block, each from the tensors
     the run itself stored.  P, A: dicts of tensors on one device.  Returns what the regime assertions need.
     f: None, or the dropout factors {0: [M, E], 1: [M, 4 E], 2: [M, E]} (fp64, keep . scale) of rgbnm_vit_block_fwd_drop."""
@@ -335,8 +378,9 @@ def check_block_fwd(worst, where, P, A, B, inter=False, nxt=None, f=None):
     ref, mag = linear(d64(A["xn1"]), d64(P["wqkv"]), d64(P["bqkv"]))
     e = A["x_in"].shape[1]
     _chk(worst, "qkv", A["qkv"], ref, mag, e * U, where, B=B, tile=(32, 64))
-    r = check_attn_fwd(worst, where, A["qkv"], A["attn"], A["lse"], B, 1.0 / math.sqrt(e))
+    r = check_attn_fwd(worst, where, A["qkv"], A["attn"], A["lse"], B, 1.0 / math.sqrt(e), logit)
     info["onehot_rows"] = int((r["pmax"] > 0.9).sum())
+    info["lse_absmin"] = float(r["lse"].abs().min())
     del r, ref, mag
     check_res(worst, "x_mid", where, A["attn"], P["wproj"], P["bproj"], A["x_in"], A["x_mid"], inter, B, f.get(0))
     check_ln_fwd(worst, "xn2", where, A["x_mid"], P["ln2_g"], P["ln2_b"], A["xn2"], A["mean2"], A["rstd2"], B)
@@ -369,7 +413,7 @@ def check_lnbwd_fused(worst, key, where, a, wt, x, mean, rstd, g, res, dx, part,
     return r
 
 
-def check_block_bwd(worst, where, P, A, G, B):
+def check_block_bwd(worst, where, P, A, G, B, logit=False):
     """Backward stages 1 - 6a of one block on the fused forms (one-launch backward / per-operation fused path): G holds dy, du,
     dx_mid, dattn (None: its scratch was reused), dqkv, dx and part2 / part1 ([B, 2, E], None: not checked here).
     The dropout backward (vit.hip block_bwd with d) adds dy_m and dxmid_m: the GEMM operands of du and dattn; the two residuals
@@ -393,10 +437,10 @@ def check_block_bwd(worst, where, P, A, G, B):
         ref = d64(G["dattn"])
     else:       # the scratch has been reused by an earlier block: d(qkv) from the fp64 d(attention output), its GEMM bound propagated
         delta = gemm_bound(ref, mag, e, dt)
-    r = attn_bwd(d64(A["qkv"]), d64(A["attn"]), ref, d64(A["lse"]).reshape(B, inner // 64, NTOK), B, 1.0 / math.sqrt(e), delta)
+    r = attn_bwd(d64(A["qkv"]), d64(A["attn"]), ref, d64(A["lse"]).reshape(B, inner // 64, NTOK), B, 1.0 / math.sqrt(e), delta, logit)
     del ref, mag, delta
     for i, nm in enumerate(("dq", "dk", "dv")):
-        extra = tiny(dt) * r["under"][nm] + (r[nm][2] if r[nm][2] is not None else 0.0)
+        extra = tiny(dt) * r["under"][nm] + (r[nm][2] if r[nm][2] is not None else 0.0) + (r["logit"][nm] if logit else 0.0)
         _chk(worst, nm, G["dqkv"][:, i * inner:(i + 1) * inner], r[nm][0], r[nm][1], ATTN_C[nm] * u_p(dt), where, extra=extra,
              B=B, tile=(NTOK, 64))
     del r

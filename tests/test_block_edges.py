@@ -15,6 +15,9 @@ Measured on one MI355X (worst |err| / bound over all cases, one-launch | per-ope
     dv 0.35 | 0.29   dx 0.53 | 0.50   dxn - | 0.50   part2, part1 0.25   dln 0.17 | 0.07   dW 0.015 | 0.003   db 0.013 | 0.004
     pe_dw 0.03   pe_db 0.01                              (dxn exists on the generic paths only; the fused forms keep it in LDS)
 The 31 tests take 62 s there ("Encoder blocks, element-wise", says which cases cost it and why they stay).
+Two later cases run block_ref.make_params(offset=+-1) -- every logit and lse at +-148 scaled units -- with the same stage checks plus
+block_ref.logit_err: the one-launch forward + backward at B = 2 and the per-operation path at B = 42 (0.09 s and 0.20 s; attention
+output 0.34, lse 0.05, dq 0.27, dk 0.22, dv 0.27 of their bounds; DESIGN.md, "Value regimes").
 """
 import ctypes as C
 
@@ -58,10 +61,10 @@ def gelu_table():
 class Case:
     """Parameters, chain images and inputs of one (B, depth) on the device; everything the kernels write is guarded."""
 
-    def __init__(self, B, depth, seed=1, images=True, dt=BF16, e=E, heads=HEADS):
+    def __init__(self, B, depth, seed=1, images=True, dt=BF16, e=E, heads=HEADS, offset=None):
         self.B, self.depth, self.M, self.dt, self.e, self.inner, self.heads = B, depth, B * NTOK, dt, e, heads * 64, heads
         wk = ("wqkv", "wproj", "w1", "w2")
-        self.P = [{k: v.to(DEV).to(dt if k in wk else F32) for k, v in p.items()} for p in R.make_params(depth, seed, e, heads)]
+        self.P = [{k: v.to(DEV).to(dt if k in wk else F32) for k, v in p.items()} for p in R.make_params(depth, seed, e, heads, offset)]
         self.x0 = nan_padded(R.make_x0(B, seed, e).to(DEV).to(dt), extra_rows=8)
         self.dy = nan_padded(R.make_dy(B, seed, e).to(DEV).to(dt), extra_rows=8)
         self.cfg = L.VitCfg(L.dt_of(dt), B, NTOK, e, heads, R.EPS, 1.0 / e ** 0.5)
@@ -288,6 +291,24 @@ def test_chain_forward_backward_and_weight_gradients(option, b, depth):
     finish(where, ("chain-fwd", "chain-bwd", "chain-dw"), soft)
 
 
+def test_chain_forward_backward_with_a_logit_offset():
+    """B = 2, depth 1 with make_params(offset=+1): q[:, 0] = 32 and k[:, 0] = 64 in every head, so every logit and lse of the
+    one-launch forward carries +148 scaled units (exp of it overflows fp32 without the max subtraction) and the backward rebuilds P
+    from an lse of that size.  The stage checks of the case above plus block_ref.logit_err."""
+    B = 2
+    c = Case(B, 1, offset=1)
+    where = f"chain B={B} depth=1 offset=+1"
+    wf, wb = collecting("chain-fwd", "chain-bwd")
+    acts = c.run_fwd()
+    info = R.check_block_fwd(wf, f"{where} block 0", c.P[0], c.act_tensors(acts, 0), B, logit=True)
+    soft = [] if info["lse_absmin"] >= 70 and info["onehot_rows"] >= c.M // 10 else [
+        f"{where}: min |lse| {info['lse_absmin']:.4g}, one-hot rows {info['onehot_rows']}"]
+    del info
+    bw, dattn = c.run_bwd(acts)
+    R.check_block_bwd(wb, f"{where} block 0", c.P[0], c.act_tensors(acts, 0), c.bwd_tensors(bw, dattn, 0), B, logit=True)
+    finish(where, ("chain-fwd", "chain-bwd"), soft)
+
+
 def test_chain_backward_twice_gives_the_same_bits():
     c = Case(cu_count() + 1, 2)
     acts = c.run_fwd()
@@ -304,7 +325,7 @@ def table_kernel(names):
     return any("mlp_fwd_kernel" in n and ("<true>" in n or "<(bool)1>" in n) for n in names)
 
 
-def per_operation(c, where, fused, tn_kernels=None):
+def per_operation(c, where, fused, tn_kernels=None, logit=False):
     """rgbnm_vit_block_fwd_chain (block 0 with a next block, block 1 without -- its LN1 comes out of block 0's fc2 epilogue when
     rgbnm_vit_ln_chain says so) and rgbnm_vit_block_bwd over the two blocks of Case c; every stage of both from what the run
     stored, residual epilogues with the `inter` term of the per-operation kernels.  fused: the E = 192 row-panel kernels with
@@ -341,7 +362,9 @@ def per_operation(c, where, fused, tn_kernels=None):
     for i in range(2):
         for k, g in acts[i].items():
             g.check(f"{where} block {i} {k}")
-        info = R.check_block_fwd(wf, f"{where} block {i}", c.P[i], c.act_tensors(acts, i), B, inter=True)
+        info = R.check_block_fwd(wf, f"{where} block {i}", c.P[i], c.act_tensors(acts, i), B, inter=True, logit=logit)
+        if logit and info["lse_absmin"] < 70:
+            soft.append(f"{where} block {i}: min |lse| {info['lse_absmin']:.4g}, no logit offset")
         lo, mid, hi = table_regimes(info["pre"])
         if not (lo >= 4 * c.M and hi >= 4 * c.M and mid > info["pre"].numel() // 2):
             soft.append(f"{where} block {i}: table regimes {(lo, mid, hi)}")
@@ -377,7 +400,7 @@ def per_operation(c, where, fused, tn_kernels=None):
             g.check(f"{w} {k}")
         A = c.act_tensors(acts, i)
         G = dict(dy=dy, du=sc["du"].t, dx_mid=sc["dx_mid"].t, dattn=sc["dattn"].t, dqkv=sc["dqkv"].t, dx=sc["dx"].t)
-        r2, r1 = R.check_block_bwd(wb, w, c.P[i], A, G, B)
+        r2, r1 = R.check_block_bwd(wb, w, c.P[i], A, G, B, logit=logit)
         Wg = {k: g.t for k, g in grads.items()}
         R.check_block_dw(wd, w, A, G, Wg, B)
         R.check_dln_total(wd, w, r2, r1, Wg, B)
@@ -396,6 +419,12 @@ def test_per_operation_blocks_at_their_launchers_edges(option, B, dmast):
         option("mlp_dmast", dmast)
     per_operation(Case(B, 2, images=False), f"per-operation B={B}" + ("" if dmast is None else f" mlp_dmast={dmast}"),
                   B * NTOK >= 8192)
+
+
+def test_per_operation_blocks_with_a_logit_offset(option):
+    """The fused per-operation path at its first eligible batch (B = 42, bf16) with make_params(offset=-1): every logit carries -148
+    scaled units, where exp of the unshifted logit is zero in fp32; attention v2 forward and backward inside the block."""
+    per_operation(Case(42, 2, images=False, offset=-1), "per-operation B=42 offset=-1", True, logit=True)
 
 
 GENERIC_OFF = ("nt_small", "nt_kpipe", "nt_wres", "nt_staged", "ln_fuse", "tn_pipe", "tn_group", "tn_direct", "tn_wide", "attn_v2",

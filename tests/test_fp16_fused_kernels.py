@@ -105,7 +105,7 @@ def is_table(n):
     return "mlp_fwd_kernel" in n and ("mlp_fwd_kernel<true" in n or "<(bool)1" in n or "mlp_fwd_kernelILb1" in n)
 
 
-def per_block(c, where, fused, attn2=None):
+def per_block(c, where, fused, attn2=None, logit=False):
     """tests/test_block_edges.py per_operation for an fp16 Case.  fused True: the E = 192 fused kernels are expected in their fp16
     instantiations; False: none of them may run (LayerNorm-chained epilogues, fused MLP); None: E = 384, only attention is asked.
     attn2: True / False / None -- attention v2 in its fp16 instantiation is expected / forbidden / not asked."""
@@ -155,7 +155,9 @@ def per_block(c, where, fused, attn2=None):
     for i in range(2):
         for k, g in acts[i].items():
             g.check(f"{where} block {i} {k}")
-        info = R.check_block_fwd(wf, f"{where} block {i}", c.P[i], c.act_tensors(acts, i), B, inter=True)
+        info = R.check_block_fwd(wf, f"{where} block {i}", c.P[i], c.act_tensors(acts, i), B, inter=True, logit=logit)
+        if logit and info["lse_absmin"] < 70:
+            soft.append(f"{where} block {i}: min |lse| {info['lse_absmin']:.4g}, no logit offset")
         if info["onehot_rows"] < c.M // 10 or (i == 0 and info["rstd1_max"] <= 0.8 * R.EPS ** -0.5):
             soft.append(f"{where} block {i}: one-hot rows {info['onehot_rows']}, max rstd1 {info['rstd1_max']:.4g}")
         del info
@@ -188,7 +190,7 @@ def per_block(c, where, fused, attn2=None):
             g.check(f"{w} {k}")
         A = c.act_tensors(acts, i)
         G = dict(dy=dy, du=sc["du"].t, dx_mid=sc["dx_mid"].t, dattn=sc["dattn"].t, dqkv=sc["dqkv"].t, dx=sc["dx"].t)
-        r2, r1 = R.check_block_bwd(wb, w, c.P[i], A, G, B)
+        r2, r1 = R.check_block_bwd(wb, w, c.P[i], A, G, B, logit=logit)
         Wg = {k: g.t for k, g in grads.items()}
         R.check_block_dw(wd, w, A, G, Wg, B)
         R.check_dln_total(wd, w, r2, r1, Wg, B)
@@ -207,6 +209,14 @@ def test_per_block_fused_path_fp16(option, B, dmast):
         option("mlp_dmast", dmast)
     per_block(Case(B, 2, images=False, dt=F16), f"fp16 per-block B={B}" + ("" if dmast is None else f" mlp_dmast={dmast}"),
               B * NTOK >= 8192, attn2=True)
+
+
+def test_per_block_fused_path_fp16_with_a_logit_offset(option):
+    """B = 42 at level 2 with block_ref.make_params(offset=+1): q[:, 0] = 32 and k[:, 0] = 64 in every head (exact in fp16), every
+    logit and lse at +148 scaled units, through the fp16 attn2 forward (the 2^14 shift) and backward inside the block; the stage
+    checks of the case above plus block_ref.logit_err."""
+    option("f16_tuned", 2)
+    per_block(Case(42, 2, images=False, dt=F16, offset=1), "fp16 per-block B=42 offset=+1", True, attn2=True, logit=True)
 
 
 def test_per_block_level_1_runs_none_of_the_fused_kernels(option):

@@ -426,11 +426,14 @@ ATTN_C = {"out": 2.5,    # [1.22]
           "dv": 4.6}     # [2.27]
 
 
-def attn_case(dt, B, N, H, seed, want_f, want_b, worst, key):
+def attn_case(dt, B, N, H, seed, want_f, want_b, worst, key, *, qkv=None, dout=None, scale=None, check=None):
+    """qkv, dout, scale: the caller's inputs in place of the unit-scale draws.  check(where, qkv, dout, out, lse, dqkv, scale): the
+    caller's bounds (its added terms included) in place of the ones below (tests/test_value_regimes.py); the launches, the guards
+    and the asserted kernels are the same.  The defaults give the tensors and bounds this case always had."""
     I = H * 64
-    scale = 1.0 / math.sqrt(I)
-    qkv = rnd((B * N, 3 * I), seed, 1.5, dt)
-    dout = rnd((B * N, I), seed + 1, 1.0, dt)
+    scale = 1.0 / math.sqrt(I) if scale is None else scale
+    qkv = rnd((B * N, 3 * I), seed, 1.5, dt) if qkv is None else qkv
+    dout = rnd((B * N, I), seed + 1, 1.0, dt) if dout is None else dout
     out = guarded(B * N, I, dt)
     lse = guarded(B * H * N, None, F32)
     dqkv = guarded(B * N, 3 * I, dt)
@@ -450,6 +453,8 @@ def attn_case(dt, B, N, H, seed, want_f, want_b, worst, key):
     out.check(where + " out")
     lse.check(where + " lse")
     dqkv.check(where + " dqkv")
+    if check is not None:
+        return check(where, qkv, dout, out.t, lse.t, dqkv.t, scale)
     uP = KC.U_OF[dt] if dt != F32 else N * U
 
     def heads(t):                                    # [B*N, 3I] -> three [B, H, N, 64]
@@ -534,9 +539,13 @@ def ln_ref_fwd(x64, g64, b64, eps):
     return mu, rs, xh
 
 
-def ln_case(dt, M, E, dres_on, acc, seed, worst, key, generic=False, res_on=False, ss_on=False, rps=7, want=None):
+def ln_case(dt, M, E, dres_on, acc, seed, worst, key, generic=False, res_on=False, ss_on=False, rps=7, want=None, *, x=None,
+            dy=None, check=None):
+    """x, dy: the caller's rows in place of the unit-scale draws.  check: an object whose fwd(...) and bwd(...) take the place of the
+    bounds below, which are the same forms stated per row regime (tests/regime_ref.py ln_check_fwd / ln_check_bwd); the launches, the
+    guards and the asserted kernels are the same.  The defaults give the tensors and bounds this case always had."""
     eps = 1e-5
-    x = (rnd((M, E), seed, 2.0) + 0.5).to(dt)
+    x = (rnd((M, E), seed, 2.0) + 0.5).to(dt) if x is None else x
     gamma = 1 + rnd((E,), seed + 1, 0.2)
     beta = rnd((E,), seed + 2, 0.2)
     res = rnd((M, E), seed + 3, 1.0, dt) if res_on else None
@@ -558,20 +567,23 @@ def ln_case(dt, M, E, dres_on, acc, seed, worst, key, generic=False, res_on=Fals
     for t, nm in ((y, "y"), (mean, "mean"), (rstd, "rstd")):
         t.check(where + " " + nm)
     x64, g64, b64 = x.double(), gamma.double(), beta.double()
-    mu, rs, xh = ln_ref_fwd(x64, g64, b64, eps)
     sc = ss.double()[torch.arange(M, device=DEV) // rps][:, None] if ss_on else 1.0
+    if check is not None:
+        check.fwd(where, x, gamma, beta, y.t, mean.t, rstd.t, eps, res, sc)
+    mu, rs, xh = ln_ref_fwd(x64, g64, b64, eps)
     yref = (xh * g64 + b64) * sc
     ymag = (g64.abs() * (xh.abs() + rs * x64.abs().mean(1, keepdim=True)) + b64.abs()) * sc
     if res_on:
         yref = yref + res.double()
         ymag = ymag + res.double().abs()
     cE = LN_C["y"] * E * U
-    worst(key + "-y", check_bound(y.t, yref, ymag, dt, 1, cE, where + " y", tile=(16, E)))
-    worst(key + "-stat", check_bound(mean.t, mu[:, 0], x64.abs().mean(1), F32, 1, LN_C["stat"] * E * U, where + " mean"))
-    worst(key + "-stat", check_bound(rstd.t, rs[:, 0], rs[:, 0], F32, 1, LN_C["stat"] * E * U, where + " rstd"))
+    if check is None:
+        worst(key + "-y", check_bound(y.t, yref, ymag, dt, 1, cE, where + " y", tile=(16, E)))
+        worst(key + "-stat", check_bound(mean.t, mu[:, 0], x64.abs().mean(1), F32, 1, LN_C["stat"] * E * U, where + " mean"))
+        worst(key + "-stat", check_bound(rstd.t, rs[:, 0], rs[:, 0], F32, 1, LN_C["stat"] * E * U, where + " rstd"))
     del yref, ymag
     # backward on the kernel's own statistics (inputs of the operation: exact in the reference)
-    dy = rnd((M, E), seed + 4, 1.0, dt)
+    dy = rnd((M, E), seed + 4, 1.0, dt) if dy is None else dy
     dres = rnd((M, E), seed + 5, 1.0, dt) if dres_on else None
     dx = guarded(M, E, dt)
     dg, dbt = guarded(E, None, F32), guarded(E, None, F32)
@@ -595,6 +607,8 @@ def ln_case(dt, M, E, dres_on, acc, seed, worst, key, generic=False, res_on=Fals
     expect(nb, (want[1],), where + " bwd")
     for t, nm in ((dx, "dx"), (dg, "dgamma"), (dbt, "dbeta"), (ws, "workspace")):
         t.check(where + " " + nm, written=(nm != "workspace"))
+    if check is not None:
+        return check.bwd(where, x, gamma, dy, mean.t, rstd.t, dx.t, dg.t, dbt.t, dres, init if acc else None, sc)
     kmu, krs = mean.t.double()[:, None], rstd.t.double()[:, None]
     xh = (x64 - kmu) * krs
     d = dy.double() * sc
