@@ -97,6 +97,8 @@ int rgbnm_abi_version(void);
  *   "fwd_chain"    1  rgbnm_vit_chain_fwd eligible        "bwd_chain"  1  rgbnm_vit_chain_bwd eligible (0: the per-operation kernels)
  *   SwinV2
  *   "ln_rows"      1  lanes-per-row LayerNorm kernels for the four stage widths            "win_xcd"  1  XCD-aware window walk
+ *   JPEG entropy decode
+ *   "jpeg_lanes"   0  runs per wave of rgbnm_jpeg_decode_batch, 1..64 (0: chosen per launch so that about 2048 waves share the runs)
  *   measurement
  *   "trace"        0  bit mask of kernel classes to bracket with HIP events, see rgbnm_trace_collect */
 int rgbnm_set_option(const char* name, int value);
@@ -411,6 +413,87 @@ int rgbnm_pixels_to_dct(const uint8_t* pixels, int B, int C, int H, int W, const
                         void* stream);
 int rgbnm_dct_to_pixels(const int16_t* Y, const int16_t* CbCr, int B, int H, int W, const int16_t* quant_host, uint8_t* pixels,
                         void* stream);
+
+/* Entropy decoding of baseline JPEG files on the device (csrc/jpeg_scan.h, jpeg_walk.h, jpeg_decode.hip): from file bytes to the
+ * int16 coefficient tensors of rgbnm_read_coefficients_batch (include/rgbnm_reader.h), bit for bit.  A baseline scan is a set of
+ * independent bit streams -- the whole scan, or one per restart interval -- so the host only FINDS them (rgbnm_jpeg_prepare: marker
+ * parse, removal of the stuffed FF 00, split at RSTn; a byte scan, no Huffman decode, callable without a GPU) and the device walks
+ * them, one lane per run (rgbnm_jpeg_decode_batch).
+ * Accepted: SOF0 / SOF1, 8 bit, Huffman, ONE scan holding all components; one component, or three whose block grids are Hb x Wb,
+ * Hbc x Wbc, Hbc x Wbc with at most 10 blocks per MCU and sampling factors <= 4 (4:2:0 gives 2x2, 1x1, 1x1).  Anything else gets a
+ * negative per-file status and leaves the other files of the batch untouched.
+ *
+ * Per-file status (rgbnm_jpeg_image.status, and the device status array, which starts as a copy of it): */
+#define RGBNM_JPEG_ETRUNCATED (-10)    /* a marker segment or the scan runs past the end of the file (no EOI) */
+#define RGBNM_JPEG_EMARKER (-11)       /* inconsistent marker segment: no SOI / SOF / table, bad length, bad table, bad scan header */
+#define RGBNM_JPEG_EUNSUPPORTED (-12)  /* progressive, arithmetic, lossless, 12 bit, several scans, DNL, 2 or 4 components, sampling */
+#define RGBNM_JPEG_EGRID (-13)         /* the file's block grids are not the requested ones */
+#define RGBNM_JPEG_ERESTART (-14)      /* RSTn out of sequence (D0..D7 cyclic), or the run count is not ceil(MCUs / interval) */
+#define RGBNM_JPEG_ECAPACITY (-15)     /* the plan's stream / runs / tables buffer is too small for this file */
+#define RGBNM_JPEG_ECODE (-20)         /* device: a bit pattern that no Huffman code of the table matches, or a DC category > 15 */
+#define RGBNM_JPEG_EINDEX (-21)        /* device: a coefficient index past 63 */
+#define RGBNM_JPEG_EOVERRUN (-22)      /* device: more bits consumed than the run holds */
+#define RGBNM_JPEG_ETRAILING (-23)     /* device: more than a byte of bits left over after the run's last MCU */
+#define RGBNM_JPEG_ERECORD (-24)       /* device: a run / image record that does not fit the buffers it points into */
+
+/* One run: the entropy-coded bytes between two markers, un-stuffed.  offset is a multiple of 4; behind the nbytes bytes the stream
+ * holds zeros up to the next multiple of 4 and 4 more, so that 32-bit reads of a run never leave the buffer.  nmcu == 0: a record of
+ * a file that was refused after its records had been laid out; the device skips it. */
+typedef struct rgbnm_jpeg_run { uint32_t offset, nbytes; int32_t image, mcu0, nmcu, _pad[3]; } rgbnm_jpeg_run;            /* 32 bytes */
+/* One image.  An MCU is nblk blocks; block j of it belongs to component blk_comp[j] and sits at (blk_dy[j], blk_dx[j]) inside the
+ * MCU's vs[c] x hs[c] patch of that component.  dc_tab / ac_tab: index of each component's table in the batch's table array.
+ * The kept grids are the call's Hb x Wb (component 0) and Hbc x Wbc (components 1, 2): blocks of the MCU padding beyond them are
+ * decoded and dropped. */
+typedef struct rgbnm_jpeg_image {
+  int32_t ncomp, mcus_x, mcus_y, nblk, status;
+  int32_t dc_tab[3], ac_tab[3], hs[3], vs[3];
+  int32_t blk_comp[10], blk_dx[10], blk_dy[10];
+  int32_t nruns;                        /* runs of this image (consecutive records) */
+} rgbnm_jpeg_image;                                                                                                       /* 192 bytes */
+/* One Huffman table in the form the walk looks up: look[next 9 bits] = (code length << 8) | symbol, 0 for codes longer than 9 bits;
+ * for those, libjpeg's canonical search: the first l in 10..16 with (next l bits) <= maxcode[l] (-1: no code of that length) gives
+ * symbol vals[(next l bits) + valoff[l]].  bits / vals are the DHT segment's (the key tables are de-duplicated by). */
+typedef struct rgbnm_jpeg_hufftab {
+  uint16_t look[512];
+  int32_t maxcode[18], valoff[18];
+  uint8_t vals[256], bits[16];
+} rgbnm_jpeg_hufftab;                                                                                                     /* 1440 bytes */
+/* What rgbnm_jpeg_prepare fills.  The caller owns every buffer (pinned, when the plan is to be copied to the device) and sets the
+ * pointers, the capacities and `threads`; the call sets the counts.  stream_cap of sum(lens) + 8 * runs_cap always suffices;
+ * an image has at most min(MCUs, len / 2 + 1) runs; a batch has at most 65535 distinct tables.
+ *   stream   the runs' bytes (FF 00 -> FF, fill FFs and markers dropped), each run aligned and padded as above; a file's runs
+ *            lie in the file's own region (laid out from its header before the scan is read), so the regions have small gaps
+ *   runs     [nruns] in file order, a file's runs in scan order          images  [n]
+ *   tables   [ntables]: every distinct table of the batch once           quant   int16 [n][3][64], natural order, unit tables
+ *   messages [n][message_len] (may be NULL): why a file was refused              for the chroma slots of a one-component file
+ *   threads  files are un-stuffed by up to this many threads (1..16; the header pass is serial) */
+typedef struct rgbnm_jpeg_plan {
+  uint8_t* stream; size_t stream_cap;
+  rgbnm_jpeg_run* runs; rgbnm_jpeg_image* images; rgbnm_jpeg_hufftab* tables;
+  int16_t* quant; char* messages;
+  int32_t runs_cap, tables_cap, message_len, threads;
+  size_t stream_bytes;                  /* out: used prefix of stream */
+  int32_t nruns, ntables, nbad, _pad;   /* out: records used, tables used, files with a negative status */
+} rgbnm_jpeg_plan;
+/* bufs[i] / lens[i]: file i in host memory.  Returns the number of refused files (>= 0), or RGBNM_EINVAL (NULL pointer, n <= 0, a
+ * grid outside 1..4096, capacities <= 0) with nothing written.  Host only: no HIP call. */
+int rgbnm_jpeg_prepare(const uint8_t* const* bufs, const size_t* lens, int n, int Hb, int Wb, int Hbc, int Wbc, rgbnm_jpeg_plan* plan);
+/* The plan's buffers on the device (copies of the used prefixes) and its counts. */
+typedef struct rgbnm_jpeg_device_plan {
+  const uint8_t* stream; size_t stream_bytes;
+  const rgbnm_jpeg_run* runs; const rgbnm_jpeg_image* images; const rgbnm_jpeg_hufftab* tables;
+  int32_t nruns, ntables;
+} rgbnm_jpeg_device_plan;
+/* One launch, one lane per run: Y int16 [n][Hb][Wb][64], CbCr int16 [n][2][Hbc][Wbc][64] (16-byte aligned).  Every element of an
+ * accepted image is written, zeros included (the chroma of a one-component file too); images with a negative host status are not
+ * touched.  status: int32 [n] on the device, holding the host statuses on entry (copy rgbnm_jpeg_image.status there, or zeros); a run
+ * that ends in an error lowers its image's entry to the RGBNM_JPEG_E* code (atomicMin) and zero-fills the blocks it has not written.
+ * The kernel checks every record against the buffer sizes given here, bounds every loop by counts known at entry, waits for no other
+ * lane, and cannot write outside Y / CbCr / status whatever the stream holds.  No allocation, no copy, no synchronisation: capturable.
+ * RGBNM_EINVAL with nothing launched: NULL pointers, n <= 0, a grid outside 1..4096, nruns < 0, misaligned outputs.  nruns == 0
+ * returns 0 without a launch. */
+int rgbnm_jpeg_decode_batch(const rgbnm_jpeg_device_plan* plan, int n, int Hb, int Wb, int Hbc, int Wbc, int16_t* Y, int16_t* CbCr,
+                            int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Train-step tail

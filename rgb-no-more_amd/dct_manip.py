@@ -213,6 +213,163 @@ def read_coefficients_batch_crop(paths, boxes, threads=8, grid=(64, 64), pin_mem
     return Yp[:ny], Cp[:ncc], quant[:n], y_off, c_off
 
 
+# ---- entropy decode on the device (csrc/jpeg_scan.h, jpeg_walk.h, jpeg_decode.hip; include/rgbnm.h) -------------------------------
+_MSGLEN = 128
+
+
+class JpegBatchPlan:
+    """The buffers rgbnm_jpeg_prepare fills (include/rgbnm.h, rgbnm_jpeg_plan) as CPU tensors -- pinned when asked, so that each is
+    one asynchronous H2D copy -- and, after prepare_jpeg_batch, the counts, the per-file status (0, or a negative RGBNM_JPEG_E* code)
+    and message.  Sized once for batches of up to n files and re-used (a ring of them in the loader):
+        stream uint8 [stream_cap] | runs int32 [runs_cap, 8] | images int32 [n, 48] | tables uint8 [tables_cap, 1440]
+        quant int16 [n, 3, 8, 8] | status int32 [n]"""
+
+    def __init__(self, n, grid=(64, 64), stream_cap=None, runs_cap=None, tables_cap=None, pin_memory=False):
+        hb, wb = grid
+        hbc, wbc = (hb + 1) // 2, (wb + 1) // 2
+        if stream_cap is None:                       # 192 KB per 512 x 512 file (quality 90 on a noisy image: 98 KB), one run per MCU row ...
+            stream_cap = n * max(4096, 48 * hb * wb)
+        if runs_cap is None:                         # ... up to one run per 4:2:0 MCU
+            runs_cap = n * max(64, hbc * wbc)
+        if tables_cap is None:
+            tables_cap = min(65535, 4 + 6 * n)
+        kw = dict(pin_memory=pin_memory)
+        self.capacity, self.grid = int(n), (hb, wb)
+        self.stream = torch.empty(int(stream_cap) + 8 * int(runs_cap), dtype=torch.uint8, **kw)
+        self.runs = torch.empty((int(runs_cap), 8), dtype=torch.int32, **kw)
+        self.images = torch.empty((n, 48), dtype=torch.int32, **kw)
+        self.tables = torch.empty((int(tables_cap), 1440), dtype=torch.uint8, **kw)
+        self.quant = torch.empty((n, 3, 8, 8), dtype=torch.int16, **kw)
+        self.status = torch.zeros(n, dtype=torch.int32, **kw)
+        self._msg = C.create_string_buffer(n * _MSGLEN)
+        self.n = self.nruns = self.ntables = self.stream_bytes = self.nbad = 0
+        self.names, self.messages = [], []
+
+    def buffers(self):
+        """The used prefixes: what crosses PCIe."""
+        return (self.stream[:self.stream_bytes], self.runs[:self.nruns], self.images[:self.n], self.tables[:self.ntables],
+                self.quant[:self.n], self.status[:self.n])
+
+    def h2d_bytes(self):
+        return sum(t.numel() * t.element_size() for t in self.buffers())
+
+
+def _read_file(d):
+    try:
+        with open(d, "rb") as fh:
+            return fh.read()
+    except OSError:
+        raise RuntimeError(f"Unable to open file for reading: {d}") from None
+
+
+def _jpeg_bytes(datas):
+    """(file contents, names) of a list of bytes or paths."""
+    isb = [isinstance(d, (bytes, bytearray, memoryview)) for d in datas]
+    names = [f"<bytes #{k}>" if b else os.fspath(d) for k, (d, b) in enumerate(zip(datas, isb))]
+    return [bytes(d) if b else _read_file(d) for d, b in zip(datas, isb)], names
+
+
+def prepare_jpeg_batch(datas, grid=(64, 64), out=None, threads=1, pin_memory=False):
+    """Host half of the device decode; needs no GPU.  datas: JPEG files as bytes or paths.  Finds the independent bit streams of
+    every file -- marker parse, un-stuffing, split at the restart markers; no Huffman decode -- and returns a JpegBatchPlan (out:
+    one to fill again) whose buffers decode_jpeg_batch ships and walks.  A file the device cannot decode (progressive, another
+    grid, damaged, ...) gets a negative plan.status[i] and plan.messages[i]; the other files are not affected."""
+    from . import lib as L
+    datas, names = _jpeg_bytes(datas)
+    n = len(datas)
+    if n == 0:
+        raise ValueError("no files")
+    hb, wb = grid
+    hbc, wbc = (hb + 1) // 2, (wb + 1) // 2
+    if out is None:
+        total = sum(len(d) for d in datas)
+        out = JpegBatchPlan(n, grid, stream_cap=total + 4 * n, runs_cap=sum(min(hb * wb, len(d) // 2 + 1) for d in datas),
+                            pin_memory=pin_memory)
+    if n > out.capacity or tuple(out.grid) != (hb, wb):
+        raise ValueError("plan buffers do not match the batch (JpegBatchPlan(n, grid))")
+    p = L.JpegPlan(stream=out.stream.data_ptr(), stream_cap=out.stream.numel(), runs=out.runs.data_ptr(), images=out.images.data_ptr(),
+                   tables=out.tables.data_ptr(), quant=out.quant.data_ptr(), messages=C.addressof(out._msg),
+                   runs_cap=out.runs.shape[0], tables_cap=out.tables.shape[0], message_len=_MSGLEN, threads=int(threads))
+    bufs = (C.c_char_p * n)(*datas)
+    lens = (C.c_size_t * n)(*[len(d) for d in datas])
+    rc = L.lib().rgbnm_jpeg_prepare(bufs, lens, n, hb, wb, hbc, wbc, C.byref(p))
+    if rc < 0:
+        L.check(rc, "jpeg_prepare")
+    out.n, out.nruns, out.ntables, out.stream_bytes, out.nbad = n, p.nruns, p.ntables, p.stream_bytes, p.nbad
+    out.status[:n] = out.images[:n, 4]
+    out.names = names
+    out.messages = [out._msg.raw[i * _MSGLEN:(i + 1) * _MSGLEN].split(b"\0", 1)[0].decode(errors="replace") for i in range(n)]
+    return out
+
+
+def alloc_jpeg_out(n, grid=(64, 64), device="cuda"):
+    """Device tensors for decode_jpeg_batch(out=...): (Y, CbCr, quant, status)."""
+    hb, wb = grid
+    hbc, wbc = (hb + 1) // 2, (wb + 1) // 2
+    kw = dict(dtype=torch.int16, device=device)
+    return (torch.empty((n, 1, hb, wb, 8, 8), **kw), torch.empty((n, 2, hbc, wbc, 8, 8), **kw), torch.empty((n, 3, 8, 8), **kw),
+            torch.empty(n, dtype=torch.int32, device=device))
+
+
+def upload_jpeg_plan(plan, device):
+    """One asynchronous H2D copy per plan buffer on the current stream: (stream, runs, images, tables, quant, status) on the device."""
+    return tuple(t.to(device, non_blocking=True) for t in plan.buffers())
+
+
+def launch_jpeg_decode(plan, dev, out):
+    """The decode launch alone (no copy, no allocation, no sync: capturable).  dev: upload_jpeg_plan's tensors; out: (Y, CbCr, quant,
+    status) device tensors (alloc_jpeg_out); quant and status must already hold the plan's (decode_jpeg_batch copies them)."""
+    from . import lib as L
+    Y, CbCr, _, status = out
+    hb, wb = plan.grid
+    n = plan.n
+    L.require_cuda(Y, CbCr, status, *dev[:4])
+    if tuple(Y.shape) != (n, 1, hb, wb, 8, 8) or tuple(CbCr.shape) != (n, 2, (hb + 1) // 2, (wb + 1) // 2, 8, 8) or status.numel() != n \
+            or Y.dtype != torch.int16 or CbCr.dtype != torch.int16 or status.dtype != torch.int32:
+        raise L.RgbnmError("out tensors do not match the plan (alloc_jpeg_out)")
+    dp = L.JpegDevicePlan(stream=dev[0].data_ptr(), stream_bytes=plan.stream_bytes, runs=dev[1].data_ptr(), images=dev[2].data_ptr(),
+                          tables=dev[3].data_ptr(), nruns=plan.nruns, ntables=plan.ntables)
+    with torch.cuda.device(Y.device):
+        L.check(L.lib().rgbnm_jpeg_decode_batch(C.byref(dp), n, hb, wb, (hb + 1) // 2, (wb + 1) // 2, Y.data_ptr(), CbCr.data_ptr(),
+                                                status.data_ptr(), L.stream()), "jpeg_decode_batch")
+
+
+def decode_jpeg_batch(plan, device="cuda", out=None):
+    """Device half: one H2D copy per plan buffer on the current stream, then ONE launch that walks every run with one lane (there is
+    no CPU fallback).  Returns (Y, CbCr, quant, status) on the device: the int16 tensors of read_coefficients_batch, bit for bit, and
+    int32 status per file -- the plan's host status, lowered to a negative code where the walk met an error in the stream (the file's
+    blocks not yet written are then zeros).  Files with a negative HOST status are not written at all.  No host sync."""
+    n = plan.n
+    if out is None:
+        out = alloc_jpeg_out(n, plan.grid, device)
+    out = tuple(t[:n] for t in out)
+    dev = upload_jpeg_plan(plan, out[0].device)
+    out[2].copy_(dev[4], non_blocking=True)
+    out[3].copy_(dev[5], non_blocking=True)
+    launch_jpeg_decode(plan, dev, out)
+    for t in dev[:4]:                        # the launch reads them on this stream: keep the allocator from handing them out early
+        t.record_stream(torch.cuda.current_stream(out[0].device))
+    return out
+
+
+def jpeg_status_text(code):
+    from . import lib as L
+    return L.JPEG_STATUS.get(int(code), f"status {int(code)}")
+
+
+def read_coefficients_batch_device(paths_or_bytes, grid=(64, 64), device="cuda"):
+    """read_coefficients_batch with the entropy decode on the device: (Y, CbCr, quant) int16 DEVICE tensors.  Raises, naming the file,
+    when one cannot be decoded there (synchronises to read the device status)."""
+    plan = prepare_jpeg_batch(paths_or_bytes, grid)
+    Y, CbCr, quant, status = decode_jpeg_batch(plan, device)
+    st = status.cpu()
+    if int((st != 0).sum()):
+        i = int((st != 0).nonzero()[0])
+        raise libjpeg_exception(f"{plan.names[i]}: device decode refused the file: {jpeg_status_text(st[i])}"
+                                f"{' (' + plan.messages[i] + ')' if plan.messages[i] else ''} ({int((st != 0).sum())} of {plan.n} files failed)")
+    return Y, CbCr, quant
+
+
 # ---- pixels <-> coefficients on the device (csrc/pixel_dct.hip) --------------------------------------------------------------
 # ITU-T T.81 Annex K, natural order
 _LUMA_TABLE = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,

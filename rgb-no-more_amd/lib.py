@@ -89,6 +89,44 @@ class DftJob(C.Structure):
     _fields_ = [("sample", _i), ("rot90s", _i), ("map_y", _i), ("map_c", _i)]
 
 
+class JpegRun(C.Structure):
+    """rgbnm_jpeg_run (32 bytes)."""
+    _fields_ = [("offset", C.c_uint32), ("nbytes", C.c_uint32), ("image", C.c_int32), ("mcu0", C.c_int32), ("nmcu", C.c_int32),
+                ("_pad", C.c_int32 * 3)]
+
+
+class JpegImage(C.Structure):
+    """rgbnm_jpeg_image (192 bytes)."""
+    _fields_ = [(n, C.c_int32) for n in ("ncomp", "mcus_x", "mcus_y", "nblk", "status")] + \
+               [(n, C.c_int32 * 3) for n in ("dc_tab", "ac_tab", "hs", "vs")] + \
+               [(n, C.c_int32 * 10) for n in ("blk_comp", "blk_dx", "blk_dy")] + [("nruns", C.c_int32)]
+
+
+class JpegHuffTab(C.Structure):
+    """rgbnm_jpeg_hufftab (1440 bytes)."""
+    _fields_ = [("look", C.c_uint16 * 512), ("maxcode", C.c_int32 * 18), ("valoff", C.c_int32 * 18), ("vals", C.c_uint8 * 256),
+                ("bits", C.c_uint8 * 16)]
+
+
+class JpegPlan(C.Structure):
+    """rgbnm_jpeg_plan: caller-owned buffers and capacities in, counts out."""
+    _fields_ = [("stream", _vp), ("stream_cap", _sz), ("runs", _vp), ("images", _vp), ("tables", _vp), ("quant", _vp),
+                ("messages", _vp), ("runs_cap", C.c_int32), ("tables_cap", C.c_int32), ("message_len", C.c_int32),
+                ("threads", C.c_int32), ("stream_bytes", _sz), ("nruns", C.c_int32), ("ntables", C.c_int32), ("nbad", C.c_int32),
+                ("_pad", C.c_int32)]
+
+
+class JpegDevicePlan(C.Structure):
+    """rgbnm_jpeg_device_plan: the plan's buffers on the device."""
+    _fields_ = [("stream", _vp), ("stream_bytes", _sz), ("runs", _vp), ("images", _vp), ("tables", _vp), ("nruns", C.c_int32),
+                ("ntables", C.c_int32)]
+
+
+JPEG_STATUS = {-10: "truncated", -11: "inconsistent marker segment", -12: "unsupported kind of JPEG", -13: "grid differs",
+               -14: "restart markers inconsistent", -15: "plan buffers too small", -20: "unassigned Huffman code",
+               -21: "coefficient index past 63", -22: "more bits consumed than the run holds",
+               -23: "more than a byte of bits left over", -24: "inconsistent run record"}
+
 ABI_VERSION = 3      # include/rgbnm.h RGBNM_ABI_VERSION this binding was written against
 
 _P = C.POINTER
@@ -137,6 +175,8 @@ PROTOTYPES = {
     "rgbnm_dct_dft_ops": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "rgbnm_pixels_to_dct": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "rgbnm_dct_to_pixels": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "rgbnm_jpeg_prepare": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _P(JpegPlan)]),
+    "rgbnm_jpeg_decode_batch": (_i, [_P(JpegDevicePlan), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "rgbnm_softxent": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "rgbnm_softxent_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "rgbnm_softxent_grad": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),

@@ -26,6 +26,14 @@ buffers, and ONE H2D copy of the used prefix ships the batch: 787 KB -> ~380 KB 
 ("768 KB/img raw coefficients also make PCIe the next limit -- crop on host before H2D, or ship only the crop
 box").  The kernels read the packed boxes in place (rgbnm_dct_augment_packed): same output bits as the whole-grid path.
 
+`decode="device"` (default "host"): the producer thread reads the files and only FINDS their independent bit streams
+(dct_manip.prepare_jpeg_batch: a byte scan into a pinned ring of plans); the consumer ships the compressed bytes -- a tenth of the
+coefficients -- and launches the Huffman walk on a side stream (csrc/jpeg_decode.hip, one lane per restart run), up to `prefetch`
+batches ahead, each on a stream of its own, without a host sync; the step's stream waits on the batch's event.  The transform gets
+the same whole-grid tensors, bit for bit.  A file the device path refuses (progressive, ...) is decoded by the host reader and
+uploaded into its slot.  The device status of a batch comes back through a pinned copy and is looked at once it has arrived, a
+batch or more later; a negative one raises, naming the file.  Not combinable with crop_on_host.
+
 Everything except the H2D copy and the transform is host logic and runs (and is tested) without a GPU: with device="cpu"
 the loader yields the raw (Yq, CbCrq, quant) batches.  Files must share one coefficient grid (default 64 x 64 luma blocks =
 512 x 512, the pre-resized layout of the reference's dataset, README "resize to 512"); a file with another grid or an
@@ -41,7 +49,7 @@ from . import dct_manip as dm
 
 class DCTBatchLoader:
     def __init__(self, paths, labels, batch_size, device="cuda", grid=(64, 64), threads=None, prefetch=2, shuffle=True,
-                 seed=0, rank=0, world_size=1, drop_last=False, transform=None, crop_on_host=False):
+                 seed=0, rank=0, world_size=1, drop_last=False, transform=None, crop_on_host=False, decode="host"):
         if len(paths) != len(labels):
             raise ValueError("paths and labels differ in length")
         if batch_size <= 0 or prefetch < 1:
@@ -58,6 +66,15 @@ class DCTBatchLoader:
             if not isinstance(transform, CT.TrainTransform_DCT) or transform.eval_mode or self.device.type != "cuda":
                 raise ValueError("crop_on_host needs the fused train transform (TrainTransform_DCT) and a HIP device: the crop "
                                  "boxes are drawn before the decode; the eval transform reads the whole grid")
+        if decode not in ("host", "device"):
+            raise ValueError(f'decode must be "host" or "device", got {decode!r}')
+        if decode == "device" and self.crop_on_host:
+            raise ValueError('decode="device" ships the compressed bytes, a tenth of the coefficients: there is nothing left to crop '
+                             "before PCIe (crop_on_host=True belongs to the host decode)")
+        if decode == "device" and self.device.type != "cuda":
+            raise ValueError('decode="device" needs a HIP device')
+        self.decode = decode
+        self.h2d_bytes = 0
         self.last_packed = None        # crop_on_host: the (packed parameters, nops) of the batch yielded last (tests)
         self.epoch = 0
         n = len(self.paths)
@@ -94,9 +111,70 @@ class DCTBatchLoader:
     def _buffers(self):
         if self._ring is None:
             pin = self.device.type == "cuda"
+            if self.decode == "device":      # queued + launched but not yet uploaded + one being filled
+                self._ring = [dm.JpegBatchPlan(self.batch_size, self.grid, pin_memory=True) for _ in range(2 * self.prefetch + 1)]
+                return self._ring
             alloc = dm.alloc_packed if self.crop_on_host else dm.alloc_batch
             self._ring = [alloc(self.batch_size, self.grid, pin_memory=pin) for _ in range(self.prefetch + 2)]
         return self._ring
+
+    # ---- decode="device": the producer finds the runs, the device walks them
+    def _prepare_device(self, plan, bi):
+        """Producer side of one batch: file bytes -> plan (pinned ring slot).  A file the device cannot take is decoded by the host
+        reader here; its tensors travel with the item and are uploaded into its slot."""
+        if getattr(plan, "busy", None) is not None:
+            plan.busy.synchronize()          # the H2D copies of the slot's last batch
+            plan.busy = None
+        names = [self.paths[i] for i in bi]
+        datas, _ = dm._jpeg_bytes(names)
+        dm.prepare_jpeg_batch(datas, self.grid, out=plan, threads=min(self.threads, 16))
+        plan.names = names
+        hb, wb = self.grid
+        fallback = []
+        for k in (plan.status[:plan.n] != 0).nonzero().flatten().tolist():
+            try:
+                _, q, y, c = dm.read_coefficients_bytes(datas[k])
+            except dm.libjpeg_exception as e:
+                raise dm.libjpeg_exception(f"{names[k]}: {e}") from None
+            if tuple(y.shape) != (1, hb, wb, 8, 8) or (c is not None and tuple(c.shape) != (2, (hb + 1) // 2, (wb + 1) // 2, 8, 8)):
+                raise dm.libjpeg_exception(f"{names[k]}: reader error -4 (coefficient grid differs from the batch shape)")
+            q3 = torch.ones((3, 8, 8), dtype=torch.int16)
+            q3[:q.shape[0]] = q
+            fallback.append((k, y, c, q3))
+        return plan, fallback
+
+    def _launch_device(self, plan, fallback, lab, stream):
+        """Consumer side: uploads and the decode launch on a side stream; nothing here waits for the device."""
+        with torch.cuda.stream(stream):
+            Y, C, Q, st = dm.decode_jpeg_batch(plan, self.device)
+            for k, y, c, q in fallback:          # refused by prepare: the kernel leaves these slots alone
+                Y[k].copy_(y, non_blocking=True)
+                if c is None:
+                    C[k].zero_()
+                else:
+                    C[k].copy_(c, non_blocking=True)
+                Q[k].copy_(q, non_blocking=True)
+                st[k] = 0
+            ld = lab.to(self.device, non_blocking=True)
+            st_host = torch.empty(plan.n, dtype=torch.int32, pin_memory=True)
+            st_host.copy_(st, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(stream)
+        plan.busy = done
+        self.h2d_bytes = plan.h2d_bytes()
+        return (Y, C, Q, ld), (done, st_host, list(plan.names))
+
+    @staticmethod
+    def _check_status(pending, wait):
+        """Raise for the first batch whose device status (read back through a pinned copy) holds a negative code.  wait=False: only
+        batches whose copy has arrived are looked at, so the step is never stalled."""
+        while pending and (wait or pending[0][0].query()):
+            done, st, names = pending.pop(0)
+            done.synchronize()
+            bad = (st != 0).nonzero().flatten().tolist()
+            if bad:
+                raise dm.libjpeg_exception(f"{names[bad[0]]}: device decode error {int(st[bad[0]])} "
+                                           f"({dm.jpeg_status_text(st[bad[0]])}; {len(bad)} of {len(names)} files failed)")
 
     def __iter__(self):
         idx = self.indices()
@@ -117,7 +195,9 @@ class DCTBatchLoader:
                     if stop.is_set():
                         return
                     buf = ring[k % len(ring)]
-                    if sampler is not None:
+                    if self.decode == "device":
+                        item = (self._prepare_device(buf, bi), self.labels[bi])
+                    elif sampler is not None:
                         packed, nops = sampler.sample(len(bi), self.grid[0], self.grid[1])
                         Yp, Cp, Qp, yo, co = dm.read_coefficients_batch_crop([self.paths[i] for i in bi], packed["crop"],
                                                                              threads=self.threads, grid=self.grid, out=buf)
@@ -140,6 +220,37 @@ class DCTBatchLoader:
         th.start()
         copy_stream = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
         try:
+            if self.decode == "device":
+                # up to `prefetch` batches are uploaded and decoded ahead, each on a side stream of its own: a batch without restart
+                # markers is 256 long walks, and several of them run beside each other and beside the step
+                streams = [torch.cuda.Stream(self.device) for _ in range(self.prefetch)]
+                inflight, pending, launched, ended = [], [], 0, False
+                while True:
+                    while not ended and len(inflight) < self.prefetch:
+                        try:
+                            item = q.get(block=not inflight)
+                        except queue.Empty:
+                            break
+                        if item is None:
+                            ended = True
+                            break
+                        if isinstance(item, BaseException):
+                            raise item
+                        (plan, fallback), lab = item
+                        st = streams[launched % len(streams)]
+                        launched += 1
+                        inflight.append((st,) + self._launch_device(plan, fallback, lab, st))
+                    if not inflight:
+                        self._check_status(pending, wait=True)
+                        return
+                    st, (Yd, Cd, Qd, ld), check = inflight.pop(0)
+                    cur = torch.cuda.current_stream(self.device)
+                    cur.wait_event(check[0])
+                    for t in (Yd, Cd, Qd, ld):
+                        t.record_stream(cur)
+                    self._check_status(pending, wait=False)      # the batches before this one, as far as their status has arrived
+                    pending.append(check)
+                    yield self._finish(Yd, Cd, Qd, ld)
             while True:
                 item = q.get()
                 if item is None:

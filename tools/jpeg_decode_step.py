@@ -1,0 +1,166 @@
+#!/usr/bin/env python
+"""Measure the device JPEG entropy decode (csrc/jpeg_scan.h, jpeg_decode.hip) on one GPU.  B = 256 files of 512 x 512, 4:2:0, made as
+tests/test_loader_gpu.py makes them (16 x 16 random colours upsampled bicubic, plus N(0, 8) noise; 64 distinct files, repeated).
+
+  (a) dct_manip.prepare_jpeg_batch alone, on the host, ms per batch with 1 and with 16 threads (file bytes already in memory).
+  (b) the decode launch alone (plan already on the device: dct_manip.launch_jpeg_decode) for four file sets -- quality 75 and 90
+      without restart markers, quality 90 with one restart per MCU row and with one per 4 MCUs -- with the bytes a batch ships
+      beside the 201 MB of coefficients the host path ships.
+  (c) tools/pipeline_bench.py images/s: --decode host (the loader's existing path, 16 threads, measured again here) and --decode
+      device on the same files without restart markers and with one per MCU row; each a process of its own.
+
+Protocol of the other step tools: warm-up, then ROUNDS interleaved rounds (order reversed every other round); median and min - max.
+Writes profiles/jpeg_decode.json (parts given with --parts are replaced, the others kept) and prints it.
+usage: python tools/jpeg_decode_step.py [--parts a,b,c] [--rounds 6] [--batch 256]"""
+import argparse
+import io
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from rgb_no_more_amd import dct_manip as DM, lib as L  # noqa: E402
+from tools.aug_chain_step import timed, summary  # noqa: E402
+
+SETS = {"q75": dict(quality=75), "q90": dict(quality=90), "q90_rst_row": dict(quality=90, restart_marker_rows=1),
+        "q90_rst_4mcu": dict(quality=90, restart_marker_blocks=4)}
+COEF_BYTES = (64 * 64 + 2 * 32 * 32) * 128 + 3 * 128
+
+
+def synth(n, **kw):
+    from PIL import Image
+    rng = np.random.default_rng(0)
+    out = []
+    for _ in range(n):
+        small = rng.integers(0, 256, (16, 16, 3), dtype=np.uint8)
+        img = np.asarray(Image.fromarray(small).resize((512, 512), Image.BICUBIC), dtype=np.float32)
+        img = np.clip(img + rng.normal(0, 8, img.shape), 0, 255).astype(np.uint8)
+        buf = io.BytesIO()
+        Image.fromarray(img).save(buf, format="JPEG", subsampling="4:2:0", **kw)
+        out.append(buf.getvalue())
+    return out
+
+
+def spread(v):
+    return {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v)), "rounds": [float(x) for x in v]}
+
+
+def part_a(B, rounds, reps=4):
+    res = {}
+    for name in ("q90", "q90_rst_row"):
+        files = synth(64, **SETS[name])
+        batch = [files[i % 64] for i in range(B)]
+        plan = DM.JpegBatchPlan(B, (64, 64), pin_memory=True)
+        ms = {1: [], 16: []}
+        for th in (1, 16):
+            DM.prepare_jpeg_batch(batch, out=plan, threads=th)
+        assert plan.nbad == 0
+        for r in range(rounds):
+            for th in ((1, 16) if r % 2 == 0 else (16, 1)):
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    DM.prepare_jpeg_batch(batch, out=plan, threads=th)
+                ms[th].append((time.perf_counter() - t0) * 1e3 / reps)
+        res[name] = {"file_bytes_per_batch": sum(len(b) for b in batch), "runs": plan.nruns,
+                     "ms_per_batch_1_thread": spread(ms[1]), "ms_per_batch_16_threads": spread(ms[16]),
+                     "images_per_s_1_thread": B / np.median(ms[1]) * 1e3, "images_per_s_16_threads": B / np.median(ms[16]) * 1e3}
+        print(f"(a) {name}: 1 thread {np.median(ms[1]):.2f} ms, 16 threads {np.median(ms[16]):.2f} ms per batch", file=sys.stderr)
+    return res
+
+
+def part_b(B, rounds, iters, warmup):
+    dev = torch.device("cuda", 0)
+    fns, meta, keep = {}, {}, []
+    for name, kw in SETS.items():
+        files = synth(64, **kw)
+        batch = [files[i % 64] for i in range(B)]
+        plan = DM.prepare_jpeg_batch(batch, grid=(64, 64))
+        assert plan.nbad == 0
+        up = DM.upload_jpeg_plan(plan, dev)
+        out = DM.alloc_jpeg_out(B, (64, 64), dev)
+        out[2].copy_(up[4])
+        out[3].copy_(up[5])
+        DM.launch_jpeg_decode(plan, up, out)
+        torch.cuda.synchronize()
+        ref = DM.read_coefficients_bytes(batch[5])                        # same bits as the host reader, at the size that is timed
+        assert torch.equal(out[0][5].cpu(), ref[2]) and torch.equal(out[1][5].cpu(), ref[3]) and int(out[3].min()) == 0
+        keep.append((plan, up, out))
+        fns[name] = lambda plan=plan, up=up, out=out: DM.launch_jpeg_decode(plan, up, out)
+        meta[name] = {"runs": plan.nruns, "tables": plan.ntables, "h2d_bytes_per_batch": plan.h2d_bytes(),
+                      "h2d_bytes_host_path": COEF_BYTES * B, "file_bytes_per_batch": sum(len(b) for b in batch),
+                      "runs_per_wave": max(1, min(64, -(-plan.nruns // 2048)))}
+        # the same launch with every wave full (option "jpeg_lanes" = 64): what spreading the runs over more waves is worth
+        fns[name + "_64_per_wave"] = fns[name]
+        meta[name + "_64_per_wave"] = dict(meta[name], runs_per_wave=64)
+    out = summary(timed(list(fns), fns, warmup, rounds, iters,
+                        before=lambda cfg: L.set_option("jpeg_lanes", 64 if cfg.endswith("_64_per_wave") else 0)))
+    L.set_option("jpeg_lanes", 0)
+    for k, v in out.items():
+        v.update(meta[k])
+        v["images_per_s"] = B / v["ms_median"] * 1e3
+        print(f"(b) {k}: {v['ms_median']:.3f} ms ({v['ms_min']:.3f} - {v['ms_max']:.3f}) per batch, {v['runs']} runs, "
+              f"{v['h2d_bytes_per_batch'] / 1e6:.1f} MB shipped", file=sys.stderr)
+    return out
+
+
+def part_c(B, rounds, steps, warmup):
+    cfgs = {"host_16_threads": ["--decode", "host", "--threads", "16"],
+            "device": ["--decode", "device", "--threads", "16", "--prefetch", "4"],
+            "device_rst_row": ["--decode", "device", "--threads", "16", "--prefetch", "4", "--restart-rows", "1"]}
+    val = {k: [] for k in cfgs}
+    last = {}
+    for r in range(rounds):
+        for k in (list(cfgs) if r % 2 == 0 else list(cfgs)[::-1]):
+            cmd = [sys.executable, os.path.join(ROOT, "tools", "pipeline_bench.py"), "--steps", str(steps), "--warmup", str(warmup),
+                   "--batch", str(B)] + cfgs[k]
+            p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+            if p.returncode != 0:
+                raise RuntimeError(f"{' '.join(cmd)} failed:\n{p.stderr[-2000:]}")
+            last[k] = json.loads(p.stdout.strip().splitlines()[-1])
+            val[k].append(last[k]["value"])
+            print(f"(c) round {r} {k}: {last[k]['value']} images/s", file=sys.stderr, flush=True)
+    return {k: {"images_per_s": spread(val[k]), "ms_per_step": last[k]["ms_per_step"], "h2d_bytes_per_image": last[k]["h2d_bytes_per_image"],
+                "host_decode_only_images_per_sec": last[k]["host_decode_only_images_per_sec"], "steps": steps, "args": cfgs[k]}
+            for k in cfgs}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parts", default="a,b,c")
+    ap.add_argument("--rounds", type=int, default=6)
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--iters", type=int, default=5, help="(b) launches per timed block")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=40, help="(c) timed steps per process")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode.json"))
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "needs the GPU"
+    torch.cuda.set_device(0)
+    res = {}
+    if os.path.exists(a.out):
+        with open(a.out) as fh:
+            res = json.loads(fh.read())
+    res.update({"batch": a.batch, "rounds": a.rounds, "device": torch.cuda.get_device_name(0), "source_hash": L.source_hash(),
+                "host_cpus": DM.default_threads()})
+    parts = a.parts.split(",")
+    if "a" in parts:
+        res["a_prepare_host"] = part_a(a.batch, a.rounds)
+    if "b" in parts:
+        res["b_decode_launch"] = part_b(a.batch, a.rounds, a.iters, a.warmup)
+    if "c" in parts:
+        res["c_pipeline"] = part_c(a.batch, a.rounds, a.steps, 8)
+    line = json.dumps(res)
+    with open(a.out, "w") as fh:
+        fh.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()

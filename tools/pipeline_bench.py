@@ -3,7 +3,9 @@
 JPEG files -> librgbnm_reader.so (pthread pool, libjpeg coefficient read, no IDCT) into pinned int16 batches -> one H2D
 copy -> HIP dequant/crop/resize/RandAugment/ToRange -> mixup -> HIP ViT train step.  The decoder thread runs ahead of
 the GPU by a two-deep queue.  Prints one JSON line; never part of bench.py's `value` (that one starts from HBM-resident
-coefficients).  S-jpeg set: 64 files, 512x512, 4:2:0, q90 (32x32 uniform RGB upsampled bicubic + N(0,8) noise)."""
+coefficients).  --decode device: the loader ships the compressed bytes instead and the GPU walks the files' restart runs
+(csrc/jpeg_decode.hip; whole grids, no crop on the host); --restart-rows N writes the files with a restart marker per N MCU rows.
+S-jpeg set: 64 files, 512x512, 4:2:0, q90 (32x32 uniform RGB upsampled bicubic + N(0,8) noise)."""
 import argparse
 import json
 import os
@@ -20,7 +22,7 @@ from rgb_no_more_amd import custom_transforms as CT  # noqa: E402
 from rgb_no_more_amd import dct_manip as dm  # noqa: E402
 
 
-def write_sjpeg(d, n=64):
+def write_sjpeg(d, n=64, restart_rows=0, quality=90):
     from PIL import Image
     rng = np.random.default_rng(0)
     paths = []
@@ -29,7 +31,8 @@ def write_sjpeg(d, n=64):
         img = np.asarray(Image.fromarray(small).resize((512, 512), Image.BICUBIC), dtype=np.float32)
         img = np.clip(img + rng.normal(0, 8, img.shape), 0, 255).astype(np.uint8)
         p = os.path.join(d, f"s{i:03d}.jpg")
-        Image.fromarray(img).save(p, quality=90, subsampling="4:2:0")
+        kw = {"restart_marker_rows": restart_rows} if restart_rows else {}      # one restart marker per so many MCU rows
+        Image.fromarray(img).save(p, quality=quality, subsampling="4:2:0", **kw)
         paths.append(p)
     return paths
 
@@ -41,11 +44,17 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--threads", type=int, default=dm.default_threads())
     ap.add_argument("--crop-on-host", type=int, default=1, help="1: only the crop boxes cross PCIe (loader crop_on_host)")
+    ap.add_argument("--decode", choices=("host", "device"), default="host",
+                    help="device: the loader ships the compressed bytes and the GPU walks the restart runs (no crop on the host then)")
+    ap.add_argument("--restart-rows", type=int, default=0, help="synthetic files carry a restart marker every N MCU rows (0: none)")
+    ap.add_argument("--prefetch", type=int, default=2, help="batches the loader keeps ahead of the step")
     a = ap.parse_args()
+    if a.decode == "device":
+        a.crop_on_host = 0
     dev = "cuda:0"
     torch.cuda.set_device(0)
     tmp = tempfile.mkdtemp(prefix="sjpeg_")
-    paths = write_sjpeg(tmp)
+    paths = write_sjpeg(tmp, restart_rows=a.restart_rows)
     fsize = sum(os.path.getsize(p) for p in paths) / len(paths)
     B = a.batch
     batch_paths = [paths[i % len(paths)] for i in range(B)]
@@ -76,8 +85,8 @@ def main():
     from rgb_no_more_amd.loader import DCTBatchLoader
     nb = a.warmup + a.steps + 4
     loader = DCTBatchLoader([batch_paths[i % B] for i in range(nb * B)], [int(v) for v in torch.randint(0, 999, (nb * B,))], B,
-                            device=dev, threads=a.threads, prefetch=2, shuffle=False,
-                            transform=aug if a.crop_on_host else None, crop_on_host=bool(a.crop_on_host))
+                            device=dev, threads=a.threads, prefetch=a.prefetch, shuffle=False,
+                            transform=aug if a.crop_on_host else None, crop_on_host=bool(a.crop_on_host), decode=a.decode)
     it = iter(loader)
 
     def step():
@@ -103,11 +112,13 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     it.close()
-    out = {"metric": "images/sec JPEG-Ti DCT train step fed from JPEG files (host entropy decode + H2D inside)",
+    h2d = loader.h2d_bytes / B if (a.crop_on_host or a.decode == "device") else 64 * 64 * 64 * 2 + 2 * 32 * 32 * 64 * 2 + 3 * 64 * 2
+    out = {"metric": f"images/sec JPEG-Ti DCT train step fed from JPEG files ({a.decode} entropy decode + H2D inside)",
+           "decode": a.decode, "restart_rows": a.restart_rows, "prefetch": a.prefetch,
            "value": round(B * a.steps / dt, 1), "unit": "images/sec", "n_gpus": 1, "steps": a.steps,
            "ms_per_step": round(1e3 * dt / a.steps, 3), "per_gpu_batch": B, "host_threads": a.threads,
            "host_decode_only_images_per_sec": round(dec, 1), "avg_jpeg_bytes": round(fsize),
-           "h2d_bytes_per_image": round(loader.h2d_bytes / B) if a.crop_on_host else 64 * 64 * 64 * 2 + 2 * 32 * 32 * 64 * 2 + 3 * 64 * 2,
+           "h2d_bytes_per_image": round(h2d),
            "crop_on_host": bool(a.crop_on_host),
            "loss": round(float(loss.item()), 4),
            "note": "one process; decoder thread (pthread pool inside librgbnm_reader.so, GIL released) runs two batches "
