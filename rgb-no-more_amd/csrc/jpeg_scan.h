@@ -53,6 +53,7 @@ static inline bool derive(const RawTable& r, rgbnm_jpeg_hufftab* t) {
   for (int l = 1; l <= 16; ++l) {
     const int cnt = r.bits[l - 1];
     if (cnt) {
+      if (code + cnt > (1 << l)) return false;  // more codes of this length than the prefix leaves room for: before `look` is indexed
       t->valoff[l] = k - code;
       for (int j = 0; j < cnt; ++j, ++k, ++code)
         if (l <= 9) {
@@ -60,7 +61,6 @@ static inline bool derive(const RawTable& r, rgbnm_jpeg_hufftab* t) {
           for (int f = 0; f < (1 << (9 - l)); ++f) t->look[lo + f] = (uint16_t)((l << 8) | r.vals[k]);
         }
       t->maxcode[l] = code - 1;
-      if (code > (1 << l)) return false;      // more codes of this length than the prefix leaves room for
     } else {
       t->maxcode[l] = -1;
     }

@@ -5,8 +5,8 @@
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -pthread tools/jpeg_scan_check.cpp -o jpeg_scan_check
 //   ./jpeg_scan_check DIR/*.jpg
 //
-// It parses and decodes every file as given (that must succeed), then every truncation length of the first two, then 6000 single-byte
-// mutations from a fixed seed.  Every outcome must be "decoded" or "refused with a status"; the outputs are heap blocks of the exact
+// It parses and decodes every file as given (that must succeed; a file named *_refused.jpg must be refused by the parser instead),
+// then every truncation length of the first two, then 6000 single-byte mutations from a fixed seed.  Every outcome must be "decoded" or "refused with a status"; the outputs are heap blocks of the exact
 // size, so a store outside them, like any read outside the file or the plan, stops the program.  Exit status 0: clean.
 #define __host__
 #define __device__
@@ -117,7 +117,11 @@ int main(int argc, char** argv) {
   for (const File& f : files) {
     const int st = run_one(f.bytes.data(), f.bytes.size(), f.Hb, f.Wb, &whole, &sum);
     printf("%-28s %7zu bytes  grid %3d x %3d  status %d\n", f.name.c_str(), f.bytes.size(), f.Hb, f.Wb, st);
-    if (st) { fprintf(stderr, "%s must decode as given\n", f.name.c_str()); return 1; }
+    const bool refuse = f.name.size() >= 12 && f.name.compare(f.name.size() - 12, 12, "_refused.jpg") == 0;
+    if (refuse ? (st == 0 || whole.refused_walk) : st != 0) {
+      fprintf(stderr, "%s must %s as given\n", f.name.c_str(), refuse ? "be refused by the parser" : "decode");
+      return 1;
+    }
   }
   for (size_t k = 0; k < 2; ++k)
     for (size_t len = 0; len < files[k].bytes.size(); ++len) run_one(files[k].bytes.data(), len, files[k].Hb, files[k].Wb, &cut, &sum);
