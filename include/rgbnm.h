@@ -853,7 +853,13 @@ int rgbnm_ln_generic_bwd(int dtype, const void* dy, const void* x, const float* 
  * cosine attention, shift mask -100.
  * out [B, res*res, C]; lse [B * nW * heads * 64] saved for backward.  Backward writes dbias (per-wave partials in the
  * workspace, deterministic reduction), one partial d(scale) per (window, head) into dscale_part [B * nW * heads] and -- when
- * dscale is not NULL -- their sum into dscale [heads] (a job of the same batched reduction). */
+ * dscale is not NULL -- their sum into dscale [heads] (a job of the same batched reduction).
+ * Normalisation contract, forward and backward: q^ = q / max(|q|, eps), eps = 1e-12 as F.normalize, for rows with |q|^2 finite in
+ * fp32 (likewise k).  A row with |q| < eps is scaled by 1 / eps (an all-zero row stays zero) and its gradient is
+ * dq = dq^ / eps WITHOUT the projection (I - q^ q^T): the clamp passes no gradient to the norm, as autograd of F.normalize;
+ * every other row gets (I - q^ q^T) dq^ / |q|.  The kernel decides by its fp32 reciprocal norm reaching 1e12f, so rows whose norm
+ * lies within fp32 rounding of eps may fall on either side.  Results that leave the element type's range (fp16: the 1 / eps of a
+ * clamped row) are stored as +-inf. */
 int rgbnm_window_attention_fwd(int dtype, const void* qkv, const float* bias, const float* scale, void* out, float* lse,
                                int B, int res, int C, int heads, int shift, void* stream);
 size_t rgbnm_window_attention_bwd_workspace(int B, int res, int heads);

@@ -487,9 +487,14 @@ __global__ __launch_bounds__(256) void cpb_bias_kernel(CpbArgs a) {
   const int h = blockIdx.y;
   if (h >= b.heads) return;
   const float* t = a.table + ((size_t)blockIdx.x * CPB_MAXH + h) * CPB_E;
-  for (int p = threadIdx.x; p < CPB_POS; p += 256)
-    b.bias[(size_t)h * CPB_POS + p] = 16.f / (1.f + expf(-t[a.index[p]]));
-  if (threadIdx.x == 0) b.scale[h] = expf(fminf(b.ls[h], 4.605170185988092f));       // ln(1 / 0.01)
+  for (int p = threadIdx.x; p < CPB_POS; p += 256) {
+    // expf(-t) overflows below t = -88.7, where 16 sigmoid(t) = 16 e^t to fp32 is still a number down to t = -106
+    const float tv = t[a.index[p]], e = expf(-tv);
+    b.bias[(size_t)h * CPB_POS + p] = e < INFINITY ? 16.f / (1.f + e) : expf(tv + 2.7725887222397811f);   // ln 16
+  }
+  // (one thread per head, in double: the build's -ffp-contract=fast folds expf's own `x log2e - round` into an fma and counts the
+  // product's rounding residual twice, an error of up to 0.35 |x| u -- 3.3 ulp at logit_scale = -20)
+  if (threadIdx.x == 0) b.scale[h] = (float)exp((double)fminf(b.ls[h], 4.605170185988092f));       // ln(1 / 0.01)
 }
 
 // grid (nblocks, CPB_MAXH): d table[h][e] = 16 s (1 - s) * sum of d bias over the <= 64 positions that read entry e (inv: [225][64],
@@ -512,10 +517,12 @@ __global__ __launch_bounds__(256) void cpb_dtable_kernel(CpbArgs a) {
     float acc = 0.f;
 #pragma unroll
     for (int q = 0; q < 64; ++q) acc += val[q];
-    const float s = 1.f / (1.f + expf(-a.table[((size_t)blockIdx.x * CPB_MAXH + h) * CPB_E + e]));
-    a.dtable[((size_t)blockIdx.x * CPB_MAXH + h) * CPB_E + e] = acc * 16.f * s * (1.f - s);
+    // s (1 - s) = x / (1 + x)^2 with x = e^-|t|: no overflow, and no cancellation in 1 - s (which left the tail 8 < t < 17
+    // with a fifth of its value as error and everything beyond at 0)
+    const float x = expf(-fabsf(a.table[((size_t)blockIdx.x * CPB_MAXH + h) * CPB_E + e])), r = 1.f / (1.f + x);
+    a.dtable[((size_t)blockIdx.x * CPB_MAXH + h) * CPB_E + e] = acc * (16.f * x * r * r);
   }
-  if (e == 255) b.dls[h] = b.ls[h] <= 4.605170185988092f ? b.dscale[h] * expf(b.ls[h]) : 0.f;    // clamp passes its gradient inside the range
+  if (e == 255) b.dls[h] = b.ls[h] <= 4.605170185988092f ? b.dscale[h] * (float)exp((double)b.ls[h]) : 0.f;    // clamp passes its gradient inside the range
 }
 
 // grid (nblocks, 16): 32 hidden units per workgroup, EIGHT lanes per unit, each walking an eighth of the 225 entries; the eight partial

@@ -175,8 +175,10 @@ struct WinPos {
     }
   }
 };
-// 1 / max(|x|, 1e-12) from |x|^2  (F.normalize's eps; v_rsq_f32 is 1 ulp)
-__device__ __forceinline__ float inv_norm(float n2) { return fminf(__builtin_amdgcn_rsqf(n2), 1e12f); }
+// 1 / max(|x|, 1e-12) from |x|^2  (F.normalize's eps; v_rsq_f32 is 1 ulp).  A row whose reciprocal norm comes out as NORM_CLAMP
+// was clamped: its backward is dy / eps without the projection (autograd of clamp_min), see the contract in include/rgbnm.h
+constexpr float NORM_CLAMP = 1e12f;
+__device__ __forceinline__ float inv_norm(float n2) { return fminf(__builtin_amdgcn_rsqf(n2), NORM_CLAMP); }
 
 template <typename T> __device__ __forceinline__ Frag<T> rowfrag(const T* tile, int row, int c, int g) {
   return load_frag<T>(tile + row * RP + c * WA<T>::CH + g * WA<T>::EPL);
@@ -629,7 +631,7 @@ __global__ __launch_bounds__(64 * WA<T>::BWD_WAVES) void win_attn_bwd_kernel(
 #pragma unroll
         for (int fi = 0; fi < A::FPT; ++fi) mma(dq, tok_frag<T>(trK, Knt, l31, t, fi, g), pfrag<T>(dss, fi));   // rows = d
       }
-      // d(x/|x|) = (I - n n^T) dy / |x| ; dq[r] belongs to d = acc_row(r), the other 16 d live in lane ^ 32
+      // d(x/max(|x|, eps)) = (I - n n^T) dy / |x| where |x| >= eps, dy / eps below ; dq[r] belongs to d = acc_row(r), the other 16 d live in lane ^ 32
       float qn[16];
       float proj = 0.f;
 #pragma unroll
@@ -643,6 +645,7 @@ __global__ __launch_bounds__(64 * WA<T>::BWD_WAVES) void win_attn_bwd_kernel(
       }
       proj += __shfl_xor(proj, 32, 64);
       const float ir = Rq[q];
+      proj = ir == NORM_CLAMP ? 0.f : proj;            // |q| below eps: the clamp passes no gradient to the norm, d q = dy / eps
       // 16-bit: rows go to the staging tile and leave as whole 64-byte token slices (16 lines per store instruction instead of 64)
       T* drow = A::STAGE_DQ ? St + q * RP : dqkv + ((size_t)b * res * res + tokq) * 3 * C + h * HD;
 #pragma unroll
@@ -736,6 +739,7 @@ __global__ __launch_bounds__(64 * WA<T>::BWD_WAVES) void win_attn_bwd_kernel(
       }
       proj += __shfl_xor(proj, 32, 64);
       const float ir = Rk[key];
+      proj = ir == NORM_CLAMP ? 0.f : proj;            // as for dq
       // dk / dv rows replace the key tile's own Kn / V rows (kf, vf and kn are in registers; nobody else reads these rows in
       // this phase) and leave as whole token slices after both tiles
       (void)tokk;

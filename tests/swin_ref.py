@@ -7,7 +7,8 @@ tests/test_swin_edges_cpu.py.  A plain module, imported by name from the tests (
   column) in row-major order, which is also the window order of the kernel's lse [(w heads + h) 64 + query] and
   dscale_part [w heads + h].
 - win_fwd / win_bwd: the operation in fp64 on one chunk of windows, plus the forward-error terms of the bound (see the docstring
-  of tests/test_swin_edges.py for the terms).  The backward runs on the kernel's own out and lse.
+  of tests/test_swin_edges.py for the terms).  The backward runs on the kernel's own out and lse.  Rows below F.normalize's eps
+  get g / eps without the projection, as autograd does (tests/test_swin_value_regimes_cpu.py anchors that to the oracle).
 - head_grid / geometry: a copy of swin_attn.hip's head_grid() and of the WA<T> LDS sizes, pinned to the C++ source by the CPU
   test (rgbnm_window_attention_bwd_workspace) and used to pick the cases that reach each launch class.
 """
@@ -122,9 +123,17 @@ def window_mask(res, shift, nimg, device):
 
 
 # ------------------------------------------------------------------------------------------------------------- fp64 math
+EPS = 1e-12                                                     # F.normalize's eps
+
+
 def normalize(x):
-    n = x.norm(dim=-1, keepdim=True).clamp_min(1e-12)          # F.normalize(eps = 1e-12)
+    n = x.norm(dim=-1, keepdim=True).clamp_min(EPS)            # F.normalize(eps = 1e-12)
     return x / n, n
+
+
+def clamped(x):
+    """[..., 1] bool: rows whose norm lies below eps.  clamp_min passes no gradient there (it does at |x| == eps)."""
+    return x.norm(dim=-1, keepdim=True) < EPS
 
 
 def logits(q, k, bias, scale, mask):
@@ -139,7 +148,7 @@ def logits(q, k, bias, scale, mask):
     if mask is not None:
         m = mask[:, None]
         lg = lg + m
-    return {"qh": qh, "kh": kh, "nq": nq, "nk": nk, "cos": cos, "A": A, "lg": lg, "s": s, "m": m}
+    return {"qh": qh, "kh": kh, "nq": nq, "nk": nk, "cq": clamped(q), "ck": clamped(k), "cos": cos, "A": A, "lg": lg, "s": s, "m": m}
 
 
 def logit_err(L, uT, lse):
@@ -170,10 +179,15 @@ def win_fwd(q, k, v, bias, scale, mask, uT, uP, eta=0.0):
     return L, out, lse, P, E_out, E_lse
 
 
-def proj_back(nh, nrm, g, Eg, uT):
+def proj_back(nh, nrm, g, Eg, uT, clamp=None, project_clamped=False):
     """d x = (I - n n^T) g / |x| for n = x / |x| (F.normalize's backward), and its error bound: Eg through the projection, n
-    rounded to T in the kernel (2 u_T), the fp32 dot product / subtraction / 1 / |x| (24 u)."""
+    rounded to T in the kernel (2 u_T), the fp32 dot product / subtraction / 1 / |x| (24 u).  Rows with clamp set (|x| < eps, nrm
+    = eps) get g / eps without the projection: autograd of x / clamp_min(|x|, eps) passes nothing to the norm there.  The bound
+    keeps the projection's terms on those rows too (they only add |n|^2 of it).  project_clamped: the unconditional form, kept to
+    show what it misses (tests/test_swin_value_regimes_cpu.py)."""
     dot = (nh * g).sum(-1, keepdim=True)
+    if clamp is not None and not project_clamped:
+        dot = torch.where(clamp, torch.zeros_like(dot), dot)
     dx = (g - nh * dot) / nrm
     na = nh.abs()
     mg = g.abs() + na * (na * g.abs()).sum(-1, keepdim=True)
@@ -181,7 +195,7 @@ def proj_back(nh, nrm, g, Eg, uT):
     return dx, E
 
 
-def win_bwd(L, v, dO, O_k, lse_k, uT, uP, eta=0.0):
+def win_bwd(L, v, dO, O_k, lse_k, uT, uP, eta=0.0, project_clamped=False):
     """Backward of one chunk on the kernel's own out O_k and lse lse_k (fp64 of the T values).  Returns a dict of references
     and error terms (E_*, without ulp) for dq, dk, dv [n, H, 64, 32], dS and its error term [n, H, 64, 64] (summed over windows
     by the caller into d(bias)), and the d(scale) partial per (window, head) with its error term."""
@@ -205,11 +219,11 @@ def win_bwd(L, v, dO, O_k, lse_k, uT, uP, eta=0.0):
     dqh = s * (dS @ L["kh"])
     # (+ eta sum_j |k^_j|: s dS rounded into T's subnormals)
     E_dqh = s * (E_dS @ L["kh"].abs()) + (2 * uT + 64 * U) * s * (dS.abs() @ L["kh"].abs()) + eta * L["kh"].abs().sum(-2, keepdim=True)
-    r["dq"], r["E_dq"] = proj_back(L["qh"], L["nq"], dqh, E_dqh, uT)
+    r["dq"], r["E_dq"] = proj_back(L["qh"], L["nq"], dqh, E_dqh, uT, L["cq"], project_clamped)
     dkh = s * (dS.transpose(-1, -2) @ L["qh"])
     E_dkh = (s * (E_dS.transpose(-1, -2) @ L["qh"].abs()) + (2 * uT + 64 * U) * s * (dS.abs().transpose(-1, -2) @ L["qh"].abs())
              + eta * L["qh"].abs().sum(-2, keepdim=True))
-    r["dk"], r["E_dk"] = proj_back(L["kh"], L["nk"], dkh, E_dkh, uT)
+    r["dk"], r["E_dk"] = proj_back(L["kh"], L["nk"], dkh, E_dkh, uT, L["ck"], project_clamped)
     # dv = P^T dO: P from the kernel's logits (P e), P rounded to T (u_P), 64 u accumulation
     r["dv"] = P.transpose(-1, -2) @ dO
     mdv = P.transpose(-1, -2) @ dO.abs()

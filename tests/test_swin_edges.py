@@ -14,7 +14,8 @@ Window attention (u = 2^-24, u_T = 2^-8 bf16 / 2^-11 fp16 / u fp32, A = |q^||k^|
 - out: (P o e)|v| + (sum_j P e) P|v| (the logit error through the softmax); P rounded to T before P V: u_T P|v| (16-bit);
   fp32 P V accumulation: 64 u P|v|.   lse: sum_j P e + 4 u (|lse| + 1).
 - backward, on the kernel's own out and lse: dS = P (dO V^T - dO . O): P e |dP - D| + 40 u P (|dO||V|^T + |dO| . |O|).
-  dq^ = s dS k^: s E_dS |k^| + (2 u_T + 64 u) s |dS||k^| (s dS and k^ rounded to T before the MFMA); dq = (I - q^q^^T) dq^ / |q|:
+  dq^ = s dS k^: s E_dS |k^| + (2 u_T + 64 u) s |dS||k^| (s dS and k^ rounded to T before the MFMA); dq = (I - q^q^^T) dq^ / |q|
+  (dq^ / eps where |q| < eps = 1e-12, as autograd of F.normalize: include/rgbnm.h):
   E through the projection + (2 u_T + 24 u)(|dq^| + |q^| (|q^| . |dq^|)) / |q| (q^ rounded to T, fp32 projection); dk likewise.
   dv = P^T dO: (P o e)^T |dO| + (u_T + 64 u) P^T |dO|.
   d(bias)[h] = sum over windows of dS: sum E_dS + (most windows per wave + slices) u sum |dS| (the wave's running sum, then
@@ -122,20 +123,22 @@ class Fit:
 
 
 # ------------------------------------------------------------------------------------------------------------- window attention
-def win_inputs(dt, B, res, heads, seed):
+def win_inputs(dt, B, res, heads, seed, device=DEV):
+    """The default inputs of win_case.  device: where the generator draws (the CPU file compares this recipe with its copy of
+    the one before the keyword existed, bit for bit)."""
     C = heads * 32
     N = B * res * res
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    x = torch.randn((N, 3, heads, 32), generator=g, device=DEV)
+    g = torch.Generator(device=device).manual_seed(seed)
+    x = torch.randn((N, 3, heads, 32), generator=g, device=device)
     # q / k norms over four orders of magnitude per (token, head): cosine attention must not see them
-    x[:, :2] *= 10.0 ** (torch.rand((N, 2, heads, 1), generator=g, device=DEV) * 4 - 2)
+    x[:, :2] *= 10.0 ** (torch.rand((N, 2, heads, 1), generator=g, device=device) * 4 - 2)
     qkv = nan_padded(x.reshape(N, 3 * C).to(dt), extra_rows=7)
-    dout = nan_padded(torch.randn((N, C), generator=g, device=DEV).to(dt), extra_rows=5)
-    bias = torch.rand((heads, 64, 64), generator=g, device=DEV) * 16
+    dout = nan_padded(torch.randn((N, C), generator=g, device=device).to(dt), extra_rows=5)
+    bias = torch.rand((heads, 64, 64), generator=g, device=device) * 16
     bias[:, ::7, ::5] = 15.999                      # the top of 16 sigmoid
     bias[:, 1::9, 2::11] = 1e-3
     bias = nan_padded(bias.reshape(heads * 64, 64), extra_rows=64).view(heads, 64, 64)
-    scale = nan_padded(torch.tensor([SCALES[(h + seed) % len(SCALES)] for h in range(heads)], device=DEV).view(heads, 1),
+    scale = nan_padded(torch.tensor([SCALES[(h + seed) % len(SCALES)] for h in range(heads)], device=device).view(heads, 1),
                        extra_rows=3).view(heads)
     return qkv, dout, bias, scale
 
@@ -156,8 +159,12 @@ def bits(t):
     return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32).clone()
 
 
-def win_case(dt, B, res, heads, shift, seed, fit, seen, xcd=1, twice=False):
-    """One forward + backward of the window attention, checked element-wise; returns the launch classes it reached."""
+def win_case(dt, B, res, heads, shift, seed, fit, seen, xcd=1, twice=False, qkv=None, dout=None, bias=None, scale=None, c=None,
+             check=None):
+    """One forward + backward of the window attention, checked element-wise; returns the launch classes it reached.
+    qkv / dout / bias / scale: the caller's device tensors (with NaN behind them) in place of win_inputs(seed)'s, each on its own;
+    c: the bound's weights per output in place of WIN_C[dt]; check: called with win_check's arguments in its place (the value
+    regimes of tests/test_swin_value_regimes.py).  The defaults are the tensors and bounds from before the keywords existed."""
     C = heads * 32
     N = B * res * res
     nw = res // 8
@@ -167,7 +174,9 @@ def win_case(dt, B, res, heads, shift, seed, fit, seen, xcd=1, twice=False):
     gf = R.geometry(ESZ[dt], "fwd", B, res, heads, ncu, xcd)
     gb = R.geometry(ESZ[dt], "bwd", B, res, heads, ncu, xcd)
     seen.update(R.classes(ESZ[dt], "fwd", gf) | R.classes(ESZ[dt], "bwd", gb))
-    qkv, dout, bias, scale = win_inputs(dt, B, res, heads, seed)
+    if qkv is None or dout is None or bias is None or scale is None:
+        own = win_inputs(dt, B, res, heads, seed)
+        qkv, dout, bias, scale = (o if t is None else t for t, o in zip((qkv, dout, bias, scale), own))
     out = guarded(N, C, dt)
     lse = guarded(nwin * heads * 64, None, F32)
     _, nf = launched(lambda: win_fwd_call(dt, qkv, bias, scale, out.t, lse.t, B, res, heads, shift))
@@ -202,24 +211,27 @@ def win_case(dt, B, res, heads, shift, seed, fit, seen, xcd=1, twice=False):
         assert torch.equal(bits(dbias.t), first[1]) and torch.equal(bits(dsc.t), first[2]), where + ": d(bias) / d(scale) bits differ"
         print(f"{where}: d(bias) and d(scale) identical bits over two launches")
     ws.check(where + " workspace", written=False)
-    win_check(dt, B, res, heads, shift, qkv, dout, bias, scale, out, lse, dqkv, dbias, dsp, dsc, gb, fit, where)
+    if check is not None:
+        check(dt, B, res, heads, shift, qkv, dout, bias, scale, out, lse, dqkv, dbias, dsp, dsc, gb, fit, where)
+    else:
+        win_check(dt, B, res, heads, shift, qkv, dout, bias, scale, out, lse, dqkv, dbias, dsp, dsc, gb, fit, where, c)
     return R.classes(ESZ[dt], "fwd", gf) | R.classes(ESZ[dt], "bwd", gb)
 
 
-def win_check(dt, B, res, heads, shift, qkv, dout, bias, scale, out, lse, dqkv, dbias, dsp, dsc, gb, fit, where):
+def win_check(dt, B, res, heads, shift, qkv, dout, bias, scale, out, lse, dqkv, dbias, dsp, dsc, gb, fit, where, c=None):
     C = heads * 32
     nw = res // 8
     nwin = B * nw * nw
     uT = KC.U_OF[dt]
     uP = 0.0 if dt == F32 else uT
-    cw = WIN_C[dt]
+    cw = WIN_C[dt] if c is None else c
     k = NAMES[dt]
     qkv_w, dout_w = R.partition(qkv, B, res, shift), R.partition(dout, B, res, shift)
     out_w, dqkv_w = R.partition(out.t, B, res, shift), R.partition(dqkv.t, B, res, shift)
     lse_k = lse.t.view(nwin, heads, 64)
     dsp_k = dsp.t.view(nwin, heads)
     b64, s64 = bias.double(), scale.double()
-    db_ref = torch.zeros(heads, 64, 64, dtype=torch.float64, device=DEV)
+    db_ref = torch.zeros(heads, 64, 64, dtype=torch.float64, device=qkv.device)
     db_E, db_abs = torch.zeros_like(db_ref), torch.zeros_like(db_ref)
     dsp_ref, dsp_E, dsp_mag = [], [], []
     per = max(1, (1 << 24) // (nw * nw * heads * 4096))      # images per chunk: 128 MB per [windows, heads, 64, 64] fp64 tensor
@@ -229,7 +241,7 @@ def win_check(dt, B, res, heads, shift, qkv, dout, bias, scale, out, lse, dqkv, 
         tag = f"{where} windows {w0}..{w1 - 1}, element (window - {w0}, head, query, d)"
         x = qkv_w[w0:w1].double()
         q, kk, v = (R.split_heads(x[..., i * C:(i + 1) * C], heads) for i in range(3))
-        mask = R.window_mask(res, shift, nimg, DEV)
+        mask = R.window_mask(res, shift, nimg, qkv.device)
         Lg, o_ref, lse_ref, P, E_out, E_lse = R.win_fwd(q, kk, v, b64, s64, mask, uT, uP, ETA[dt])
         O_k = R.split_heads(out_w[w0:w1], heads)
         fit(k + "-out", O_k, o_ref, E_out, dt, 1, cw["out"], tag + " out")
@@ -329,10 +341,14 @@ def cpb_consts():
             SW.inverse_index(idx, 225).contiguous())
 
 
-def cpb_case(heads, seed, fit):
+def cpb_case(heads, seed, fit, span=None, ls_low=()):
+    """span: W2 of every block rescaled so that its table spans +-span (saturation of 16 sigmoid; the bias must then be exactly
+    0.0 / 16.0 where the fp32 rounding of the fp64 value is, nothing may be NaN, and d(table) exactly 0 where 16 s (1 - s) rounds
+    to 0 in fp32); ls_low: blocks whose logit_scale is -20.  Returns the number of (exactly 0, exactly 16) bias elements."""
     n = len(heads)
     coords, index, inv = cpb_consts()
-    where = f"position bias {n} blocks"
+    where = f"position bias {n} blocks" + (f" span {span}" if span else "")
+    sat = [0, 0]
     lib = L.lib()
     P, O = [], []
     for i, h in enumerate(heads):
@@ -340,6 +356,11 @@ def cpb_case(heads, seed, fit):
         w1, b1, w2 = rnd((512, 2), s), rnd((512,), s + 1, 0.5), rnd((h, 512), s + 2, 0.1)
         ls = torch.rand(h, device=DEV, generator=torch.Generator(device=DEV).manual_seed(s + 3)) * 4 + 1.5   # some > ln 100
         ls[ls.sub(math.log(100.0)).abs() < 1e-3] += 2e-3
+        if i in ls_low:
+            ls[:] = -20.0
+        if span:
+            t0 = (ST.coords_table(8).double().reshape(-1, 2).to(DEV) @ w1.double().T + b1.double()).clamp_min(0) @ w2.double().T
+            w2 = (w2.double() * (span / t0.abs().amax(0))[:, None]).float()          # per head: max |table| = span
         dbias, dscale = rnd((h, 4096), s + 4), rnd((h,), s + 5)
         P.append([nan_padded(t.view(t.shape[0], -1) if t.dim() > 1 else t.view(-1, 1), extra_rows=3) for t in
                   (w1, b1, w2, ls, dbias, dscale)])
@@ -380,10 +401,21 @@ def cpb_case(heads, seed, fit):
         t = hid @ w2.T                                          # [225, h]
         E_t = 18 * U * (Hm @ w2.abs().T)
         sg = torch.sigmoid(t)
-        d1 = 16 * sg * (1 - sg)
+        ea = torch.exp(-t.abs())
+        d1 = 16 * ea / (1 + ea) ** 2                            # 16 s (1 - s) without the cancellation of 1 - s beyond t = 37
         bias_ref = (16 * sg)[pidx].T                            # [h, 4096]
         E_b = (d1 * E_t + 4 * U * 16 * sg)[pidx].T
         fit("bias", o["bias"].t.view(h, 4096), bias_ref, E_b, F32, 1, CPB_C["bias"], tg + " bias (head, position)")
+        if span:
+            got_b = o["bias"].t.view(h, 4096)
+            assert float(t.abs().max()) > 0.999 * span and all(bool(torch.isfinite(g.t).all()) for g in o.values()), tg
+            for v_, j in ((0.0, 0), (16.0, 1)):
+                at = bias_ref.float() == v_
+                assert bool((got_b[at] == v_).all()), f"{tg}: bias not exactly {v_} where fp32 rounds there"
+                sat[j] += int(at.sum())
+            dtk = dtable.t.view(-1, 24, 225)[i, :h].T                  # scratch of the backward: d table [225, h]
+            flat = (16 * torch.exp(-t.abs())).float() == 0             # 16 s (1 - s) = 16 e^-|t| (1 + e^-|t|)^-2 rounds to 0 in fp32: |t| > 106.7
+            assert bool((dtk[flat] == 0).all()) and int(flat.sum()) > 0, f"{tg}: d(table) not exactly 0 at saturation"
         sc_ref = torch.exp(ls.clamp(max=math.log(100.0)))
         fit("scale", o["scale"].t, sc_ref, 4 * U * sc_ref, F32, 1, 1.0, tg + " scale (head)")
         Gs = torch.zeros(225, h, dtype=torch.float64, device=DEV).index_add_(0, pidx, dbias.T)
@@ -406,6 +438,7 @@ def cpb_case(heads, seed, fit):
         dls_ref = torch.where(inside, dscale * torch.exp(ls), torch.zeros_like(ls))
         fit("dls", o["dls"].t, dls_ref, 4 * U * dls_ref.abs(), F32, 1, 1.0, tg + " dls (head)")
         assert bool((o["dls"].t[~inside] == 0).all()), tg + ": d(logit_scale) beyond ln 100 not exactly 0"
+    return tuple(sat)
 
 
 def test_position_bias_at_model_block_counts():
