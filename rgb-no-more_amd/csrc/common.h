@@ -229,6 +229,42 @@ __device__ __forceinline__ float ln_bwd_dx(float rs, float gv, float c1, float x
   return __builtin_fmaf(rs, __builtin_fmaf(-xh, c2, t), res);
 }
 
+// The arithmetic of one LayerNorm forward element, one struct per spelling; the lane-split forward body (ln_split.h) takes one as a
+// parameter: mean<E>(row sum), sq (q += (x - mu)^2), rstd<E>(row sum of q, eps), norm (xhat * gamma + beta).  The spellings round
+// differently and stay apart on purpose -- folding one into the other changes results.  (The backward's exact spelling is
+// ln_bwd_acc / ln_bwd_dx above.)
+// LnExact: every FMA explicit, nothing contracted -- the ViT forward, whose bits the row-panel epilogue EPI_RES_LN (gemm_nt_kpipe.hip)
+// repeats in another lane layout.
+struct LnExact {
+  template <int E> static __device__ __forceinline__ float mean(float s) {
+#pragma clang fp contract(off)
+    return s * (1.f / E);
+  }
+  static __device__ __forceinline__ void sq(float x, float mu, float& q) {
+#pragma clang fp contract(off)
+    const float d = x - mu;
+    q = __builtin_fmaf(d, d, q);
+  }
+  template <int E> static __device__ __forceinline__ float rstd(float q, float eps) {
+#pragma clang fp contract(off)
+    return rsqrtf(__builtin_fmaf(q, 1.f / E, eps));
+  }
+  static __device__ __forceinline__ float norm(float x, float mu, float rs, float gm, float bt) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf((x - mu) * rs, gm, bt);
+  }
+};
+// LnDiv: the plain expressions with divisions by E, the compiler free to contract -- the SwinV2 LayerNorm.
+struct LnDiv {
+  template <int E> static __device__ __forceinline__ float mean(float s) { return s / E; }
+  static __device__ __forceinline__ void sq(float x, float mu, float& q) {
+    const float d = x - mu;
+    q += d * d;
+  }
+  template <int E> static __device__ __forceinline__ float rstd(float q, float eps) { return rsqrtf(q / E + eps); }
+  static __device__ __forceinline__ float norm(float x, float mu, float rs, float gm, float bt) { return (x - mu) * rs * gm + bt; }
+};
+
 // ---- lane exchanges inside a row of 16 lanes as DPP operand modifiers.  __shfl_xor compiles to ds_bpermute_b32 (an address
 // computation plus an LDS round trip of ~100 cycles); the row sums of the LayerNorm epilogues are chains of 3-4 of them per
 // row and made up most of those loops' time (mlp_bwd_kernel: 64 dependent exchanges, 9.3 k of its 26 k epilogue cycles).

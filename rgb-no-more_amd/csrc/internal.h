@@ -75,5 +75,9 @@ bool rgbnm_reduce_defer_active();                    // inside a bracket opened 
 void rgbnm_reduce_defer_begin();                     // queue the following submits ...
 int rgbnm_reduce_defer_flush(hipStream_t st);        // ... and run them as one launch
 int rgbnm_reduce_submit(const RgbnmReduceJob& job, hipStream_t st);
+// The two jobs (dgamma | dbeta) of a LayerNorm backward's partial sums part[nblk][2][E] (layernorm.hip).  own_bracket: when no defer
+// bracket is active, open one around the pair so that it runs as ONE reduction launch; false for callers inside a bracket of their own.
+int rgbnm_submit_ln_reduce(const float* part, float* dgamma, float* dbeta, int nblk, int E, int accumulate, bool own_bracket,
+                           hipStream_t st);
 int rgbnm_trace_begin(int tag, double flops, double bytes, hipStream_t st);
 void rgbnm_trace_end(int slot, hipStream_t st);

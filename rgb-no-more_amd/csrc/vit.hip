@@ -127,12 +127,7 @@ static bool fused_dx_lnbwd(int dt, const void* A, int lda, const void* Wt, int l
   const int rc = rgbnm_launch_nt_kpipe_lnbwd(dt, A, lda, Wt, ldw, x, E, gamma, mean, rstd, dres, E, dx, E, (float*)ws,
                                              &npanels, M, E, K, st);
   if (rc != RGBNM_OK) return false;
-  RgbnmReduceJob j;
-  j.part = (const float*)ws; j.stride = 2LL * E; j.out = dgamma; j.n = E; j.S = npanels; j.cols = 1; j.perm_heads = 0;
-  j.accumulate = 0; j.epw = 8;
-  if (rgbnm_reduce_submit(j, st) != RGBNM_OK) return false;
-  j.part = (const float*)ws + E; j.out = dbeta;
-  return rgbnm_reduce_submit(j, st) == RGBNM_OK;
+  return rgbnm_submit_ln_reduce((const float*)ws, dgamma, dbeta, npanels, E, 0, false, st) == RGBNM_OK;    // the caller's bracket
 }
 
 // du = (dy . W2) * gelu'(u), dx = dy + LayerNorm'(du . W1) in one launch (mlp_fused.hip) + two jobs for the batched reduction.
@@ -146,12 +141,7 @@ static bool fused_mlp_bwd(int dt, const void* dy, const void* w2t, const void* w
   const int rc = rgbnm_launch_mlp_bwd(dt, dy, E, w2t, w1t, gp, 4 * E, du, 4 * E, x, E, gamma, mean, rstd, dx, E, (float*)ws,
                                       &npanels, M, E, 4 * E, st);
   if (rc != RGBNM_OK) return false;
-  RgbnmReduceJob j;
-  j.part = (const float*)ws; j.stride = 2LL * E; j.out = dgamma; j.n = E; j.S = npanels; j.cols = 1; j.perm_heads = 0;
-  j.accumulate = 0; j.epw = 8;
-  if (rgbnm_reduce_submit(j, st) != RGBNM_OK) return false;
-  j.part = (const float*)ws + E; j.out = dbeta;
-  return rgbnm_reduce_submit(j, st) == RGBNM_OK;
+  return rgbnm_submit_ln_reduce((const float*)ws, dgamma, dbeta, npanels, E, 0, false, st) == RGBNM_OK;    // the caller's bracket
 }
 
 // workspace regions of one block backward: fc2 dW | fc1 dW | proj dW | qkv dW | LN2 | LN1 ; returns the total
@@ -392,16 +382,8 @@ int rgbnm_vit_blocks_bwd_dw_pe(const rgbnm_vit_cfg* c, int n, const rgbnm_block_
     if (pe_dx0) TRY(rgbnm_gemm_tn(dt, pe_dx0, E, pe_feat, 384, pe_dw, pe_db, M, E, 384, 0, 0, pe_ws, pe_ws_bytes, st));
     if (group) { tn_open = false; TRY(rgbnm_tn_defer_flush((hipStream_t)st)); }
     for (int i = 0; i < n; ++i) {       // per-image partial sums of the LayerNorm parameter gradients (one panel per image)
-      RgbnmReduceJob j;
-      j.stride = 2LL * E; j.n = E; j.S = c->B; j.cols = 1; j.perm_heads = 0; j.accumulate = 0; j.epw = 8;
-      j.part = part2[i]; j.out = g[i]->dln2_g;
-      TRY(rgbnm_reduce_submit(j, (hipStream_t)st));
-      j.part = part2[i] + E; j.out = g[i]->dln2_b;
-      TRY(rgbnm_reduce_submit(j, (hipStream_t)st));
-      j.part = part1[i]; j.out = g[i]->dln1_g;
-      TRY(rgbnm_reduce_submit(j, (hipStream_t)st));
-      j.part = part1[i] + E; j.out = g[i]->dln1_b;
-      TRY(rgbnm_reduce_submit(j, (hipStream_t)st));
+      TRY(rgbnm_submit_ln_reduce(part2[i], g[i]->dln2_g, g[i]->dln2_b, c->B, E, 0, false, (hipStream_t)st));
+      TRY(rgbnm_submit_ln_reduce(part1[i], g[i]->dln1_g, g[i]->dln1_b, c->B, E, 0, false, (hipStream_t)st));
     }
     return RGBNM_OK;
   }();
