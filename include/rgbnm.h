@@ -98,7 +98,10 @@ int rgbnm_abi_version(void);
  *   SwinV2
  *   "ln_rows"      1  lanes-per-row LayerNorm kernels for the four stage widths            "win_xcd"  1  XCD-aware window walk
  *   JPEG entropy decode
- *   "jpeg_lanes"   0  runs per wave of rgbnm_jpeg_decode_batch, 1..64 (0: chosen per launch so that about 2048 waves share the runs)
+ *   "jpeg_lanes"   0  runs per wave of rgbnm_jpeg_decode_batch, 1..64 (0: chosen per launch so that about 2048 waves share the runs);
+ *                     in rgbnm_jpeg_decode_batch_split also the segments per wave of its segment launches
+ *   "jpeg_min_seg" 0  rgbnm_jpeg_decode_batch_split splits runs of at least this many segments (0: 16; at least 2)
+ *   "jpeg_split_wgs" 0  cap on the workgroups of each of its launches (0: 4096; tests send the grid-stride loops round again)
  *   measurement
  *   "trace"        0  bit mask of kernel classes to bracket with HIP events, see rgbnm_trace_collect */
 int rgbnm_set_option(const char* name, int value);
@@ -494,6 +497,33 @@ typedef struct rgbnm_jpeg_device_plan {
  * returns 0 without a launch. */
 int rgbnm_jpeg_decode_batch(const rgbnm_jpeg_device_plan* plan, int n, int Hb, int Wb, int Hbc, int Wbc, int16_t* Y, int16_t* CbCr,
                             int32_t* status, void* stream);
+/* The same decode with long runs cut into bit segments of seg_bits, ONE LANE PER SEGMENT (csrc/jpeg_split.h): for files without
+ * restart markers, whose single run is one dependent chain for the call above.  Y, CbCr and status come out as from
+ * rgbnm_jpeg_decode_batch, bit for bit, for every input, damaged ones included.
+ * A run of at least 16 segments (option "jpeg_min_seg") is split: every segment is walked from a guessed state (scout), then `rounds`
+ * times every segment whose entry state differs from its predecessor's exit of the round before walks again from that exit
+ * (Huffman codes self-synchronise, so most segments agree after a few rounds; a run of at most rounds + 1 segments is CERTAIN to).
+ * A run passes if every entry equals the predecessor's exit, its nmcu * nblk blocks are complete with at most 8 bits left, and no
+ * walk met an impossible symbol on the way; then one lane per segment writes the blocks whose DC symbol starts in it.  Every image
+ * with a run that did not pass is decoded once more, whole, by the one-lane walk of the call above, which also takes the runs that
+ * were not split and alone lowers `status`: the worst case costs that call plus the passes.
+ *   path      int32 [n] on the device, written for every image: 0 no run split, 1 split and passed, 2 split, then the one-lane walk
+ *   scratch   device memory, 16-byte aligned, at least rgbnm_jpeg_split_scratch_bytes(plan->stream_bytes, plan->nruns, seg_bits)
+ *             bytes (about 76 per segment); nothing is kept in it between calls
+ *   seg_bits  128..65536, a multiple of 32 (2048 measured best with 16 rounds)         rounds  0..64 sync launches
+ * 6 + rounds launches whatever the data; no lane waits for another; no lane reads what the same launch writes, except path[] in the
+ * write pass (a lane whose walk fails raises it to 2 while others read it: harmless, the one-lane walk then rewrites that image);
+ * every record, trip count, stream read and store is bounded as in the call above.
+ * Precondition, met by every plan of rgbnm_jpeg_prepare: the runs lie in `stream` in record order without overlap (the segments'
+ * scratch slots follow from the offsets).  A plan that breaks it stays memory-safe; a run whose slots another run took fails verify
+ * and is decoded by the one-lane walk.  No allocation, no copy, no synchronisation: capturable.
+ * RGBNM_EINVAL with nothing launched: whatever the call above refuses, path NULL or misaligned, scratch NULL, misaligned or too
+ * small, seg_bits or rounds out of range.  nruns == 0: path is zeroed, nothing else.
+ * rgbnm_jpeg_split_scratch_bytes is host only (no HIP call) and gives 0 for nruns < 0 or seg_bits out of range. */
+size_t rgbnm_jpeg_split_scratch_bytes(size_t stream_bytes, int nruns, int seg_bits);
+int rgbnm_jpeg_decode_batch_split(const rgbnm_jpeg_device_plan* plan, int n, int Hb, int Wb, int Hbc, int Wbc, int16_t* Y, int16_t* CbCr,
+                                  int32_t* status, int32_t* path, void* scratch, size_t scratch_bytes, int seg_bits, int rounds,
+                                  void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Train-step tail

@@ -14,6 +14,7 @@
 #include "common.h"
 #include "jpeg_scan.h"
 #include "jpeg_walk.h"
+#include "jpeg_split.h"
 #include "../../include/rgbnm.h"
 
 namespace jpegdec {
@@ -31,6 +32,10 @@ struct Args {
   jpegwalk::Out g;
   int32_t* status;
   int lanes;                               // runs per wave, 1..64
+  // the split call's last launch (rgbnm_jpeg_decode_batch_split; NULL in the plain call): a split run whose image the segment
+  // lanes have written (path == 1) is left alone
+  const jpegsplit::RunInfo* info;
+  const int32_t* path;
 };
 
 __global__ __launch_bounds__(LANES) void decode_kernel(Args a) {
@@ -60,6 +65,8 @@ __global__ __launch_bounds__(LANES) void decode_kernel(Args a) {
       } else if (check_run(r, a.p.images, a.g.n, a.p.stream_bytes, a.p.ntables, &L) != 0) {
         live = false;
         if (r.image >= 0 && r.image < a.g.n) atomicMin(&a.status[r.image], RGBNM_JPEG_ERECORD);
+      } else if (a.info && a.info[ri].nseg && a.path[r.image] == 1) {
+        live = false;
       }
     }
     // one table set for the whole wave?
@@ -93,6 +100,186 @@ __global__ __launch_bounds__(LANES) void decode_kernel(Args a) {
   }
 }
 
+// ---- the split decode (jpeg_split.h): one lane per bit segment of a run -----------------------------------------------------------
+// Launches, in stream order: init, map, scout, `rounds` x sync, verify, write, then decode_kernel for what is left.  Their number
+// depends on the arguments only.  A lane reads its predecessor's exit from the buffer the launch BEFORE wrote, never from its own.
+// One exception, harmless: a write lane whose walk fails raises path[image] to 2 while other write lanes of the launch read it; whichever
+// value they see, the one-lane kernel behind them rewrites that whole image.
+struct SArgs {
+  rgbnm_jpeg_device_plan p;
+  jpegwalk::Out g;
+  int32_t* path;
+  jpegsplit::Scratch s;
+  int seg_bits, min_seg, cur, lanes;       // cur: the exit buffer to read (sync), the final one (verify)
+};
+
+__global__ __launch_bounds__(256) void split_init_kernel(SArgs a) {
+  const size_t m = a.s.nslots > (uint32_t)a.g.n ? a.s.nslots : (size_t)a.g.n;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (size_t)gridDim.x * blockDim.x) {
+    if (i < a.s.nslots) a.s.seg_run[i] = -1;
+    if (i < (size_t)a.g.n) a.path[i] = 0;
+  }
+}
+
+// one wave per run: is it split, where do its segments go
+__global__ __launch_bounds__(LANES) void split_map_kernel(SArgs a) {
+  using namespace jpegsplit;
+  const int lane = threadIdx.x;
+  for (int ri = blockIdx.x; ri < a.p.nruns; ri += gridDim.x) {
+    const rgbnm_jpeg_run r = a.p.runs[ri];
+    Lane L;
+    RunInfo info = {0u, 0u};
+    if (r.nmcu != 0 && jpegwalk::check_run(r, a.p.images, a.g.n, a.p.stream_bytes, a.p.ntables, &L) == 0)
+      info = map_run(r, ri, a.seg_bits, a.min_seg, a.s.nslots);
+    if (lane == 0) {
+      a.s.info[ri] = info;
+      if (info.nseg) atomicMax(&a.path[r.image], 1);
+    }
+    for (uint32_t j = lane; j < info.nseg; j += LANES) a.s.seg_run[info.base + j] = ri;
+  }
+}
+
+// MODE 0 scout, 1 sync, 2 write.  Workgroup = one wave; lanes = consecutive slots, so normally consecutive segments of one run, and
+// the tables are staged in LDS when every live lane of the wave uses the same six, as in decode_kernel.
+template <int MODE>
+__global__ __launch_bounds__(LANES) void split_seg_kernel(SArgs a) {
+  using namespace jpegsplit;
+  __shared__ alignas(16) uint8_t s_tile[MODE == 2 ? LANES * PITCH : 16];
+  __shared__ alignas(16) rgbnm_jpeg_hufftab s_tab[SLOTS];
+  __shared__ uint8_t s_zz[64];
+  const int lane = threadIdx.x;
+  int16_t* tile = reinterpret_cast<int16_t*>(s_tile + (MODE == 2 ? lane * PITCH : 0));
+  if (MODE == 2) {
+    s_zz[lane] = d_zigzag[lane];
+    V16* t = reinterpret_cast<V16*>(tile);
+    const V16 zero = {0, 0, 0, 0};
+    for (int j = 0; j < 8; ++j) t[j] = zero;
+  }
+  __syncthreads();
+  const uint32_t nslots = a.s.nslots;
+  const int per = a.lanes, nxt = a.cur ^ 1;
+  for (long long base = (long long)blockIdx.x * per; base < (long long)nslots; base += (long long)gridDim.x * per) {
+    const uint32_t slot = (uint32_t)base + (uint32_t)lane;
+    bool live = lane < per && slot < nslots;
+    int ri = -1;
+    uint32_t j = 0, nseg = 0;
+    rgbnm_jpeg_run r = {};
+    Lane L = {};
+    if (live) {
+      ri = a.s.seg_run[slot];
+      live = ri >= 0 && ri < a.p.nruns;
+    }
+    if (live) {
+      const RunInfo info = a.s.info[ri];
+      j = slot - info.base;                // unsigned: a slot in front of the run's fails the next test too
+      nseg = info.nseg;
+      live = j < nseg;
+    }
+    if (live) {
+      r = a.p.runs[ri];
+      live = r.nmcu != 0 && jpegwalk::check_run(r, a.p.images, a.g.n, a.p.stream_bytes, a.p.ntables, &L) == 0;
+    }
+    uint64_t state = 0;
+    if (MODE == 0 && live) state = j == 0 ? pack_state(0, 0, 0) : seg_first_state(j, a.seg_bits);
+    if (MODE == 1 && live) {               // walk again only where the entry is not the predecessor's exit of the round before
+      const uint64_t mine = a.s.exits[a.cur][slot];
+      const uint64_t pe = j ? a.s.exits[a.cur][slot - 1] : 0;
+      if (j == 0 || a.s.entry[slot] == pe) {
+        a.s.exits[nxt][slot] = mine;
+        live = false;
+      }
+      state = pe;
+    }
+    if (MODE == 2 && live) {
+      live = a.path[r.image] == 1;
+      state = a.s.entry[slot];
+    }
+    const unsigned long long mask = __ballot(live);
+    if (mask == 0) continue;
+    const int first = __ffsll((long long)mask) - 1;
+    const uint64_t dc0 = __shfl((unsigned long long)L.dcsel, first, LANES), ac0 = __shfl((unsigned long long)L.acsel, first, LANES);
+    const bool shared = __all(!live || (L.dcsel == dc0 && L.acsel == ac0));
+    const rgbnm_jpeg_hufftab* tabs = a.p.tables;
+    Lane S = L;
+    if (shared) {
+      __syncthreads();                     // the previous round's readers of s_tab are done
+      for (int q = lane; q < SLOTS * TAB_PIECES; q += LANES) {
+        const int slot_t = q / TAB_PIECES, piece = q - slot_t * TAB_PIECES;
+        const uint32_t t = (uint32_t)(((slot_t & 1) ? ac0 : dc0) >> (16 * (slot_t >> 1))) & 0xFFFFu;   // < ntables: check_run
+        reinterpret_cast<V16*>(&s_tab[slot_t])[piece] = reinterpret_cast<const V16*>(&a.p.tables[t])[piece];
+      }
+      __syncthreads();
+      S.dcsel = 0ull | (2ull << 16) | (4ull << 32);
+      S.acsel = 1ull | (3ull << 16) | (5ull << 32);
+      tabs = s_tab;
+    }
+    if (!live) continue;
+    const uint32_t end = seg_end(r, j, a.seg_bits);
+    if (MODE == 2) {
+      const SegScan sc = a.s.scan[slot];
+      if (write_walk(a.p.stream, r, S, tabs, s_zz, a.g, tile, state, end, (uint32_t)a.seg_bits + 64u, sc) != 0) atomicMax(&a.path[r.image], 2);
+      if (L.ncomp == 1) zero_chroma_part(a.g, r.image, (uint32_t)r.mcu0, (uint32_t)r.nmcu, L.total, j, nseg);
+    } else {
+      SegRec rec;
+      const uint64_t out = scout_walk(a.p.stream, r, S, tabs, state, end, (uint32_t)a.seg_bits + 1u, &rec);
+      a.s.entry[slot] = state;
+      a.s.exits[MODE == 0 ? 0 : nxt][slot] = out;
+      a.s.rec[slot] = rec;
+    }
+  }
+}
+
+// one wave per split run: converged? complete? and the exclusive scan over its segments (block index and DC predictors at each entry)
+__global__ __launch_bounds__(LANES) void split_verify_kernel(SArgs a) {
+  using namespace jpegsplit;
+  const int lane = threadIdx.x;
+  const uint64_t* fin = a.s.exits[a.cur];
+  for (int ri = blockIdx.x; ri < a.p.nruns; ri += gridDim.x) {
+    const RunInfo info = a.s.info[ri];
+    if (info.nseg == 0) continue;
+    const rgbnm_jpeg_run r = a.p.runs[ri];
+    Lane L;
+    if (jpegwalk::check_run(r, a.p.images, a.g.n, a.p.stream_bytes, a.p.ntables, &L) != 0) continue;   // map split it: it passed there
+    const uint64_t N = (uint64_t)r.nmcu * (uint64_t)L.nblk;
+    const uint32_t total_bits = r.nbytes * 8u;
+    uint32_t carry[5] = {0, 0, 0, 0, 0};   // blocks completed, blocks started, DC sums
+    bool bad = false, found = false;
+    for (uint32_t c0 = 0; c0 < info.nseg; c0 += LANES) {
+      const uint32_t j = c0 + (uint32_t)lane, slot = info.base + j;
+      const bool v = j < info.nseg;
+      SegRec c = {};
+      bool conv = true;
+      if (v) {
+        c = a.s.rec[slot];
+        // the slot is this run's (two runs that overlap in the stream would share slots: then the records are not this run's)
+        conv = a.s.seg_run[slot] == ri && a.s.entry[slot] == (j ? fin[slot - 1] : pack_state(0, 0, 0));
+      }
+      const uint32_t own[5] = {c.ndone, c.nstart, c.dc[0], c.dc[1], c.dc[2]};
+      uint32_t incl[5];
+      for (int q = 0; q < 5; ++q) {
+        uint32_t x = own[q];
+        for (int d = 1; d < LANES; d <<= 1) {
+          const uint32_t y = __shfl_up(x, d, LANES);
+          if (lane >= d) x += y;
+        }
+        incl[q] = x;
+      }
+      int verdict = 0;
+      if (v) {
+        verdict = seg_verdict(c, (uint64_t)carry[0] + incl[0] - own[0], N, total_bits);
+        SegScan sc;
+        sc.b0 = carry[1] + incl[1] - own[1];
+        for (int q = 0; q < 3; ++q) sc.p[q] = carry[2 + q] + incl[2 + q] - own[2 + q];
+        a.s.scan[slot] = sc;
+      }
+      bad = bad || __any(!conv || verdict == 1);
+      found = found || __any(verdict == 2);
+      for (int q = 0; q < 5; ++q) carry[q] += __shfl(incl[q], LANES - 1, LANES);
+    }
+    if (lane == 0 && (bad || !found)) atomicMax(&a.path[r.image], 2);
+  }
+}
+
 }  // namespace jpegdec
 
 extern "C" {
@@ -116,6 +303,8 @@ int rgbnm_jpeg_decode_batch(const rgbnm_jpeg_device_plan* plan, int n, int Hb, i
   a.p = *plan;
   a.g.n = n; a.g.Hb = Hb; a.g.Wb = Wb; a.g.Hbc = Hbc; a.g.Wbc = Wbc; a.g.Y = Y; a.g.C = CbCr;
   a.status = status;
+  a.info = nullptr;
+  a.path = nullptr;
   // Runs per wave.  What is rare for a lane -- a code longer than 9 bits, a refill, the end of a block -- happens in almost every
   // trip of a wave whose 64 lanes all walk, and the wave pays for each.  A batch rarely has runs for every SIMD of the device
   // (256 without restart markers, 8192 with one per MCU row), so the runs are spread over about 2048 waves first and the waves fill
@@ -126,6 +315,78 @@ int rgbnm_jpeg_decode_batch(const rgbnm_jpeg_device_plan* plan, int n, int Hb, i
   a.lanes = per;
   const int groups = cdiv(plan->nruns, per);
   decode_kernel<<<groups < MAX_WGS ? groups : MAX_WGS, LANES, 0, (hipStream_t)stream>>>(a);
+  LAUNCH_CHECK();
+  return RGBNM_OK;
+}
+
+size_t rgbnm_jpeg_split_scratch_bytes(size_t stream_bytes, int nruns, int seg_bits) {
+  return jpegsplit::scratch_bytes(stream_bytes, nruns, seg_bits);
+}
+
+int rgbnm_jpeg_decode_batch_split(const rgbnm_jpeg_device_plan* plan, int n, int Hb, int Wb, int Hbc, int Wbc, int16_t* Y, int16_t* CbCr,
+                                  int32_t* status, int32_t* path, void* scratch, size_t scratch_bytes, int seg_bits, int rounds,
+                                  void* stream) {
+  using namespace jpegdec;
+  if (!plan || !Y || !CbCr || !status || !path || n <= 0 || Hb < 1 || Wb < 1 || Hbc < 1 || Wbc < 1 || Hb > 4096 || Wb > 4096 ||
+      Hbc > 4096 || Wbc > 4096 || plan->nruns < 0 || plan->ntables < 0)
+    return RGBNM_EINVAL;
+  if (((uintptr_t)Y & 15) || ((uintptr_t)CbCr & 15) || ((uintptr_t)status & 3) || ((uintptr_t)path & 3)) return RGBNM_EINVAL;
+  if (rounds < 0 || rounds > jpegsplit::ROUNDS_MAX) return RGBNM_EINVAL;
+  const size_t need = jpegsplit::scratch_bytes(plan->stream_bytes, plan->nruns, seg_bits);   // 0: seg_bits out of range
+  if (need == 0 || !scratch || ((uintptr_t)scratch & 15) || scratch_bytes < need) return RGBNM_EINVAL;
+  if (plan->nruns &&
+      (!plan->stream || !plan->runs || !plan->images || !plan->tables || ((uintptr_t)plan->stream & 3) || ((uintptr_t)plan->tables & 15) ||
+       ((uintptr_t)plan->runs & 3) || ((uintptr_t)plan->images & 3)))
+    return RGBNM_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  SArgs s;
+  s.p = *plan;
+  s.g.n = n; s.g.Hb = Hb; s.g.Wb = Wb; s.g.Hbc = Hbc; s.g.Wbc = Wbc; s.g.Y = Y; s.g.C = CbCr;
+  s.path = path;
+  s.s = jpegsplit::carve(scratch, plan->stream_bytes, plan->nruns, seg_bits);
+  s.seg_bits = seg_bits;
+  const int ms = rgbnm_get_option("jpeg_min_seg");
+  s.min_seg = ms >= 2 ? ms : jpegsplit::MIN_SEG;
+  s.cur = 0;
+  // Option "jpeg_split_wgs" caps the workgroups of every launch below (tests: each grid-stride loop goes round again).
+  const int cap_opt = rgbnm_get_option("jpeg_split_wgs");
+  const int cap = cap_opt >= 1 && cap_opt < MAX_WGS ? cap_opt : MAX_WGS;
+  auto grid = [cap](long long groups) { return (unsigned)(groups < 1 ? 1 : groups < cap ? groups : cap); };
+  const long long nslots = s.s.nslots;
+  split_init_kernel<<<grid(cdivl(nslots > n ? nslots : n, 256)), 256, 0, st>>>(s);
+  LAUNCH_CHECK();
+  if (plan->nruns == 0) return RGBNM_OK;
+  // Segments per wave: as for the runs of the plain launch, about 2048 waves first ("jpeg_lanes" fixes the number).
+  const int opt = rgbnm_get_option("jpeg_lanes");
+  int per = opt >= 1 && opt <= LANES ? opt : (int)cdivl(nslots, 2048);
+  per = per < 1 ? 1 : per > LANES ? LANES : per;
+  s.lanes = per;
+  const unsigned seg_grid = grid(cdivl(nslots, per)), run_grid = grid(plan->nruns);
+  split_map_kernel<<<run_grid, LANES, 0, st>>>(s);
+  LAUNCH_CHECK();
+  split_seg_kernel<0><<<seg_grid, LANES, 0, st>>>(s);
+  LAUNCH_CHECK();
+  for (int j = 0; j < rounds; ++j) {
+    s.cur = j & 1;
+    split_seg_kernel<1><<<seg_grid, LANES, 0, st>>>(s);
+    LAUNCH_CHECK();
+  }
+  s.cur = rounds & 1;
+  split_verify_kernel<<<run_grid, LANES, 0, st>>>(s);
+  LAUNCH_CHECK();
+  split_seg_kernel<2><<<seg_grid, LANES, 0, st>>>(s);
+  LAUNCH_CHECK();
+  // what is left: the runs that were not split, and every run of an image whose split did not pass (path 2)
+  Args a;
+  a.p = *plan;
+  a.g = s.g;
+  a.status = status;
+  a.info = s.s.info;
+  a.path = path;
+  int rper = opt >= 1 && opt <= LANES ? opt : cdiv(plan->nruns, 2048);
+  rper = rper < 1 ? 1 : rper > LANES ? LANES : rper;
+  a.lanes = rper;
+  decode_kernel<<<grid(cdiv(plan->nruns, rper)), LANES, 0, st>>>(a);
   LAUNCH_CHECK();
   return RGBNM_OK;
 }

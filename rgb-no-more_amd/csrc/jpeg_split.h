@@ -1,0 +1,322 @@
+// The split decode of the device JPEG path (include/rgbnm.h, rgbnm_jpeg_decode_batch_split): a run is cut into bit segments of
+// seg_bits, ONE LANE PER SEGMENT, and the lanes find the true parse by the self-synchronisation of Huffman codes (Klein & Wiseman;
+// Weissenberger & Schmidt).  Like jpeg_walk.h this is __host__ __device__ text over plain pointers: jpeg_decode.hip runs it per lane,
+// tools/jpeg_split_check.cpp runs the same text on the CPU under the host sanitizers, lane after lane, pass by pass.
+//
+// The passes (each a launch; a lane touches its own segment's records only and reads its predecessor's from the launch before;
+// the one word a launch both reads and writes is path[image] in the write pass, raised to 2 by a lane whose walk failed -- harmless,
+// the one-lane walk behind it rewrites that image whatever the other lanes saw):
+//   map     per run: number of segments, first slot, split or not.  Slot of segment j of run i: floor(offset * 8 / seg_bits) + i + j;
+//           the runs lie in the stream in record order without overlap, so the slot ranges do not overlap either (a run's segments
+//           number at most floor(distance to the next run * 8 / seg_bits) + 1) and no scan is needed to place them.  That order is
+//           rgbnm_jpeg_prepare's and a precondition of the call; runs that break it stay memory-safe (every lane re-checks its slot,
+//           run and image) and verify fails a run one of whose slots another run took, so it goes to the one-lane walk.
+//   scout   segment 0 starts in the true state (bit 0, k = 0, blk = 0), every other at its first bit with (k = 0, blk = 0).  The lane
+//           walks symbols until it is at or past the segment's end and records the exit state and what it met (SegRec).
+//   sync    `rounds` times: a segment whose entry differs from its predecessor's exit OF THE ROUND BEFORE (the exits are double
+//           buffered, so a round is a Jacobi step whatever the order of the lanes) walks again from that exit.  After round j the
+//           segments 0..j are true, so a run of at most rounds + 1 segments is certain to converge.
+//   verify  per run: converged (every entry equals the predecessor's exit); the block that completes as number nmcu * nblk is the
+//           last to complete in its segment, at a position that leaves at most 8 bits; no walk met an impossible symbol up to there.
+//           An exclusive scan gives each segment the index of the first block that starts in it and the DC predictors there.
+//   write   per segment of a run that passed: skip the block under way at the entry, decode every block whose DC symbol starts
+//           before the segment's end -- on past the end until the last of them is complete -- and store through flush_block.
+// Every image with a run that did not pass is decoded by the one-lane walk afterwards, as are the runs that were not split.
+//
+// Safety (the bytes are untrusted): a walk that meets an impossible symbol carries on -- it skips one bit of an unassigned code,
+// clamps a coefficient index past 63, ignores the run nibble of a DC symbol -- and notes it, because a walk from a guessed state
+// meets such symbols in well-formed streams and would otherwise never fall into step.  Every trip consumes at least one bit; trips
+// are bounded by seg_bits + 1 (scout, sync) or seg_bits + 64 (write); reads of the stream are clamped to the run's words; stores go
+// through flush_block's range check.  The write walk stops at the first impossible symbol and reports it (that cannot happen after
+// verify; the image then goes to the one-lane walk like any that failed).  Nothing waits for another lane.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "jpeg_walk.h"
+
+namespace jpegsplit {
+
+using jpegwalk::Lane;
+using jpegwalk::Out;
+using jpegwalk::V16;
+
+constexpr int SEG_BITS_MIN = 128, SEG_BITS_MAX = 65536;    // a multiple of 32 in this range
+constexpr int ROUNDS_MAX = 64;
+constexpr int MIN_SEG = 16;                                // runs of fewer segments are not split (option "jpeg_min_seg")
+constexpr uint32_t ERR_ANY = 1u, ERR_DONE = 2u;            // SegRec.err: an impossible symbol anywhere / up to the last completed block
+
+// a parse state in one word, so that it is loaded, stored and compared whole: bit position in the run | k << 32 | blk << 40
+__host__ __device__ inline uint64_t pack_state(uint32_t pos, int k, int blk) { return (uint64_t)pos | ((uint64_t)k << 32) | ((uint64_t)blk << 40); }
+__host__ __device__ inline uint32_t state_pos(uint64_t s) { return (uint32_t)s; }
+__host__ __device__ inline int state_k(uint64_t s) { return (int)(s >> 32) & 63; }
+__host__ __device__ inline int state_blk(uint64_t s) { return (int)(s >> 40) & 15; }
+
+struct RunInfo { uint32_t base, nseg; };                   // first slot; segments, 0: the run is not split
+// what a scout / sync walk met: DC symbols decoded (= blocks that start in the segment), blocks completed, the position behind the
+// last completed block, the sums of the DC differences per component (wrapping, like the int sums of decode_run)
+struct SegRec { uint32_t nstart, ndone, done_pos, err, dc[3], _pad; };   // 32 bytes
+struct SegScan { uint32_t b0, p[3]; };                     // first block that starts in the segment; predictors at its entry
+
+struct Scratch {
+  RunInfo* info;        // [nruns]
+  int32_t* seg_run;     // [nslots]: run of the slot, -1: none
+  uint64_t* entry;      // [nslots]
+  uint64_t* exits[2];   // [nslots] each: the exits of the round before / of this round
+  SegRec* rec;          // [nslots]
+  SegScan* scan;        // [nslots]
+  uint32_t nslots;
+};
+
+inline size_t slot_count(size_t stream_bytes, int nruns, int seg_bits) { return stream_bytes * 8 / (size_t)seg_bits + (size_t)nruns + 1; }
+inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+// 0: arguments out of range (or more slots than 32 bits index)
+inline size_t scratch_bytes(size_t stream_bytes, int nruns, int seg_bits) {
+  if (nruns < 0 || seg_bits < SEG_BITS_MIN || seg_bits > SEG_BITS_MAX || (seg_bits & 31) || stream_bytes > ((size_t)1 << 40)) return 0;
+  const size_t S = slot_count(stream_bytes, nruns, seg_bits);
+  if (S > 0x7FFFFFFFu) return 0;
+  return align16((size_t)nruns * sizeof(RunInfo)) + align16(S * 4) + 3 * align16(S * 8) + S * sizeof(SegRec) + S * sizeof(SegScan);
+}
+inline Scratch carve(void* mem, size_t stream_bytes, int nruns, int seg_bits) {
+  const size_t S = slot_count(stream_bytes, nruns, seg_bits);
+  uint8_t* p = static_cast<uint8_t*>(mem);
+  Scratch s;
+  s.info = reinterpret_cast<RunInfo*>(p); p += align16((size_t)nruns * sizeof(RunInfo));
+  s.seg_run = reinterpret_cast<int32_t*>(p); p += align16(S * 4);
+  s.entry = reinterpret_cast<uint64_t*>(p); p += align16(S * 8);
+  s.exits[0] = reinterpret_cast<uint64_t*>(p); p += align16(S * 8);
+  s.exits[1] = reinterpret_cast<uint64_t*>(p); p += align16(S * 8);
+  s.rec = reinterpret_cast<SegRec*>(p); p += S * sizeof(SegRec);
+  s.scan = reinterpret_cast<SegScan*>(p);
+  s.nslots = (uint32_t)S;
+  return s;
+}
+
+// map: segments and first slot of run `ri` (its record has passed check_run).  nseg = 0: not split.
+__host__ __device__ inline RunInfo map_run(const rgbnm_jpeg_run& r, int ri, int seg_bits, int min_seg, uint32_t nslots) {
+  const uint64_t bits = (uint64_t)r.nbytes * 8u, sb = (uint64_t)seg_bits;
+  const uint64_t nseg = (bits + sb - 1) / sb, base = (uint64_t)r.offset * 8u / sb + (uint64_t)ri;
+  RunInfo i = {(uint32_t)(base < nslots ? base : 0), 0u};
+  if (nseg >= (uint64_t)(min_seg < 2 ? 2 : min_seg) && base + nseg <= (uint64_t)nslots) i.nseg = (uint32_t)nseg;
+  return i;
+}
+
+// ---- the bit reader: decode_run's, opened at any bit of the run ---------------------------------------------------------------------
+struct Bits {
+  const uint32_t* words;
+  uint32_t nwords, next;   // next: index of the word behind nextw
+  uint32_t nextw;
+  uint64_t buf;
+  int have;
+};
+
+__host__ __device__ inline void bits_open(Bits& B, const uint8_t* stream, const rgbnm_jpeg_run& r, uint32_t pos) {
+  B.words = reinterpret_cast<const uint32_t*>(stream + r.offset);
+  B.nwords = (r.nbytes + 3u) >> 2;
+  const uint32_t w = pos >> 5, off = pos & 31u;
+  const uint32_t first = w < B.nwords ? B.words[w] : 0u;
+  B.buf = ((uint64_t)__builtin_bswap32(first) << 32) << off;
+  B.have = 32 - (int)off;
+  B.nextw = w + 1 < B.nwords ? B.words[w + 1] : 0u;
+  B.next = w + 2;
+}
+
+struct Sym { int len, s, rr, val; bool bad; };             // len: bits consumed in all (code and value)
+
+// The next symbol behind table T, exactly as decode_run reads it.  bad: no code of the table matches; ONE bit is consumed then.
+__host__ __device__ inline Sym next_symbol(Bits& B, const rgbnm_jpeg_hufftab* T) {
+  if (B.have <= 32) {
+    B.buf |= (uint64_t)__builtin_bswap32(B.nextw) << (32 - B.have);
+    B.have += 32;
+    B.nextw = B.next < B.nwords ? B.words[B.next] : 0u;
+    ++B.next;
+  }
+  const uint32_t e = T->look[B.buf >> 55];
+  int len = (int)(e >> 8), sym = (int)(e & 255u);
+  bool bad = false;
+  if (len == 0) {
+    int idx = -1;
+    for (int l = 10; l <= 16; ++l) {
+      const int code = (int)(B.buf >> (64 - l));
+      if (len == 0 && code <= T->maxcode[l]) {
+        len = l;
+        idx = code + T->valoff[l];
+      }
+    }
+    if (idx < 0 || idx > 255) {
+      bad = true;
+      len = 1;
+      sym = 0;
+    } else {
+      sym = T->vals[idx];
+    }
+  }
+  Sym o;
+  o.s = sym & 15;
+  o.rr = sym >> 4;
+  B.buf <<= len;
+  const uint32_t bits = (uint32_t)((B.buf >> 32) >> (32 - o.s));
+  B.buf <<= o.s;
+  B.have -= len + o.s;
+  o.len = len + o.s;
+  o.val = (o.s && bits < (1u << (o.s - 1))) ? (int)bits - (1 << o.s) + 1 : (int)bits;
+  o.bad = bad;
+  return o;
+}
+
+__host__ __device__ inline const rgbnm_jpeg_hufftab* table_of(const Lane& L, const rgbnm_jpeg_hufftab* tabs, int comp, bool isdc) {
+  return tabs + ((uint32_t)((isdc ? L.dcsel : L.acsel) >> (16 * comp)) & 0xFFFFu);
+}
+
+// scout / sync: walk from `state` until at or past `end` (a bit position of the run, <= its bit count); stores nothing.  Returns the
+// exit state and fills *rec.
+__host__ __device__ inline uint64_t scout_walk(const uint8_t* stream, const rgbnm_jpeg_run& r, const Lane& L, const rgbnm_jpeg_hufftab* tabs,
+                                               uint64_t state, uint32_t end, uint32_t maxtrips, SegRec* rec) {
+  uint32_t pos = state_pos(state);
+  int k = state_k(state), blk = state_blk(state);
+  if (blk >= L.nblk) blk = 0;                              // a state word is only ever made here; this keeps the shifts in range anyway
+  Bits B;
+  bits_open(B, stream, r, pos);
+  uint32_t nstart = 0, ndone = 0, done_pos = pos, err = 0, err_done = 0, d0 = 0, d1 = 0, d2 = 0;
+  for (uint32_t trip = 0; trip < maxtrips && pos < end; ++trip) {
+    const int comp = (int)(L.layout >> (6 * blk)) & 3;
+    const bool isdc = k == 0;
+    const Sym y = next_symbol(B, table_of(L, tabs, comp, isdc));
+    pos += (uint32_t)y.len;
+    if (y.bad) {                                           // one bit skipped, the state stays
+      err = 1;
+      continue;
+    }
+    int rr = y.rr;
+    if (isdc && rr) {
+      err = 1;
+      rr = 0;
+    }
+    nstart += isdc ? 1u : 0u;
+    d0 += (isdc && comp == 0) ? (uint32_t)y.val : 0u;
+    d1 += (isdc && comp == 1) ? (uint32_t)y.val : 0u;
+    d2 += (isdc && comp == 2) ? (uint32_t)y.val : 0u;
+    const bool wr = isdc || y.s != 0;
+    int kk = isdc ? 0 : k + rr;
+    if (wr && kk > 63) {
+      err = 1;
+      kk = 63;
+    }
+    k = wr ? kk + 1 : (rr == 15 ? k + 16 : 64);
+    if (k >= 64) {
+      k = 0;
+      blk = blk + 1 == L.nblk ? 0 : blk + 1;
+      ++ndone;
+      done_pos = pos;
+      err_done = err;
+    }
+  }
+  if (pos > r.nbytes * 8u) err = 1;
+  rec->nstart = nstart;
+  rec->ndone = ndone;
+  rec->done_pos = done_pos;
+  rec->err = (err ? ERR_ANY : 0u) | (err_done ? ERR_DONE : 0u);
+  rec->dc[0] = d0;
+  rec->dc[1] = d1;
+  rec->dc[2] = d2;
+  rec->_pad = 0;
+  return pack_state(pos, k, blk);
+}
+
+__host__ __device__ inline uint32_t seg_end(const rgbnm_jpeg_run& r, uint32_t j, int seg_bits) {
+  const uint64_t e = ((uint64_t)j + 1) * (uint64_t)seg_bits, total = (uint64_t)r.nbytes * 8u;
+  return (uint32_t)(e < total ? e : total);
+}
+__host__ __device__ inline uint64_t seg_first_state(uint32_t j, int seg_bits) { return pack_state(j * (uint32_t)seg_bits, 0, 0); }
+
+// verify, the part per segment.  done_before: blocks completed in the run's segments before this one; N = nmcu * nblk.
+// 0: before the run's last block, nothing wrong; 1: wrong (the run fails); 2: the last block completes here and all is well;
+// 3: behind the last block (only padding bits: ignored).
+__host__ __device__ inline int seg_verdict(const SegRec& c, uint64_t done_before, uint64_t N, uint32_t total_bits) {
+  if (done_before >= N) return 3;
+  const uint64_t incl = done_before + c.ndone;
+  if (incl < N) return (c.err & ERR_ANY) ? 1 : 0;
+  if (incl > N || (c.err & ERR_DONE) || c.done_pos > total_bits || total_bits - c.done_pos > 8u) return 1;
+  return 2;
+}
+
+// write: segment j's share of the blocks.  tile: as for decode_run, zero on entry and on return.  Returns 0, or -1 when the walk met
+// what verify should have excluded (the caller sends the image to the one-lane walk).
+__host__ __device__ inline int write_walk(const uint8_t* stream, const rgbnm_jpeg_run& r, const Lane& L, const rgbnm_jpeg_hufftab* tabs,
+                                          const uint8_t* zz, const Out& g, int16_t* tile, uint64_t state, uint32_t end, uint32_t maxtrips,
+                                          const SegScan& sc) {
+  const uint32_t total_bits = r.nbytes * 8u, N = (uint32_t)r.nmcu * (uint32_t)L.nblk;
+  uint32_t pos = state_pos(state), b = sc.b0;
+  int k = state_k(state), blk = state_blk(state);
+  if (blk >= L.nblk) return -1;
+  bool skipping = k != 0;                                  // the block under way at the entry belongs to the segment it started in
+  uint32_t p0 = sc.p[0], p1 = sc.p[1], p2 = sc.p[2];
+  uint32_t mcu = (uint32_t)r.mcu0 + b / (uint32_t)L.nblk;
+  int bi = (int)(b % (uint32_t)L.nblk), mx = (int)(mcu % (uint32_t)L.mcus_x), my = (int)(mcu / (uint32_t)L.mcus_x);
+  Bits B;
+  bits_open(B, stream, r, pos);
+  bool fail = false;
+  for (uint32_t trip = 0; trip < maxtrips; ++trip) {
+    const bool isdc = k == 0;
+    if ((isdc || skipping) && (pos >= end || b >= N)) break;   // nothing more starts here, or only padding bits are left
+    if (isdc && bi != blk) {
+      fail = true;
+      break;
+    }
+    const int comp = (int)(L.layout >> (6 * blk)) & 3;
+    const Sym y = next_symbol(B, table_of(L, tabs, comp, isdc));
+    pos += (uint32_t)y.len;
+    if (y.bad || (isdc && y.rr) || pos > total_bits) {
+      fail = true;
+      break;
+    }
+    p0 += (isdc && comp == 0) ? (uint32_t)y.val : 0u;
+    p1 += (isdc && comp == 1) ? (uint32_t)y.val : 0u;
+    p2 += (isdc && comp == 2) ? (uint32_t)y.val : 0u;
+    const uint32_t dc = comp == 0 ? p0 : comp == 1 ? p1 : p2;
+    const bool wr = isdc || y.s != 0;
+    const int kk = isdc ? 0 : k + y.rr;
+    if (wr && kk > 63) {
+      fail = true;
+      break;
+    }
+    if (wr && !skipping) tile[zz[kk]] = (int16_t)(isdc ? (int32_t)dc : y.val);
+    k = wr ? kk + 1 : (y.rr == 15 ? k + 16 : 64);
+    if (k >= 64) {
+      k = 0;
+      if (!skipping) {
+        jpegwalk::flush_block(tile, g, L, r.image, blk, mx, my);
+        ++b;
+        if (++bi == L.nblk) {
+          bi = 0;
+          if (++mx == L.mcus_x) {
+            mx = 0;
+            ++my;
+          }
+        }
+      }
+      skipping = false;
+      blk = blk + 1 == L.nblk ? 0 : blk + 1;
+    }
+  }
+  if (fail || (k != 0 && !skipping)) {                     // a block half written: the tile goes back to zero
+    V16* t = reinterpret_cast<V16*>(tile);
+    const V16 zero = {0, 0, 0, 0};
+    for (int j = 0; j < 8; ++j) t[j] = zero;
+    return -1;
+  }
+  return 0;
+}
+
+// A one-component file's zero chroma: segment j of nseg takes its part of the run's share (jpegwalk::zero_chroma_share).
+__host__ __device__ inline void zero_chroma_part(const Out& g, int image, uint32_t mcu0, uint32_t nmcu, uint32_t total, uint32_t j, uint32_t nseg) {
+  if (!g.C) return;
+  const uint64_t pieces = (uint64_t)2 * (uint64_t)g.Hbc * (uint64_t)g.Wbc * 8u;
+  const uint64_t lo = pieces * mcu0 / total, hi = pieces * ((uint64_t)mcu0 + nmcu) / total;
+  const uint64_t a = lo + (hi - lo) * j / nseg, b = lo + (hi - lo) * ((uint64_t)j + 1) / nseg;
+  V16* dst = reinterpret_cast<V16*>(g.C + (size_t)image * 2 * (size_t)g.Hbc * (size_t)g.Wbc * 64);
+  const V16 zero = {0, 0, 0, 0};
+  for (uint64_t q = a; q < b; ++q) dst[q] = zero;
+}
+
+}  // namespace jpegsplit

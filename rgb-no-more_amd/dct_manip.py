@@ -316,9 +316,27 @@ def upload_jpeg_plan(plan, device):
     return tuple(t.to(device, non_blocking=True) for t in plan.buffers())
 
 
-def launch_jpeg_decode(plan, dev, out):
-    """The decode launch alone (no copy, no allocation, no sync: capturable).  dev: upload_jpeg_plan's tensors; out: (Y, CbCr, quant,
-    status) device tensors (alloc_jpeg_out); quant and status must already hold the plan's (decode_jpeg_batch copies them)."""
+# The split decode's defaults (csrc/jpeg_split.h; DESIGN.md 7 has the sweep behind them)
+JPEG_SPLIT_SEG_BITS = 2048
+JPEG_SPLIT_ROUNDS = 16
+
+
+def jpeg_split_scratch(plan, seg_bits=None, device="cuda"):
+    """uint8 device tensor for launch_jpeg_decode(split=True, scratch=...) on this plan (or any with no more stream bytes and runs)."""
+    from . import lib as L
+    nbytes = L.lib().rgbnm_jpeg_split_scratch_bytes(plan.stream_bytes, plan.nruns, JPEG_SPLIT_SEG_BITS if seg_bits is None else int(seg_bits))
+    if nbytes == 0:
+        raise L.RgbnmError("seg_bits must be a multiple of 32 in 128..65536")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def launch_jpeg_decode(plan, dev, out, split=False, seg_bits=None, rounds=None, path=None, scratch=None):
+    """The decode launch alone (no copy, no sync: capturable).  dev: upload_jpeg_plan's tensors; out: (Y, CbCr, quant,
+    status) device tensors (alloc_jpeg_out); quant and status must already hold the plan's (decode_jpeg_batch copies them).
+    split=True: rgbnm_jpeg_decode_batch_split instead -- long runs cut into segments of seg_bits bits, one lane each, `rounds` sync
+    launches (defaults JPEG_SPLIT_SEG_BITS / JPEG_SPLIT_ROUNDS); the same bits in `out`.  path: int32 [n] device tensor that receives
+    0 (no run split) / 1 (split) / 2 (split, then decoded by the one-lane walk) per file, scratch: jpeg_split_scratch's tensor; each
+    is taken from the caching allocator when None.  Returns path (None without split)."""
     from . import lib as L
     Y, CbCr, _, status = out
     hb, wb = plan.grid
@@ -329,16 +347,39 @@ def launch_jpeg_decode(plan, dev, out):
         raise L.RgbnmError("out tensors do not match the plan (alloc_jpeg_out)")
     dp = L.JpegDevicePlan(stream=dev[0].data_ptr(), stream_bytes=plan.stream_bytes, runs=dev[1].data_ptr(), images=dev[2].data_ptr(),
                           tables=dev[3].data_ptr(), nruns=plan.nruns, ntables=plan.ntables)
+    if not split:
+        if seg_bits is not None or rounds is not None or path is not None or scratch is not None:
+            raise ValueError("seg_bits, rounds, path and scratch belong to split=True")
+        with torch.cuda.device(Y.device):
+            L.check(L.lib().rgbnm_jpeg_decode_batch(C.byref(dp), n, hb, wb, (hb + 1) // 2, (wb + 1) // 2, Y.data_ptr(), CbCr.data_ptr(),
+                                                    status.data_ptr(), L.stream()), "jpeg_decode_batch")
+        return None
+    seg_bits = JPEG_SPLIT_SEG_BITS if seg_bits is None else int(seg_bits)
+    rounds = JPEG_SPLIT_ROUNDS if rounds is None else int(rounds)
     with torch.cuda.device(Y.device):
-        L.check(L.lib().rgbnm_jpeg_decode_batch(C.byref(dp), n, hb, wb, (hb + 1) // 2, (wb + 1) // 2, Y.data_ptr(), CbCr.data_ptr(),
-                                                status.data_ptr(), L.stream()), "jpeg_decode_batch")
+        if scratch is None:
+            scratch = jpeg_split_scratch(plan, seg_bits, Y.device)
+        if path is None:
+            path = torch.empty(n, dtype=torch.int32, device=Y.device)
+        L.require_cuda(path, scratch)
+        if path.dtype != torch.int32 or path.numel() != n or not path.is_contiguous() or scratch.dtype != torch.uint8 \
+                or not scratch.is_contiguous():
+            raise L.RgbnmError("path must be int32 [n], scratch uint8 (jpeg_split_scratch)")
+        L.check(L.lib().rgbnm_jpeg_decode_batch_split(C.byref(dp), n, hb, wb, (hb + 1) // 2, (wb + 1) // 2, Y.data_ptr(), CbCr.data_ptr(),
+                                                      status.data_ptr(), path.data_ptr(), scratch.data_ptr(), scratch.numel(), seg_bits,
+                                                      rounds, L.stream()), "jpeg_decode_batch_split")
+    return path
 
 
-def decode_jpeg_batch(plan, device="cuda", out=None):
+def decode_jpeg_batch(plan, device="cuda", out=None, split=False, seg_bits=None, rounds=None, return_path=False):
     """Device half: one H2D copy per plan buffer on the current stream, then ONE launch that walks every run with one lane (there is
     no CPU fallback).  Returns (Y, CbCr, quant, status) on the device: the int16 tensors of read_coefficients_batch, bit for bit, and
     int32 status per file -- the plan's host status, lowered to a negative code where the walk met an error in the stream (the file's
-    blocks not yet written are then zeros).  Files with a negative HOST status are not written at all.  No host sync."""
+    blocks not yet written are then zeros).  Files with a negative HOST status are not written at all.  No host sync.
+    split=True: the split decode instead (launch_jpeg_decode), for files without restart markers; the same four tensors, and with
+    return_path=True a fifth, the int32 path per file."""
+    if return_path and not split:
+        raise ValueError("return_path belongs to split=True")
     n = plan.n
     if out is None:
         out = alloc_jpeg_out(n, plan.grid, device)
@@ -346,10 +387,10 @@ def decode_jpeg_batch(plan, device="cuda", out=None):
     dev = upload_jpeg_plan(plan, out[0].device)
     out[2].copy_(dev[4], non_blocking=True)
     out[3].copy_(dev[5], non_blocking=True)
-    launch_jpeg_decode(plan, dev, out)
+    path = launch_jpeg_decode(plan, dev, out, split=True, seg_bits=seg_bits, rounds=rounds) if split else launch_jpeg_decode(plan, dev, out)
     for t in dev[:4]:                        # the launch reads them on this stream: keep the allocator from handing them out early
         t.record_stream(torch.cuda.current_stream(out[0].device))
-    return out
+    return out + (path,) if return_path else out
 
 
 def jpeg_status_text(code):
@@ -357,11 +398,11 @@ def jpeg_status_text(code):
     return L.JPEG_STATUS.get(int(code), f"status {int(code)}")
 
 
-def read_coefficients_batch_device(paths_or_bytes, grid=(64, 64), device="cuda"):
+def read_coefficients_batch_device(paths_or_bytes, grid=(64, 64), device="cuda", split=False):
     """read_coefficients_batch with the entropy decode on the device: (Y, CbCr, quant) int16 DEVICE tensors.  Raises, naming the file,
-    when one cannot be decoded there (synchronises to read the device status)."""
+    when one cannot be decoded there (synchronises to read the device status).  split: the split decode (decode_jpeg_batch)."""
     plan = prepare_jpeg_batch(paths_or_bytes, grid)
-    Y, CbCr, quant, status = decode_jpeg_batch(plan, device)
+    Y, CbCr, quant, status = decode_jpeg_batch(plan, device, split=split)
     st = status.cpu()
     if int((st != 0).sum()):
         i = int((st != 0).nonzero()[0])

@@ -177,6 +177,8 @@ PROTOTYPES = {
     "rgbnm_dct_to_pixels": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "rgbnm_jpeg_prepare": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _P(JpegPlan)]),
     "rgbnm_jpeg_decode_batch": (_i, [_P(JpegDevicePlan), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "rgbnm_jpeg_split_scratch_bytes": (_sz, [_sz, _i, _i]),
+    "rgbnm_jpeg_decode_batch_split": (_i, [_P(JpegDevicePlan), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
     "rgbnm_softxent": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "rgbnm_softxent_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "rgbnm_softxent_grad": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),

@@ -33,6 +33,8 @@ batches ahead, each on a stream of its own, without a host sync; the step's stre
 the same whole-grid tensors, bit for bit.  A file the device path refuses (progressive, ...) is decoded by the host reader and
 uploaded into its slot.  The device status of a batch comes back through a pinned copy and is looked at once it has arrived, a
 batch or more later; a negative one raises, naming the file.  Not combinable with crop_on_host.
+`jpeg_split=True` (with decode="device" only): the launch is the split decode (dct_manip.launch_jpeg_decode(split=True)): runs of
+files without restart markers are cut into bit segments, one lane each; the same tensors, bit for bit.
 
 Everything except the H2D copy and the transform is host logic and runs (and is tested) without a GPU: with device="cpu"
 the loader yields the raw (Yq, CbCrq, quant) batches.  Files must share one coefficient grid (default 64 x 64 luma blocks =
@@ -49,7 +51,7 @@ from . import dct_manip as dm
 
 class DCTBatchLoader:
     def __init__(self, paths, labels, batch_size, device="cuda", grid=(64, 64), threads=None, prefetch=2, shuffle=True,
-                 seed=0, rank=0, world_size=1, drop_last=False, transform=None, crop_on_host=False, decode="host"):
+                 seed=0, rank=0, world_size=1, drop_last=False, transform=None, crop_on_host=False, decode="host", jpeg_split=False):
         if len(paths) != len(labels):
             raise ValueError("paths and labels differ in length")
         if batch_size <= 0 or prefetch < 1:
@@ -73,7 +75,9 @@ class DCTBatchLoader:
                              "before PCIe (crop_on_host=True belongs to the host decode)")
         if decode == "device" and self.device.type != "cuda":
             raise ValueError('decode="device" needs a HIP device')
-        self.decode = decode
+        if jpeg_split and decode != "device":
+            raise ValueError('jpeg_split=True cuts the runs of the DEVICE decode into segments: it needs decode="device"')
+        self.decode, self.jpeg_split = decode, bool(jpeg_split)
         self.h2d_bytes = 0
         self.last_packed = None        # crop_on_host: the (packed parameters, nops) of the batch yielded last (tests)
         self.epoch = 0
@@ -146,7 +150,7 @@ class DCTBatchLoader:
     def _launch_device(self, plan, fallback, lab, stream):
         """Consumer side: uploads and the decode launch on a side stream; nothing here waits for the device."""
         with torch.cuda.stream(stream):
-            Y, C, Q, st = dm.decode_jpeg_batch(plan, self.device)
+            Y, C, Q, st = dm.decode_jpeg_batch(plan, self.device, split=self.jpeg_split)
             for k, y, c, q in fallback:          # refused by prepare: the kernel leaves these slots alone
                 Y[k].copy_(y, non_blocking=True)
                 if c is None:

@@ -9,9 +9,18 @@ tests/test_loader_gpu.py makes them (16 x 16 random colours upsampled bicubic, p
   (c) tools/pipeline_bench.py images/s: --decode host (the loader's existing path, 16 threads, measured again here) and --decode
       device on the same files without restart markers and with one per MCU row; each a process of its own.
 
+  (s) the SPLIT decode launch (dct_manip.launch_jpeg_decode(split=True): long runs cut into bit segments, one lane each) beside the
+      plain launch of (b) -- the same code as before, so the yardstick -- on the same four file sets, in the same interleaved rounds:
+      seg_bits in 512 / 1024 / 2048 / 4096 and a few values of rounds, with the share of images per `path` value (0 not split,
+      1 split, 2 split and then decoded by the one-lane walk).
+  (p) tools/pipeline_bench.py images/s with --decode device --jpeg-split on the marker-less files and on those with a marker per
+      MCU row, beside --decode host at 16 threads and plain --decode device; each a process of its own per round.
+  (s) and (p) go to profiles/jpeg_split.json, (a) - (c) to profiles/jpeg_decode.json.
+
 Protocol of the other step tools: warm-up, then ROUNDS interleaved rounds (order reversed every other round); median and min - max.
-Writes profiles/jpeg_decode.json (parts given with --parts are replaced, the others kept) and prints it.
-usage: python tools/jpeg_decode_step.py [--parts a,b,c] [--rounds 6] [--batch 256]"""
+Writes profiles/jpeg_decode.json, or profiles/jpeg_split.json for parts s / p (parts given with --parts are replaced, the others
+kept), and prints it.
+usage: python tools/jpeg_decode_step.py [--parts a,b,c | s,p] [--rounds 6] [--batch 256]"""
 import argparse
 import io
 import json
@@ -110,10 +119,60 @@ def part_b(B, rounds, iters, warmup):
     return out
 
 
-def part_c(B, rounds, steps, warmup):
-    cfgs = {"host_16_threads": ["--decode", "host", "--threads", "16"],
+SPLIT_SEG_BITS = (512, 1024, 2048, 4096)
+SPLIT_ROUNDS = (2, 6, 16)
+
+
+def part_s(B, rounds, iters, warmup, sets):
+    dev = torch.device("cuda", 0)
+    fns, meta, keep = {}, {}, []
+    for name in sets:
+        files = synth(64, **SETS[name])
+        batch = [files[i % 64] for i in range(B)]
+        plan = DM.prepare_jpeg_batch(batch, grid=(64, 64))
+        assert plan.nbad == 0
+        up = DM.upload_jpeg_plan(plan, dev)
+        out = DM.alloc_jpeg_out(B, (64, 64), dev)
+        out[2].copy_(up[4])
+        out[3].copy_(up[5])
+        DM.launch_jpeg_decode(plan, up, out)
+        torch.cuda.synchronize()
+        want = [t.clone() for t in out]
+        keep.append((plan, up, out))
+        fns[name] = lambda plan=plan, up=up, out=out: DM.launch_jpeg_decode(plan, up, out)
+        meta[name] = {"runs": plan.nruns, "file_bytes_per_batch": sum(len(b) for b in batch), "stream_bytes": plan.stream_bytes}
+        for sb in SPLIT_SEG_BITS:
+            scratch = DM.jpeg_split_scratch(plan, sb, dev)
+            for r in SPLIT_ROUNDS:
+                path = torch.empty(B, dtype=torch.int32, device=dev)
+                for t in out[:2]:
+                    t.fill_(0x5555)
+                DM.launch_jpeg_decode(plan, up, out, split=True, seg_bits=sb, rounds=r, path=path, scratch=scratch)
+                torch.cuda.synchronize()
+                assert all(torch.equal(x, y) for x, y in zip(out, want)), (name, sb, r)       # the bits of the plain launch
+                share = [float((path == v).sum()) / B for v in (0, 1, 2)]
+                cfg = f"{name}_split_sb{sb}_r{r}"
+                fns[cfg] = lambda plan=plan, up=up, out=out, sb=sb, r=r, path=path, scratch=scratch: DM.launch_jpeg_decode(
+                    plan, up, out, split=True, seg_bits=sb, rounds=r, path=path, scratch=scratch)
+                meta[cfg] = dict(meta[name], seg_bits=sb, sync_rounds=r, scratch_bytes=scratch.numel(), path_share=share)
+    out = summary(timed(list(fns), fns, warmup, rounds, iters))
+    for k, v in out.items():
+        v.update(meta[k])
+        v["images_per_s"] = B / v["ms_median"] * 1e3
+        print(f"(s) {k}: {v['ms_median']:.3f} ms ({v['ms_min']:.3f} - {v['ms_max']:.3f}) per batch, path share {v.get('path_share')}",
+              file=sys.stderr)
+    return out
+
+
+PIPELINE = {"host_16_threads": ["--decode", "host", "--threads", "16"],
             "device": ["--decode", "device", "--threads", "16", "--prefetch", "4"],
             "device_rst_row": ["--decode", "device", "--threads", "16", "--prefetch", "4", "--restart-rows", "1"]}
+PIPELINE_SPLIT = {"host_16_threads": PIPELINE["host_16_threads"], "device": PIPELINE["device"],
+                  "device_split": PIPELINE["device"] + ["--jpeg-split"], "device_rst_row": PIPELINE["device_rst_row"],
+                  "device_rst_row_split": PIPELINE["device_rst_row"] + ["--jpeg-split"]}
+
+
+def part_c(B, rounds, steps, warmup, cfgs=PIPELINE):
     val = {k: [] for k in cfgs}
     last = {}
     for r in range(rounds):
@@ -127,7 +186,8 @@ def part_c(B, rounds, steps, warmup):
             val[k].append(last[k]["value"])
             print(f"(c) round {r} {k}: {last[k]['value']} images/s", file=sys.stderr, flush=True)
     return {k: {"images_per_s": spread(val[k]), "ms_per_step": last[k]["ms_per_step"], "h2d_bytes_per_image": last[k]["h2d_bytes_per_image"],
-                "host_decode_only_images_per_sec": last[k]["host_decode_only_images_per_sec"], "steps": steps, "args": cfgs[k]}
+                "host_decode_only_images_per_sec": last[k]["host_decode_only_images_per_sec"], "steps": steps, "args": cfgs[k],
+                "jpeg_split_seg_bits": last[k].get("jpeg_split_seg_bits"), "jpeg_split_rounds": last[k].get("jpeg_split_rounds")}
             for k in cfgs}
 
 
@@ -139,8 +199,14 @@ def main():
     ap.add_argument("--iters", type=int, default=5, help="(b) launches per timed block")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--steps", type=int, default=40, help="(c) timed steps per process")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode.json"))
+    ap.add_argument("--sets", default=",".join(SETS), help="(s) file sets")
+    ap.add_argument("--out", default=None, help="default: profiles/jpeg_split.json for parts s / p, else profiles/jpeg_decode.json")
     a = ap.parse_args()
+    parts = a.parts.split(",")
+    if bool(set(parts) & {"s", "p"}) and bool(set(parts) & {"a", "b", "c"}):
+        raise SystemExit("parts s / p and a / b / c write different files: run them separately")
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "jpeg_split.json" if set(parts) & {"s", "p"} else "jpeg_decode.json")
     assert torch.cuda.is_available(), "needs the GPU"
     torch.cuda.set_device(0)
     res = {}
@@ -149,13 +215,18 @@ def main():
             res = json.loads(fh.read())
     res.update({"batch": a.batch, "rounds": a.rounds, "device": torch.cuda.get_device_name(0), "source_hash": L.source_hash(),
                 "host_cpus": DM.default_threads()})
-    parts = a.parts.split(",")
     if "a" in parts:
         res["a_prepare_host"] = part_a(a.batch, a.rounds)
     if "b" in parts:
         res["b_decode_launch"] = part_b(a.batch, a.rounds, a.iters, a.warmup)
     if "c" in parts:
         res["c_pipeline"] = part_c(a.batch, a.rounds, a.steps, 8)
+    if "s" in parts:
+        res["s_split_launch"] = part_s(a.batch, a.rounds, a.iters, a.warmup, a.sets.split(","))
+        res["split_defaults"] = {"seg_bits": DM.JPEG_SPLIT_SEG_BITS, "rounds": DM.JPEG_SPLIT_ROUNDS, "min_seg": 16}
+    if "p" in parts:
+        res["p_pipeline"] = part_c(a.batch, a.rounds, a.steps, 8, PIPELINE_SPLIT)
+        res["split_defaults"] = {"seg_bits": DM.JPEG_SPLIT_SEG_BITS, "rounds": DM.JPEG_SPLIT_ROUNDS, "min_seg": 16}
     line = json.dumps(res)
     with open(a.out, "w") as fh:
         fh.write(line + "\n")

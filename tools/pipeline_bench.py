@@ -48,6 +48,8 @@ def main():
                     help="device: the loader ships the compressed bytes and the GPU walks the restart runs (no crop on the host then)")
     ap.add_argument("--restart-rows", type=int, default=0, help="synthetic files carry a restart marker every N MCU rows (0: none)")
     ap.add_argument("--prefetch", type=int, default=2, help="batches the loader keeps ahead of the step")
+    ap.add_argument("--jpeg-split", action="store_true",
+                    help="with --decode device: long runs are cut into bit segments, one lane each (loader jpeg_split)")
     a = ap.parse_args()
     if a.decode == "device":
         a.crop_on_host = 0
@@ -86,7 +88,8 @@ def main():
     nb = a.warmup + a.steps + 4
     loader = DCTBatchLoader([batch_paths[i % B] for i in range(nb * B)], [int(v) for v in torch.randint(0, 999, (nb * B,))], B,
                             device=dev, threads=a.threads, prefetch=a.prefetch, shuffle=False,
-                            transform=aug if a.crop_on_host else None, crop_on_host=bool(a.crop_on_host), decode=a.decode)
+                            transform=aug if a.crop_on_host else None, crop_on_host=bool(a.crop_on_host), decode=a.decode,
+                            jpeg_split=a.jpeg_split)
     it = iter(loader)
 
     def step():
@@ -114,7 +117,9 @@ def main():
     it.close()
     h2d = loader.h2d_bytes / B if (a.crop_on_host or a.decode == "device") else 64 * 64 * 64 * 2 + 2 * 32 * 32 * 64 * 2 + 3 * 64 * 2
     out = {"metric": f"images/sec JPEG-Ti DCT train step fed from JPEG files ({a.decode} entropy decode + H2D inside)",
-           "decode": a.decode, "restart_rows": a.restart_rows, "prefetch": a.prefetch,
+           "decode": a.decode, "jpeg_split": bool(a.jpeg_split),
+           "jpeg_split_seg_bits": dm.JPEG_SPLIT_SEG_BITS if a.jpeg_split else None,      # what the loader's split launch uses
+           "jpeg_split_rounds": dm.JPEG_SPLIT_ROUNDS if a.jpeg_split else None, "restart_rows": a.restart_rows, "prefetch": a.prefetch,
            "value": round(B * a.steps / dt, 1), "unit": "images/sec", "n_gpus": 1, "steps": a.steps,
            "ms_per_step": round(1e3 * dt / a.steps, 3), "per_gpu_batch": B, "host_threads": a.threads,
            "host_decode_only_images_per_sec": round(dec, 1), "avg_jpeg_bytes": round(fsize),
