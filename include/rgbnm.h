@@ -102,6 +102,7 @@ int rgbnm_abi_version(void);
  *                     in rgbnm_jpeg_decode_batch_split also the segments per wave of its segment launches
  *   "jpeg_min_seg" 0  rgbnm_jpeg_decode_batch_split splits runs of at least this many segments (0: 16; at least 2)
  *   "jpeg_split_wgs" 0  cap on the workgroups of each of its launches (0: 4096; tests send the grid-stride loops round again)
+ *   "jpeg_encode_wgs" 0  the same cap for the launches of rgbnm_jpeg_encode_batch
  *   measurement
  *   "trace"        0  bit mask of kernel classes to bracket with HIP events, see rgbnm_trace_collect */
 int rgbnm_set_option(const char* name, int value);
@@ -438,6 +439,8 @@ int rgbnm_dct_to_pixels(const int16_t* Y, const int16_t* CbCr, int B, int H, int
 #define RGBNM_JPEG_EOVERRUN (-22)      /* device: more bits consumed than the run holds */
 #define RGBNM_JPEG_ETRAILING (-23)     /* device: more than a byte of bits left over after the run's last MCU */
 #define RGBNM_JPEG_ERECORD (-24)       /* device: a run / image record that does not fit the buffers it points into */
+#define RGBNM_JPEG_ERANGE (-25)        /* encode: an AC coefficient beyond +-1023, a DC difference beyond +-2047 or a quantisation value
+                                          outside 1..255: baseline Huffman coding cannot express it */
 
 /* One run: the entropy-coded bytes between two markers, un-stuffed.  offset is a multiple of 4; behind the nbytes bytes the stream
  * holds zeros up to the next multiple of 4 and 4 more, so that 32-bit reads of a run never leave the buffer.  nmcu == 0: a record of
@@ -524,6 +527,39 @@ size_t rgbnm_jpeg_split_scratch_bytes(size_t stream_bytes, int nruns, int seg_bi
 int rgbnm_jpeg_decode_batch_split(const rgbnm_jpeg_device_plan* plan, int n, int Hb, int Wb, int Hbc, int Wbc, int16_t* Y, int16_t* CbCr,
                                   int32_t* status, int32_t* path, void* scratch, size_t scratch_bytes, int seg_bits, int rounds,
                                   void* stream);
+
+/* Entropy ENCODING on the device (csrc/jpeg_emit.h, jpeg_encode.hip): from the int16 coefficient tensors back to whole files, SOI to
+ * EOI.  The file is the one libjpeg's jpeg_write_coefficients writes with its defaults, byte for byte (the reference's
+ * write_coefficients, dct_manip.cpp:265-313): SOI, APP0 JFIF 1.01, one 8-bit DQT segment per table (table 0 luma, table 1 BOTH chroma
+ * planes), SOF0 (ids 1 2 3, sampling 22 11 11, or one component 11), the T.81 Annex K Huffman tables as four (two) DHT segments,
+ * DRI when restart != 0, SOS, the interleaved scan, EOI.  A luma block of the MCU padding beyond the kept grid is coded with zero AC
+ * and the DC of the block before it in its MCU, as libjpeg's transcoder fills it.
+ *   Y, CbCr   device int16 [n][Hb][Wb][64], [n][2][Hbc][Wbc][64] (16-byte aligned), natural order; CbCr NULL: one component.
+ *             Three components need Hbc = ceil(Hb / 2), Wbc = ceil(Wb / 2); grids 1..4096 with at most 2^32 / 1660 blocks per image
+ *   quant     device int16 [n][C][64], natural order, C = 3 or 1: the layout the decode writes; tables 0 and 1 are used
+ *   dims      device int32 [n][2]: height, width in pixels; the kept grids of that size must be the call's (else RGBNM_JPEG_EGRID)
+ *   restart   restart interval in MCUs, 0..65535 (0: no DRI, no RSTn); a value above the MCU count is written to DRI and has one run
+ *   out       device uint8 [n][stride]: each file from SOI on         nbytes  device int32 [n]: the file's size, 0 for a failed image
+ *   status    device int32 [n], written for every image: 0, RGBNM_JPEG_ERANGE, RGBNM_JPEG_ECAPACITY (the file is longer than
+ *             stride; rgbnm_jpeg_encode_bound always suffices) or RGBNM_JPEG_EGRID.  A failed image's slot of `out` is not touched
+ *             and the other images are unaffected
+ *   scratch   device memory, 16-byte aligned, at least rgbnm_jpeg_encode_scratch_bytes(...) bytes; nothing is kept between calls
+ * Four launches whatever n and the data (measure, place, emit, stuff: csrc/jpeg_encode.hip); no allocation, no copy, no
+ * synchronisation: capturable.  The bytes are the same on every run: shared words are merged by integer OR.  Every store is checked
+ * against its buffer and every loop is bounded by the grid or by counts the kernels computed.  Option "jpeg_encode_wgs" caps the
+ * workgroups per launch.  RGBNM_EINVAL with nothing launched: a NULL pointer other than CbCr, n <= 0, grids or restart out of
+ * range, stride 0 or >= 2^31, misaligned pointers, scratch too small.
+ * rgbnm_jpeg_encode_bound: the worst-case file size for a grid (every block at its 1660 bits, every scan byte stuffed); 0 for
+ * arguments the encode refuses.  rgbnm_jpeg_encode_scratch_bytes: 0 likewise, or for n <= 0 or stride 0.  rgbnm_jpeg_encode_header:
+ * the header bytes (SOI through the SOS header) of one image, written to out[cap]; returns their count (623 / 328, + 6 with DRI), or
+ * RGBNM_EINVAL (NULL, ncomp not 1 or 3, a size outside 1..65535, a quant value outside 1..255, restart out of range, cap too small);
+ * quant is host int16 [ncomp][64].  The kernel writes the same bytes from the same code.  All three are host only: no HIP call. */
+size_t rgbnm_jpeg_encode_bound(int Hb, int Wb, int Hbc, int Wbc, int ncomp, int restart);
+size_t rgbnm_jpeg_encode_scratch_bytes(int n, int Hb, int Wb, int Hbc, int Wbc, int ncomp, int restart, size_t stride);
+int rgbnm_jpeg_encode_header(int ncomp, int height, int width, const int16_t* quant, int restart, uint8_t* out, size_t cap);
+int rgbnm_jpeg_encode_batch(const int16_t* Y, const int16_t* CbCr, const int16_t* quant, const int32_t* dims, int n, int Hb, int Wb,
+                            int Hbc, int Wbc, int restart, uint8_t* out, size_t stride, int32_t* nbytes, int32_t* status,
+                            void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Train-step tail

@@ -10,6 +10,9 @@ H2D copy (replaces per-sample tensors + default collate, datasets.py:274-297,542
 
 `quantize_at_quality` and `decode_coeff` (dct_manip.cpp:315-375, 485-576) run on DEVICE tensors, one HIP launch per call
 (csrc/pixel_dct.hip), for one image or a batch; there is no CPU fallback.
+
+`write_coefficients` (dct_manip.cpp:265-313) writes the reference's file byte for byte, Huffman-encoded on the device
+(csrc/jpeg_encode.hip); `encode_jpeg_batch` / `write_coefficients_batch` are its batched forms, optionally with restart markers.
 """
 import ctypes as C
 import os
@@ -508,3 +511,202 @@ def decode_coeff(dim, quant, Y, CbCr=None, quality=-1):
         L.check(L.lib().rgbnm_dct_to_pixels(Y.data_ptr(), L.ptr(CbCr), B, H, W, table.data_ptr(), out.data_ptr(), L.stream()),
                 "dct_to_pixels")
     return out
+
+
+# ---- coefficients -> JPEG files on the device (csrc/jpeg_emit.h, jpeg_encode.hip) --------------------------------------------
+def _restart_interval(restart, mcus_x):
+    if restart == "row":
+        return int(mcus_x)
+    if isinstance(restart, str) or not 0 <= int(restart) <= 65535:
+        raise ValueError(f'restart must be 0..65535 MCUs or "row", got {restart!r}')
+    return int(restart)
+
+
+def _encode_grids(Y, CbCr):
+    from . import lib as L
+    if not torch.is_tensor(Y) or Y.dtype != torch.int16 or Y.dim() != 6 or tuple(Y.shape[1:2] + Y.shape[4:]) != (1, 8, 8):
+        raise L.RgbnmError(f"Y must be int16 (n,1,Hb,Wb,8,8), got {tuple(Y.shape) if torch.is_tensor(Y) else type(Y).__name__}")
+    n, hb, wb = int(Y.shape[0]), int(Y.shape[2]), int(Y.shape[3])
+    hbc, wbc = (hb + 1) // 2, (wb + 1) // 2
+    if CbCr is not None and (CbCr.dtype != torch.int16 or tuple(CbCr.shape) != (n, 2, hbc, wbc, 8, 8)):
+        raise L.RgbnmError(f"CbCr must be int16 {(n, 2, hbc, wbc, 8, 8)} for Y {tuple(Y.shape)} (4:2:0), got {tuple(CbCr.shape)}")
+    if n < 1 or hb < 1 or wb < 1:
+        raise L.RgbnmError(f"empty coefficient grid {tuple(Y.shape)}")
+    return n, hb, wb, hbc, wbc
+
+
+def _encode_quant(quant, n, ch, dev):
+    """int16 (n,ch,64) on dev from (C,8,8) / (C,64) for all images or (n,C,8,8) / (n,C,64), C >= ch (the decode returns three)."""
+    from . import lib as L
+    q = torch.as_tensor(quant)
+    if q.dtype == torch.int16 and q.dim() >= 2 and tuple(q.shape[-2:]) == (8, 8):
+        q = q.reshape(q.shape[:-2] + (64,))
+    if q.dtype != torch.int16 or q.dim() not in (2, 3) or q.shape[-1] != 64 or q.shape[-2] < ch or (q.dim() == 3 and q.shape[0] != n):
+        raise L.RgbnmError(f"quant must be int16 ({ch},8,8) or ({n},{ch},8,8), got {q.dtype} {tuple(q.shape)}")
+    if q.dim() == 2:
+        q = q.unsqueeze(0).expand(n, q.shape[0], 64)
+    return q[:, :ch].to(dev).contiguous()
+
+
+def jpeg_encode_header_bytes(channels=3, restart=0):
+    """Size of the header encode_jpeg_batch writes (SOI through the SOS header)."""
+    return (623 if channels == 3 else 328) + (6 if restart else 0)
+
+
+def _default_stride(ch, ri, hb, wb):
+    """The header plus one byte per coefficient of the kept grids."""
+    return jpeg_encode_header_bytes(ch, ri) + 64 * (hb * wb + (2 * ((hb + 1) // 2) * ((wb + 1) // 2) if ch == 3 else 0))
+
+
+def jpeg_encode_bound(grid, channels=3, restart=0):
+    """Worst-case size of a file of luma grid (Hb, Wb): a stride that never gives 'plan buffers too small' (rgbnm_jpeg_encode_bound)."""
+    from . import lib as L
+    hb, wb = (int(v) for v in grid)
+    mx = (wb + 1) // 2 if channels == 3 else wb
+    b = L.lib().rgbnm_jpeg_encode_bound(hb, wb, (hb + 1) // 2, (wb + 1) // 2, int(channels), _restart_interval(restart, mx))
+    if b == 0:
+        raise L.RgbnmError(f"grid {grid} with {channels} channel(s), restart {restart}: not a layout the encoder writes")
+    return int(b)
+
+
+def jpeg_encode_header(height, width, quant, restart=0):
+    """The header bytes of one file, SOI through the SOS header, as the device writes them (host only: rgbnm_jpeg_encode_header).
+    quant int16 (C,8,8), C = 1 or 3."""
+    from . import lib as L
+    q = torch.as_tensor(quant).detach().cpu().to(torch.int16).reshape(-1, 64).contiguous()
+    if q.shape[0] not in (1, 3):
+        raise L.RgbnmError("quant must be int16 (1,8,8) or (3,8,8)")
+    buf = (C.c_uint8 * 640)()
+    mx = -(-int(width) // (16 if q.shape[0] == 3 else 8))
+    rc = L.lib().rgbnm_jpeg_encode_header(int(q.shape[0]), int(height), int(width), q.data_ptr(), _restart_interval(restart, mx), buf, 640)
+    if rc < 0:
+        L.check(rc, "jpeg_encode_header")
+    return bytes(buf[:rc])
+
+
+def jpeg_encode_scratch(n, grid, channels=3, restart=0, stride=None, device="cuda"):
+    """uint8 device tensor for encode_jpeg_batch(scratch=...) with these arguments (restart as an interval in MCUs or "row")."""
+    from . import lib as L
+    hb, wb = (int(v) for v in grid)
+    hbc, wbc = (hb + 1) // 2, (wb + 1) // 2
+    ri = _restart_interval(restart, wbc if channels == 3 else wb)
+    if stride is None:
+        stride = _default_stride(channels, ri, hb, wb)
+    nbytes = L.lib().rgbnm_jpeg_encode_scratch_bytes(int(n), hb, wb, hbc, wbc, int(channels), ri, int(stride))
+    if nbytes == 0:
+        raise L.RgbnmError(f"n {n}, grid {grid}, {channels} channel(s), restart {restart}, stride {stride}: not a call the encoder takes")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def encode_jpeg_batch(Y, CbCr, quant, dims=None, restart=0, stride=None, out=None, scratch=None):
+    """Whole baseline JPEG files from coefficient tensors ON THE DEVICE (rgbnm_jpeg_encode_batch; there is no CPU fallback): four
+    launches, no copy and no host synchronisation when every argument already is a device tensor, so the call can be captured.
+    Y int16 (n,1,Hb,Wb,8,8), CbCr int16 (n,2,ceil(Hb/2),ceil(Wb/2),8,8) or None (one component); quant int16 (n,C,8,8) as
+    decode_jpeg_batch returns it, or (C,8,8) for all images (table 1 serves both chroma planes); dims int32 (n,2) [height, width]
+    per image, or None: 8 Hb x 8 Wb.  restart: the restart interval in MCUs, 0 for none, "row" for one interval per MCU row (the
+    layout the plain device decode is fast on).  stride: bytes per file slot; None: the header plus one byte per coefficient.
+    out: (buf uint8 (n,stride), nbytes int32 (n), status int32 (n)) to write into.  Returns (buf, nbytes, status) on the device:
+    status 0, or a negative code (jpeg_status_text) with nbytes 0 and the slot untouched -- "DCT coefficient out of range" for an AC
+    coefficient beyond +-1023 or a DC step beyond +-2047, "plan buffers too small" when the file is longer than stride
+    (jpeg_encode_bound never is), "grid differs" when dims does not give the tensors' grids.  The files are what libjpeg's
+    jpeg_write_coefficients writes (the reference's write_coefficients), byte for byte."""
+    from . import lib as L
+    n, hb, wb, hbc, wbc = _encode_grids(Y, CbCr)
+    ch = 1 if CbCr is None else 3
+    L.require_cuda(Y, CbCr)
+    dev = Y.device
+    ri = _restart_interval(restart, wbc if ch == 3 else wb)
+    quant = _encode_quant(quant, n, ch, dev)
+    if dims is None:
+        dims = torch.tensor([[8 * hb, 8 * wb]] * n, dtype=torch.int32)
+    dims = torch.as_tensor(dims)
+    if dims.dtype != torch.int32 or dims.numel() != 2 * n:
+        raise L.RgbnmError(f"dims must be int32 (n,2) [height, width], got {dims.dtype} {tuple(dims.shape)}")
+    dims = dims.reshape(n, 2).to(dev).contiguous()
+    if stride is None:
+        stride = _default_stride(ch, ri, hb, wb)
+    stride = int(stride)
+    with torch.cuda.device(dev):
+        if out is None:
+            out = (torch.empty((n, stride), dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+                   torch.empty(n, dtype=torch.int32, device=dev))
+        buf, nbytes, status = out
+        L.require_cuda(buf, nbytes, status)
+        if buf.dtype != torch.uint8 or tuple(buf.shape) != (n, stride) or nbytes.dtype != torch.int32 or nbytes.numel() != n \
+                or status.dtype != torch.int32 or status.numel() != n:
+            raise L.RgbnmError(f"out must be (uint8 ({n},{stride}), int32 ({n}), int32 ({n}))")
+        if scratch is None:
+            scratch = jpeg_encode_scratch(n, (hb, wb), ch, ri, stride, dev)
+        L.require_cuda(scratch)
+        if scratch.dtype != torch.uint8:
+            raise L.RgbnmError("scratch must be uint8 (jpeg_encode_scratch)")
+        L.check(L.lib().rgbnm_jpeg_encode_batch(Y.data_ptr(), L.ptr(CbCr), quant.data_ptr(), dims.data_ptr(), n, hb, wb, hbc, wbc, ri,
+                                                buf.data_ptr(), stride, nbytes.data_ptr(), status.data_ptr(), scratch.data_ptr(),
+                                                scratch.numel(), L.stream()), "jpeg_encode_batch")
+    return buf, nbytes, status
+
+
+def encode_jpeg_files(Y, CbCr, quant, dims=None, restart=0):
+    """encode_jpeg_batch, then the files as a list of bytes on the host (synchronises).  An image whose file did not fit the default
+    stride is encoded again with the worst-case stride; any other failure raises libjpeg_exception, with the reference's wording
+    ("DCT coefficient out of range") for a value baseline Huffman coding cannot express."""
+    from . import lib as L
+    n, hb, wb, _, _ = _encode_grids(Y, CbCr)
+    buf, nbytes, status = encode_jpeg_batch(Y, CbCr, quant, dims, restart)
+    st, nb = status.cpu(), nbytes.cpu()
+    host = buf.cpu()
+    files = [bytes(host[i, :int(nb[i])].numpy().tobytes()) for i in range(n)]
+    again = [i for i in range(n) if int(st[i]) == -15]
+    if again:
+        idx = torch.tensor(again, device=Y.device)
+        q = _encode_quant(quant, n, 1 if CbCr is None else 3, Y.device).index_select(0, idx)
+        d = None if dims is None else torch.as_tensor(dims).reshape(n, 2).to(Y.device).index_select(0, idx)
+        b2, n2, s2 = encode_jpeg_batch(Y.index_select(0, idx).contiguous(), None if CbCr is None else CbCr.index_select(0, idx).contiguous(),
+                                       q, d, restart, stride=jpeg_encode_bound((hb, wb), 1 if CbCr is None else 3, restart))
+        b2, n2, s2 = b2.cpu(), n2.cpu(), s2.cpu()
+        for k, i in enumerate(again):
+            st[i] = s2[k]
+            files[i] = bytes(b2[k, :int(n2[k])].numpy().tobytes())
+    for i in range(n):
+        if int(st[i]) != 0:
+            text = jpeg_status_text(st[i])
+            raise libjpeg_exception(text if int(st[i]) == -25 else f"image {i}: device encode refused the image: {text}")
+    return files
+
+
+def write_coefficients_batch(paths, dims, quant, Y, CbCr=None, restart=0):
+    """One file per image of a batch: Y int16 (n,1,Hb,Wb,8,8), CbCr int16 (n,2,Hbc,Wbc,8,8) or None, quant int16 (n,C,8,8) or (C,8,8),
+    dims int32 (n,2) [height, width] or None; tensors on the CPU are copied to the device, where the encode always runs.  restart as
+    in encode_jpeg_batch: restart="row" writes files the plain device decode reads at full speed (a lossless transcode when the
+    coefficients came from decode_jpeg_batch)."""
+    from . import lib as L
+    paths = list(paths)
+    if not torch.is_tensor(Y) or Y.dim() != 6 or len(paths) != Y.shape[0]:
+        raise L.RgbnmError("one path per image of Y (n,1,Hb,Wb,8,8)")
+    if not Y.is_cuda:
+        if not torch.cuda.is_available():
+            raise L.RgbnmError("write_coefficients encodes on the device (HIP); there is no CPU fallback")
+        Y = Y.to("cuda")
+    if CbCr is not None:
+        CbCr = CbCr.to(Y.device)
+    files = encode_jpeg_files(Y.contiguous(), None if CbCr is None else CbCr.contiguous(), quant, dims, restart)
+    for p, data in zip(paths, files):
+        try:
+            fh = open(p, "wb")
+        except OSError:
+            raise RuntimeError(f"Unable to open file for reading: {p}") from None      # the reference's wording, dct_manip.cpp:271-275
+        with fh:
+            fh.write(data)
+
+
+def write_coefficients(path, dimensions, quantization, Y, CbCr=None):
+    """Reference: dct_manip.write_coefficients (dct_manip.cpp:265-313) with its argument layout -- dimensions int32 [[H,W],...] (row 0
+    is used), quantization int16 (C,8,8) (table 1 serves both chroma planes), Y int16 (1,Hb,Wb,8,8), CbCr int16 (2,Hbc,Wbc,8,8) or
+    None -- and its file, byte for byte: standard Huffman tables, 4:2:0, no restart markers.  The encode runs on the device (CPU
+    tensors are copied there).  Raises libjpeg_exception("DCT coefficient out of range") like the reference."""
+    from . import lib as L
+    if not torch.is_tensor(Y) or Y.dim() != 5:
+        raise L.RgbnmError("Y must be int16 (1,Hb,Wb,8,8)")
+    dim = torch.as_tensor(dimensions).reshape(-1, 2)[:1].to(torch.int32)
+    write_coefficients_batch([path], dim, torch.as_tensor(quantization).reshape(-1, 8, 8), Y.unsqueeze(0),
+                             None if CbCr is None else CbCr.unsqueeze(0))
