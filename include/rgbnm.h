@@ -825,7 +825,9 @@ int rgbnm_vit_blocks_bwd_dw_pe(const rgbnm_vit_cfg* cfg, int n, const rgbnm_bloc
  * all 65536 inputs plus a compact LDS image of it, and reads the window back.  On devices where it has been called and the
  * image fits, the fused FeedForwardBlock forward looks gelu / gelu' up instead of computing them (option gelu_table) -- the
  * same bits as the arithmetic for every finite input except those whose u or u / 2 is a bf16 denormal (|u| < 2.36e-38), which
- * give a denormal of the right sign instead of u / 2.  Never called: the arithmetic runs.
+ * give a denormal of the right sign instead of u / 2.  Non-finite inputs: a NaN gives a NaN gelu and +inf gives +inf, as the
+ * arithmetic does; gelu' and -inf differ (lookup: gelu(-inf) = -0, gelu' = 1 / 0 beyond the window; arithmetic: NaN).  Never
+ * called: the arithmetic runs.
  * _info (test / diagnostics, synchronises): win16 = {valid, A0, P1, N1, image dwords, ...}, full65536 (may be NULL) =
  * gelu(u) | gelu'(u) << 16 per bf16 bit pattern u. */
 int rgbnm_gelu_table_init(void* stream);

@@ -60,6 +60,12 @@ __device__ __forceinline__ void gelu_table_pairs4(const unsigned (&pb)[4], unsig
     p1 &= 0x7FFF7FFFu;
     p2 &= 0x7FFF7FFFu;
     asm("v_pk_max_u16 %0, %1, %2" : "=v"(agv[jj]) : "v"(p1), "s"(0x00800080u));
+    {  // a NaN with the sign bit set (0xFF81 ..) is clamped to N1 like every large negative input: take its excess over -inf off the
+       // magnitude, so that N1 - D = 0 becomes 0 - n = 0xFFFF .. 0xFF81, a NaN again, as the arithmetic gives (n = 0 for every other input)
+      unsigned nn;
+      asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(nn) : "v"(pb[jj]), "s"(0xFF80FF80u));
+      asm("v_pk_sub_u16 %0, %1, %2" : "=v"(agv[jj]) : "v"(agv[jj]), "v"(nn));
+    }
     asm("v_pk_max_u16 %0, %1, %2" : "=v"(ak) : "v"(p2), "s"(k.klo));
     asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(i4) : "v"(ak), "v"(k4v), "s"(k.koff));
     asm("v_pk_lshrrev_b16 %0, %1, %2" : "=v"(sg) : "s"(0x000F000Fu), "v"(pb[jj]));

@@ -274,15 +274,25 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNT p) {
         const uint32_t w = ((keep >> r) & 1) ? 0xFFFFFFFFu : 0u;    // (a word drop_one keeps / drops for any threshold < 2^32)
         if (EPI == EPI_RES) v += to_f32(R[(size_t)row * p.ldr + col]);
         if constexpr (EPI == EPI_RES_DROP) v = drop_one(p.d, w, v) + to_f32(R[(size_t)row * p.ldr + col]);
-        if (EPI == EPI_GELU) {
+        if constexpr (EPI == EPI_GELU || EPI == EPI_GELU_DROP) {
           const float u = to_f32(from_f32<T>(v));   // pre-activation at the activation dtype's precision
-          C2[(size_t)row * p.ldc2 + col] = from_f32<T>(dgelu_f(u));
-          v = gelu_f(u);
-        }
-        if constexpr (EPI == EPI_GELU_DROP) {
-          const float u = to_f32(from_f32<T>(v));
-          C2[(size_t)row * p.ldc2 + col] = from_f32<T>(drop_one(p.d, w, dgelu_f(u)));
-          v = drop_one(p.d, w, gelu_f(u));
+          float ge, dg;
+          if constexpr (sizeof(T) == 2) {           // the 16-bit types: the arithmetic of the staged epilogue and of the GELU table, so that
+            const f32x2 x = {u, u};                 // every bf16 path gives the table's bits (tests/test_act_sweep.py); fp32 keeps erff
+            f32x2 gv, dgv;
+            gelu_pair_fast(x, gv, dgv);
+            ge = gv[0];
+            dg = dgv[0];
+          } else {
+            ge = gelu_f(u);
+            dg = dgelu_f(u);
+          }
+          if constexpr (EPI == EPI_GELU_DROP) {
+            ge = drop_one(p.d, w, ge);
+            dg = drop_one(p.d, w, dg);
+          }
+          C2[(size_t)row * p.ldc2 + col] = from_f32<T>(dg);
+          v = ge;
         }
         if (EPI == EPI_POS) v += p.pos[(size_t)(row % p.pos_period) * p.N + col];
         if (EPI == EPI_DGELU) v *= to_f32(R[(size_t)row * p.ldr + col]);

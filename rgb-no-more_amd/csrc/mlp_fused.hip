@@ -467,6 +467,12 @@ __global__ __launch_bounds__(NTHREADS) void mlp_fwd_kernel(MlpArgs p) {
             p1 &= 0x7FFF7FFFu;
             p2 &= 0x7FFF7FFFu;
             asm("v_pk_max_u16 %0, %1, %2" : "=v"(agv[jj]) : "v"(p1), "s"(0x00800080u));
+            {  // a NaN with the sign bit set (0xFF81 ..) is clamped to N1 like every large negative input: take its excess over -inf off the
+               // magnitude, so that N1 - D = 0 becomes 0 - n = 0xFFFF .. 0xFF81, a NaN again, as the arithmetic gives (n = 0 for every other input)
+              unsigned nn;
+              asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(nn) : "v"(pb[jj]), "s"(0xFF80FF80u));
+              asm("v_pk_sub_u16 %0, %1, %2" : "=v"(agv[jj]) : "v"(agv[jj]), "v"(nn));
+            }
             asm("v_pk_max_u16 %0, %1, %2" : "=v"(ak) : "v"(p2), "s"(klo));
             asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(i4) : "v"(ak), "v"(k4v), "s"(koff));
             asm("v_pk_lshrrev_b16 %0, %1, %2" : "=v"(sg) : "s"(0x000F000Fu), "v"(pb[jj]));   // (a literal 15 would shift the low half only)
@@ -805,6 +811,8 @@ __global__ __launch_bounds__(NTHREADS) void mlp_bwd_kernel(MlpBwdArgs p) {
 //     a <  A0 (tiny)          : gelu = u / 2  (exponent - 1: D = 0x80),  gelu' = 0.5
 //     a >= P1, u > 0 (large)  : gelu = u      (D = 0),                   gelu' = 1
 //     a >= N1, u < 0          : gelu = -0     (a clamped to N1, D = N1), gelu' = its constant there
+//       (-inf included, where the arithmetic gives NaN; a NaN with the sign bit set is clamped too and gets its excess over 0xFF80 taken
+//       off max(a, 0x80) before the subtraction: 0 - n is a NaN again, as the arithmetic gives -- tests/test_act_sweep.py)
 // (sign(gelu(u)) = sign(u) throughout).  A0, P1, N1 are not assumed: gelu_scan_kernel finds the widest tiny / narrowest large
 // regions in which the closed forms reproduce g_gelu_full bit for bit and writes the LDS image; if the window does not fit
 // the kernel's LDS the table is marked invalid and the arithmetic runs.  The only inputs whose result differs from the
