@@ -441,6 +441,8 @@ int rgbnm_dct_to_pixels(const int16_t* Y, const int16_t* CbCr, int B, int H, int
 #define RGBNM_JPEG_ERECORD (-24)       /* device: a run / image record that does not fit the buffers it points into */
 #define RGBNM_JPEG_ERANGE (-25)        /* encode: an AC coefficient beyond +-1023, a DC difference beyond +-2047 or a quantisation value
                                           outside 1..255: baseline Huffman coding cannot express it */
+#define RGBNM_JPEG_EBOX (-26)          /* device, crop decode: a crop box that is not even or not inside the grid, or a packed offset
+                                          that is misaligned or does not leave room for the box in its buffer */
 
 /* One run: the entropy-coded bytes between two markers, un-stuffed.  offset is a multiple of 4; behind the nbytes bytes the stream
  * holds zeros up to the next multiple of 4 and 4 more, so that 32-bit reads of a run never leave the buffer.  nmcu == 0: a record of
@@ -527,6 +529,36 @@ size_t rgbnm_jpeg_split_scratch_bytes(size_t stream_bytes, int nruns, int seg_bi
 int rgbnm_jpeg_decode_batch_split(const rgbnm_jpeg_device_plan* plan, int n, int Hb, int Wb, int Hbc, int Wbc, int16_t* Y, int16_t* CbCr,
                                   int32_t* status, int32_t* path, void* scratch, size_t scratch_bytes, int seg_bits, int rounds,
                                   void* stream);
+/* The decode of rgbnm_jpeg_decode_batch for a CROP BOX per image: what the fused train transform reads of a file is the box its
+ * sampler drew, about half the grid, and restart intervals let the device leave the rest alone.
+ *   boxes     device int32 [n][4]: (top, left, h, w) in luma blocks, all even, h, w > 0, inside Hb x Wb; the chroma box is the luma
+ *             box halved (and must lie inside Hbc x Wbc).  The contract of rgbnm_read_coefficients_batch_crop (rgbnm_reader.h).
+ *   y_off, c_off  device int64 [n]: element offsets of image i's crops in the packed buffers, multiples of 8
+ *   Ypacked   int16 [y_elems], 16-byte aligned: image i's luma crop [h][w][64] at Ypacked + y_off[i]
+ *   Cpacked   int16 [c_elems], 16-byte aligned: its chroma crop [2][h/2][w/2][64] at Cpacked + c_off[i]; zeros for a
+ *             one-component file.  The layout is the host crop reader's, exactly.
+ *   walked    device uint32 [nruns] or NULL: the number of MCUs the lane of run ri walked; 0 for a run that was skipped or refused
+ * One launch, one lane per run, as above.  From the boxes of the components, mapped through their sampling factors, a lane knows
+ * which MCUs of its run hold a block of the box.  A run that holds none is NOT WALKED: it reads no word of the stream.  Any other
+ * run is walked from its first MCU (predictors and bit position cannot be skipped) and STOPS after its last MCU, in raster order,
+ * that holds one.  A block is stored only if it lies inside its component's box; nothing else of the packed buffers is written,
+ * and every element of the crops of an accepted image is.
+ * For every input, damaged ones included, with the status arrays of the two calls starting from the same values:
+ *   (a) the packed output equals the box cut out of what rgbnm_jpeg_decode_batch writes for the same plan;
+ *   (b) status_whole <= status_crop <= 0: the crop decode sees a subset of each run's first errors, with their codes;
+ *   (c) status_crop == 0 wherever status_whole == 0.
+ * So a status of 0 here says NOTHING about the bytes of the stream behind the last MCU a box needed: a walk that stops early has
+ * not seen the run's tail and makes neither the RGBNM_JPEG_EOVERRUN check for missing MCUs nor the RGBNM_JPEG_ETRAILING check; a run
+ * walked to its end makes both.  After an error only the blocks of the box still owed by the run are zero-filled.
+ * Each lane checks its image's box and offsets against the grids, y_elems and c_elems before any store (they are device data,
+ * untrusted like the records): a failure lowers status[image] to RGBNM_JPEG_EBOX and nothing of that image is written.
+ * No allocation, no copy, no synchronisation: capturable, and a captured call reads the boxes and offsets at replay.
+ * RGBNM_EINVAL with nothing launched: whatever rgbnm_jpeg_decode_batch refuses (Ypacked / Cpacked for Y / CbCr), NULL boxes, y_off
+ * or c_off, boxes misaligned to 4 bytes, offsets to 8, walked to 4, y_elems or c_elems of 0.  nruns == 0 returns 0 without a launch.
+ * The split decode takes no box: its scout and sync passes must see the whole run whatever the box. */
+int rgbnm_jpeg_decode_batch_crop(const rgbnm_jpeg_device_plan* plan, int n, int Hb, int Wb, int Hbc, int Wbc, const int32_t* boxes,
+                                 const long long* y_off, const long long* c_off, int16_t* Ypacked, size_t y_elems, int16_t* Cpacked,
+                                 size_t c_elems, int32_t* status, uint32_t* walked, void* stream);
 
 /* Entropy ENCODING on the device (csrc/jpeg_emit.h, jpeg_encode.hip): from the int16 coefficient tensors back to whole files, SOI to
  * EOI.  The file is the one libjpeg's jpeg_write_coefficients writes with its defaults, byte for byte (the reference's

@@ -11,6 +11,8 @@
 //     (DC / AC per component), which is the common case: a dataset written by one encoder carries the four standard tables in every
 //     file.  Otherwise the lanes read the batch's table array in global memory.  The choice is wave-uniform.
 //   - an error lowers status[image] with atomicMin; no lane waits for another, no loop depends on the data for its bound.
+// decode_crop_kernel is the same launch for a crop box per image (rgbnm_jpeg_decode_batch_crop): runs outside the box are skipped,
+// the others stop after the last MCU the box needs, and only the box is stored, packed.
 #include "common.h"
 #include "jpeg_scan.h"
 #include "jpeg_walk.h"
@@ -97,6 +99,95 @@ __global__ __launch_bounds__(LANES) void decode_kernel(Args a) {
       if (err) atomicMin(&a.status[r.image], err);
       if (L.ncomp == 1) zero_chroma_share(a.g, r.image, (uint32_t)r.mcu0, (uint32_t)r.nmcu, L.total);
     }
+  }
+}
+
+// ---- the crop decode (rgbnm_jpeg_decode_batch_crop): decode_kernel's structure around the crop form of the walk ---------------------
+// A lane first decides, from its image's box, how many MCUs of its run it has to walk (jpeg_walk.h, crop_mcus): none -- it is then
+// as idle as the lane of a refused record, and does not count when the wave decides whether to stage the tables -- or up to the last
+// MCU that holds a block of the box.
+struct CArgs {
+  rgbnm_jpeg_device_plan p;
+  int n, Hb, Wb, Hbc, Wbc;
+  const int32_t* boxes;                    // [n][4]
+  const long long* y_off;                  // [n]
+  const long long* c_off;
+  int16_t* Y;                              // packed, y_elems
+  int16_t* C;                              // packed, c_elems
+  size_t y_elems, c_elems;
+  int32_t* status;
+  uint32_t* walked;                        // [nruns] or NULL
+  int lanes;
+};
+
+__global__ __launch_bounds__(LANES) void decode_crop_kernel(CArgs a) {
+  using namespace jpegwalk;
+  __shared__ alignas(16) uint8_t s_tile[LANES * PITCH];
+  __shared__ alignas(16) rgbnm_jpeg_hufftab s_tab[SLOTS];
+  __shared__ uint8_t s_zz[64];
+  const int lane = threadIdx.x;
+  int16_t* tile = reinterpret_cast<int16_t*>(s_tile + lane * PITCH);
+  s_zz[lane] = d_zigzag[lane];
+  {
+    V16* t = reinterpret_cast<V16*>(tile);
+    const V16 zero = {0, 0, 0, 0};
+    for (int j = 0; j < 8; ++j) t[j] = zero;
+  }
+  __syncthreads();
+  const int nruns = a.p.nruns, per = a.lanes;
+  for (long long base = (long long)blockIdx.x * per; base < nruns; base += (long long)gridDim.x * per) {
+    const int ri = (int)base + lane;
+    const bool mine = lane < per && ri < nruns;
+    bool ok = mine;                        // the records and the box passed: the run's image is written by this call
+    rgbnm_jpeg_run r = {};
+    Lane L = {};
+    Crop B = {};
+    uint32_t nwalk = 0;
+    if (ok) {
+      r = a.p.runs[ri];
+      if (r.nmcu == 0) {                   // the record of a file the host refused
+        ok = false;
+      } else if (check_run(r, a.p.images, a.n, a.p.stream_bytes, a.p.ntables, &L) != 0) {
+        ok = false;
+        if (r.image >= 0 && r.image < a.n) atomicMin(&a.status[r.image], RGBNM_JPEG_ERECORD);
+      } else if (check_box(a.boxes + 4 * (size_t)r.image, a.y_off[r.image], a.c_off[r.image], a.Hb, a.Wb, a.Hbc, a.Wbc, a.Y, a.y_elems, a.C,
+                           a.c_elems, &B) != 0) {
+        ok = false;
+        atomicMin(&a.status[r.image], RGBNM_JPEG_EBOX);
+      } else {
+        nwalk = crop_mcus(r, L, B);
+      }
+    }
+    const bool live = nwalk != 0;          // only these lanes walk
+    // one table set for the walking lanes of the wave?
+    const unsigned long long mask = __ballot(live);
+    int err = 0;
+    if (mask != 0) {
+      const int first = __ffsll((long long)mask) - 1;
+      const uint64_t dc0 = __shfl((unsigned long long)L.dcsel, first, LANES), ac0 = __shfl((unsigned long long)L.acsel, first, LANES);
+      const bool shared = __all(!live || (L.dcsel == dc0 && L.acsel == ac0));
+      if (shared) {
+        __syncthreads();                   // the previous round's readers of s_tab are done
+        for (int j = lane; j < SLOTS * TAB_PIECES; j += LANES) {
+          const int slot = j / TAB_PIECES, piece = j - slot * TAB_PIECES;
+          const uint32_t t = (uint32_t)(((slot & 1) ? ac0 : dc0) >> (16 * (slot >> 1))) & 0xFFFFu;   // < ntables: check_run
+          reinterpret_cast<V16*>(&s_tab[slot])[piece] = reinterpret_cast<const V16*>(&a.p.tables[t])[piece];
+        }
+        __syncthreads();
+        if (live) {
+          Lane S = L;
+          S.dcsel = 0ull | (2ull << 16) | (4ull << 32);
+          S.acsel = 1ull | (3ull << 16) | (5ull << 32);
+          err = decode_run_crop(a.p.stream, r, S, s_tab, s_zz, B, nwalk, tile);
+        }
+      } else if (live) {
+        err = decode_run_crop(a.p.stream, r, L, a.p.tables, s_zz, B, nwalk, tile);
+      }
+    }
+    if (err) atomicMin(&a.status[r.image], err);
+    // a skipped run takes its share of a one-component file's zero chroma like a walked one
+    if (ok && L.ncomp == 1) zero_chroma_share_crop(B, (uint32_t)r.mcu0, (uint32_t)r.nmcu, L.total);
+    if (mine && a.walked) a.walked[ri] = nwalk;
   }
 }
 
@@ -315,6 +406,39 @@ int rgbnm_jpeg_decode_batch(const rgbnm_jpeg_device_plan* plan, int n, int Hb, i
   a.lanes = per;
   const int groups = cdiv(plan->nruns, per);
   decode_kernel<<<groups < MAX_WGS ? groups : MAX_WGS, LANES, 0, (hipStream_t)stream>>>(a);
+  LAUNCH_CHECK();
+  return RGBNM_OK;
+}
+
+int rgbnm_jpeg_decode_batch_crop(const rgbnm_jpeg_device_plan* plan, int n, int Hb, int Wb, int Hbc, int Wbc, const int32_t* boxes,
+                                 const long long* y_off, const long long* c_off, int16_t* Ypacked, size_t y_elems, int16_t* Cpacked,
+                                 size_t c_elems, int32_t* status, uint32_t* walked, void* stream) {
+  using namespace jpegdec;
+  if (!plan || !Ypacked || !Cpacked || !status || n <= 0 || Hb < 1 || Wb < 1 || Hbc < 1 || Wbc < 1 || Hb > 4096 || Wb > 4096 || Hbc > 4096 ||
+      Wbc > 4096 || plan->nruns < 0 || plan->ntables < 0)
+    return RGBNM_EINVAL;
+  if (!boxes || !y_off || !c_off || y_elems == 0 || c_elems == 0) return RGBNM_EINVAL;
+  if (((uintptr_t)Ypacked & 15) || ((uintptr_t)Cpacked & 15) || ((uintptr_t)status & 3) || ((uintptr_t)boxes & 3) || ((uintptr_t)y_off & 7) ||
+      ((uintptr_t)c_off & 7) || ((uintptr_t)walked & 3))
+    return RGBNM_EINVAL;
+  if (plan->nruns == 0) return RGBNM_OK;
+  if (!plan->stream || !plan->runs || !plan->images || !plan->tables || ((uintptr_t)plan->stream & 3) || ((uintptr_t)plan->tables & 15) ||
+      ((uintptr_t)plan->runs & 3) || ((uintptr_t)plan->images & 3))
+    return RGBNM_EINVAL;
+  CArgs a;
+  a.p = *plan;
+  a.n = n; a.Hb = Hb; a.Wb = Wb; a.Hbc = Hbc; a.Wbc = Wbc;
+  a.boxes = boxes; a.y_off = y_off; a.c_off = c_off;
+  a.Y = Ypacked; a.C = Cpacked; a.y_elems = y_elems; a.c_elems = c_elems;
+  a.status = status;
+  a.walked = walked;
+  // runs per wave: the plain launch's rule (the runs a box lets skip are not known on the host)
+  const int opt = rgbnm_get_option("jpeg_lanes");
+  int per = opt >= 1 && opt <= LANES ? opt : cdiv(plan->nruns, 2048);
+  per = per < 1 ? 1 : per > LANES ? LANES : per;
+  a.lanes = per;
+  const int groups = cdiv(plan->nruns, per);
+  decode_crop_kernel<<<groups < MAX_WGS ? groups : MAX_WGS, LANES, 0, (hipStream_t)stream>>>(a);
   LAUNCH_CHECK();
   return RGBNM_OK;
 }

@@ -90,15 +90,98 @@ __host__ __device__ inline void flush_block(int16_t* tile, const Out& g, const L
   }
 }
 
+// ---- the crop form: only a box of each image is wanted (rgbnm_jpeg_decode_batch_crop) ---------------------------------------------
+// The box is (top, left, h, w) in luma blocks, all even, inside the kept grid; the chroma box is the luma box halved.  The blocks of
+// the box go to the image's slots of two packed buffers, luma [h][w][64] and chroma [2][h/2][w/2][64]: the layout of the host
+// reader's rgbnm_read_coefficients_batch_crop.  A run starts with zero predictors at a known MCU, so a run none of whose MCUs holds
+// a block of the box is not walked at all, and any other run is walked from its first MCU (predictors and bit position cannot be
+// skipped) up to its LAST MCU, in raster order, that holds one.
+struct Crop {
+  int top, left, h, w;
+  int16_t* Y;      // the image's packed luma crop [h][w][64]
+  int16_t* C;      // its packed chroma crop [2][h/2][w/2][64]
+};
+
+// The box and the offsets of one image against the grids and the packed buffers.  They come from device arrays and are as little
+// trusted as the run records.  RGBNM_JPEG_EBOX: nothing of the image may be stored.
+__host__ __device__ inline int check_box(const int32_t* box, long long y_off, long long c_off, int Hb, int Wb, int Hbc, int Wbc,
+                                         int16_t* Ypacked, size_t y_elems, int16_t* Cpacked, size_t c_elems, Crop* B) {
+  const int t = box[0], l = box[1], h = box[2], w = box[3];
+  if (t < 0 || l < 0 || h <= 0 || w <= 0 || ((t | l | h | w) & 1) || h > Hb || w > Wb || t > Hb - h || l > Wb - w ||
+      (t + h) / 2 > Hbc || (l + w) / 2 > Wbc)
+    return RGBNM_JPEG_EBOX;
+  const uint64_t ny = (uint64_t)64 * (uint64_t)h * (uint64_t)w, nc = (uint64_t)128 * (uint64_t)(h / 2) * (uint64_t)(w / 2);
+  if (y_off < 0 || c_off < 0 || (y_off & 7) || (c_off & 7) || (uint64_t)y_off > (uint64_t)y_elems || ny > (uint64_t)y_elems - (uint64_t)y_off ||
+      (uint64_t)c_off > (uint64_t)c_elems || nc > (uint64_t)c_elems - (uint64_t)c_off)
+    return RGBNM_JPEG_EBOX;
+  B->top = t; B->left = l; B->h = h; B->w = w;
+  B->Y = Ypacked + y_off;
+  B->C = Cpacked + c_off;
+  return 0;
+}
+
+// MCUs of the run to walk: up to the last one, in raster order, that holds a block of the box of some component (the box mapped
+// through the component's hs / vs).  0: the run holds none and is skipped.
+__host__ __device__ inline uint32_t crop_mcus(const rgbnm_jpeg_run& r, const Lane& L, const Crop& B) {
+  const int end = r.mcu0 + r.nmcu - 1, mcus_x = L.mcus_x;
+  int last = -1;
+  for (int c = 0; c < L.ncomp; ++c) {
+    const int hs = (int)(L.hv >> (8 * c)) & 15, vs = (int)(L.hv >> (8 * c + 4)) & 15;
+    const int t = c ? B.top / 2 : B.top, l = c ? B.left / 2 : B.left, h = c ? B.h / 2 : B.h, w = c ? B.w / 2 : B.w;
+    // the component's MCUs, inclusive (a record whose MCU grid is narrower than the call's grids is cut to its own width)
+    const int x0 = l / hs, xe = (l + w - 1) / hs, x1 = xe < mcus_x ? xe : mcus_x - 1, y0 = t / vs, y1 = (t + h - 1) / vs;
+    int y = end / mcus_x, x = end - y * mcus_x;
+    if (y > y1) {
+      y = y1;
+      x = x1;
+    } else if (x > x1) {
+      x = x1;
+    } else if (x < x0) {
+      --y;
+      x = x1;
+    }
+    const int m = y < y0 || x0 > x1 ? -1 : y * mcus_x + x;
+    last = m > last ? m : last;
+  }
+  return last >= r.mcu0 && last <= end ? (uint32_t)(last - r.mcu0 + 1) : 0u;
+}
+
+// flush_block for the crop form: the block goes to its place in the packed crop if it lies inside its component's box.
+__host__ __device__ inline void flush_block_crop(int16_t* tile, const Crop B, const Lane& L, int blk, int mx, int my) {
+  const int desc = (int)(L.layout >> (6 * blk)) & 63, comp = desc & 3;
+  const int h = (int)(L.hv >> (8 * comp)) & 15, v = (int)(L.hv >> (8 * comp + 4)) & 15;
+  const int bt = comp ? B.top / 2 : B.top, bl = comp ? B.left / 2 : B.left, bh = comp ? B.h / 2 : B.h, bw = comp ? B.w / 2 : B.w;
+  const int x = mx * h + ((desc >> 2) & 3) - bl, y = my * v + (desc >> 4) - bt;
+  const bool ok = x >= 0 && x < bw && y >= 0 && y < bh;
+  const size_t row = comp ? (size_t)(comp - 1) * (size_t)bh + (size_t)y : (size_t)y;
+  int16_t* const py = B.Y;
+  int16_t* const pc = B.C;
+  V16* dst = reinterpret_cast<V16*>((comp && ok ? pc : py) + (ok ? (row * (size_t)bw + (size_t)x) * 64 : 0));
+  V16* t = reinterpret_cast<V16*>(tile);
+  const V16 zero = {0, 0, 0, 0};
+  for (int j = 0; j < 8; ++j) {
+    const V16 x16 = t[j];
+    if (ok) dst[j] = x16;
+    t[j] = zero;
+  }
+}
+
 // Walk one run.  tile: 64 int16 of the lane's own, 16-byte aligned, ZERO on entry and zero again on return.  tabs: the table array
 // that L.dcsel / L.acsel index.  zz: zig-zag position -> natural position.  Returns 0 or a negative RGBNM_JPEG_E* code; after an
 // error every block of the run that had not been stored is stored as zeros.
+// CROP (a compile-time choice: the plain walk carries no trace of it): only the first nwalk MCUs (crop_mcus) are walked and the
+// blocks go through flush_block_crop.  A walk that stops before the run's end has not seen the run's tail, so the two checks behind
+// the loop are not made for it; the errors it does meet are the ones the plain walk meets first, with the same codes.
+// The template is the function itself, with defaults, and not a body behind a decode_run wrapper: with the wrapper the plain kernel's
+// assembly differed in four instruction encodings and the launch time moved by 1 - 8 %; this way it is what it was without the crop form.
+template <bool CROP = false>
 __host__ __device__ inline int decode_run(const uint8_t* stream, const rgbnm_jpeg_run& r, const Lane& L, const rgbnm_jpeg_hufftab* tabs,
-                                          const uint8_t* zz, const Out& g, int16_t* tile) {
+                                          const uint8_t* zz, const Out& g, int16_t* tile, const Crop B = Crop(), uint32_t nwalk = 0u) {
   const uint32_t* words = reinterpret_cast<const uint32_t*>(stream + r.offset);
   const uint32_t nwords = (r.nbytes + 3u) >> 2, total_bits = r.nbytes * 8u;
   const int image = r.image, nblk = L.nblk, mcus_x = L.mcus_x;
-  uint32_t left = (uint32_t)r.nmcu;
+  uint32_t left = CROP ? nwalk : (uint32_t)r.nmcu;
+  const bool early = CROP && nwalk < (uint32_t)r.nmcu;
   const uint32_t maxtrips = left * (uint32_t)nblk * 64u;
   int mx = r.mcu0 % mcus_x, my = r.mcu0 / mcus_x;
   uint64_t buf = 0;
@@ -164,7 +247,8 @@ __host__ __device__ inline int decode_run(const uint8_t* stream, const rgbnm_jpe
     }
     k = wr ? kk + 1 : (rr == 15 ? k + 16 : 64);
     if (k >= 64) {                         // the block is complete
-      flush_block(tile, g, L, image, blk, mx, my);
+      if (CROP) flush_block_crop(tile, B, L, blk, mx, my);
+      else flush_block(tile, g, L, image, blk, mx, my);
       k = 0;
       if (++blk == nblk) {
         blk = 0;
@@ -176,15 +260,16 @@ __host__ __device__ inline int decode_run(const uint8_t* stream, const rgbnm_jpe
       }
     }
   }
-  if (!err && left) err = RGBNM_JPEG_EOVERRUN;
-  if (!err && total_bits - used > 8u) err = RGBNM_JPEG_ETRAILING;
-  if (err) {
+  if (!early && !err && left) err = RGBNM_JPEG_EOVERRUN;
+  if (!early && !err && total_bits - used > 8u) err = RGBNM_JPEG_ETRAILING;
+  if (err || (CROP && left)) {
     // the block under way and everything behind it: zeros (flush_block clears the tile on its first pass)
     V16* t = reinterpret_cast<V16*>(tile);
     const V16 zero = {0, 0, 0, 0};
     for (int j = 0; j < 8; ++j) t[j] = zero;
     while (left) {
-      flush_block(tile, g, L, image, blk, mx, my);
+      if (CROP) flush_block_crop(tile, B, L, blk, mx, my);
+      else flush_block(tile, g, L, image, blk, mx, my);
       if (++blk == nblk) {
         blk = 0;
         --left;
@@ -198,6 +283,13 @@ __host__ __device__ inline int decode_run(const uint8_t* stream, const rgbnm_jpe
   return err;
 }
 
+// The crop form.  nwalk: crop_mcus(r, L, B), not 0.  After an error only the blocks still owed -- those of the nwalk MCUs -- are zeroed.
+__host__ __device__ inline int decode_run_crop(const uint8_t* stream, const rgbnm_jpeg_run& r, const Lane& L, const rgbnm_jpeg_hufftab* tabs,
+                                               const uint8_t* zz, const Crop& B, uint32_t nwalk, int16_t* tile) {
+  const Out none = {0, 0, 0, 0, 0, nullptr, nullptr};
+  return decode_run<true>(stream, r, L, tabs, zz, none, tile, B, nwalk);
+}
+
 // A one-component file has no chroma to decode: its CbCr slot is zeros.  The run over MCUs [mcu0, mcu0 + nmcu) of `total` writes
 // the same share of the slot's 16-byte pieces, so that the runs of the image cover it exactly once.
 __host__ __device__ inline void zero_chroma_share(const Out& g, int image, uint32_t mcu0, uint32_t nmcu, uint32_t total) {
@@ -205,6 +297,16 @@ __host__ __device__ inline void zero_chroma_share(const Out& g, int image, uint3
   const uint64_t pieces = (uint64_t)2 * (uint64_t)g.Hbc * (uint64_t)g.Wbc * 8u;
   const uint64_t lo = pieces * mcu0 / total, hi = pieces * ((uint64_t)mcu0 + nmcu) / total;
   V16* dst = reinterpret_cast<V16*>(g.C + (size_t)image * 2 * (size_t)g.Hbc * (size_t)g.Wbc * 64);
+  const V16 zero = {0, 0, 0, 0};
+  for (uint64_t j = lo; j < hi; ++j) dst[j] = zero;
+}
+
+// The same for the packed chroma crop of a one-component file: every run of the image takes its share of the slot's pieces, whether
+// it is walked or skipped, so that they are written exactly once.
+__host__ __device__ inline void zero_chroma_share_crop(const Crop& B, uint32_t mcu0, uint32_t nmcu, uint32_t total) {
+  const uint64_t pieces = (uint64_t)2 * (uint64_t)(B.h / 2) * (uint64_t)(B.w / 2) * 8u;
+  const uint64_t lo = pieces * mcu0 / total, hi = pieces * ((uint64_t)mcu0 + nmcu) / total;
+  V16* dst = reinterpret_cast<V16*>(B.C);
   const V16 zero = {0, 0, 0, 0};
   for (uint64_t j = lo; j < hi; ++j) dst[j] = zero;
 }

@@ -333,17 +333,83 @@ def jpeg_split_scratch(plan, seg_bits=None, device="cuda"):
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
-def launch_jpeg_decode(plan, dev, out, split=False, seg_bits=None, rounds=None, path=None, scratch=None):
+def alloc_jpeg_packed(n, grid=(64, 64), device="cuda"):
+    """Device tensors for decode_jpeg_batch(boxes=..., out=...): (Ypacked, Cpacked, quant, status), the flat buffers sized for n
+    WHOLE grids (a batch of crops never needs more)."""
+    hb, wb = grid
+    kw = dict(dtype=torch.int16, device=device)
+    return (torch.empty(n * hb * wb * 64, **kw), torch.empty(n * 2 * ((hb + 1) // 2) * ((wb + 1) // 2) * 64, **kw),
+            torch.empty((n, 3, 8, 8), **kw), torch.empty(n, dtype=torch.int32, device=device))
+
+
+def _check_boxes(boxes, n, grid):
+    """boxes as an int32 CPU (n, 4) tensor; the host crop reader's ValueError for a box it would refuse."""
+    bx = torch.as_tensor(boxes).to(device="cpu", dtype=torch.int32).contiguous()
+    if tuple(bx.shape) != (n, 4):
+        raise ValueError("boxes must be (len(paths), 4)")
+    hb, wb = grid
+    if bool((bx < 0).any()) or bool((bx[:, 2:] <= 0).any()) or bool((bx & 1).any()) or bool((bx[:, 0] + bx[:, 2] > hb).any()) or \
+            bool((bx[:, 1] + bx[:, 3] > wb).any()):
+        raise ValueError("crop box outside the coefficient grid (or not even)")
+    return bx
+
+
+def launch_jpeg_decode(plan, dev, out, split=False, seg_bits=None, rounds=None, path=None, scratch=None, boxes=None, packed_out=None,
+                       walked=None):
     """The decode launch alone (no copy, no sync: capturable).  dev: upload_jpeg_plan's tensors; out: (Y, CbCr, quant,
     status) device tensors (alloc_jpeg_out); quant and status must already hold the plan's (decode_jpeg_batch copies them).
     split=True: rgbnm_jpeg_decode_batch_split instead -- long runs cut into segments of seg_bits bits, one lane each, `rounds` sync
     launches (defaults JPEG_SPLIT_SEG_BITS / JPEG_SPLIT_ROUNDS); the same bits in `out`.  path: int32 [n] device tensor that receives
     0 (no run split) / 1 (split) / 2 (split, then decoded by the one-lane walk) per file, scratch: jpeg_split_scratch's tensor; each
-    is taken from the caching allocator when None.  Returns path (None without split)."""
+    is taken from the caching allocator when None.  Returns path (None without split).
+    boxes (needs split=False): rgbnm_jpeg_decode_batch_crop instead -- only each file's crop box is walked for and stored.  boxes: int
+    (n, 4) array or tensor, (top, left, height, width) in luma blocks, all even; a CPU one is uploaded here (a copy: not capturable),
+    an int32 device tensor is used in place.  packed_out = (y_off, c_off, y_elems, c_elems): int64 [n] DEVICE tensors with the element
+    offsets of every file's crops in out[0] / out[1], which are then FLAT int16 buffers (alloc_jpeg_packed) of which the first y_elems /
+    c_elems elements may be written; None: packed_offsets(boxes), uploaded here.  walked: uint32-sized (int32) [plan.nruns] device
+    tensor that receives the MCUs each run's lane walked (0: skipped), or None.  The device checks every box and offset again: a bad one
+    gives that file the status RGBNM_JPEG_EBOX and writes nothing of it.  Returns (y_off, c_off) on the device."""
     from . import lib as L
     Y, CbCr, _, status = out
     hb, wb = plan.grid
     n = plan.n
+    if boxes is not None:
+        if split:
+            raise ValueError("boxes need split=False: the split decode's scout and sync passes must see the whole run whatever the box")
+        if seg_bits is not None or rounds is not None or path is not None or scratch is not None:
+            raise ValueError("seg_bits, rounds, path and scratch belong to split=True")
+        L.require_cuda(Y, CbCr, status, *dev[:4])
+        with torch.cuda.device(Y.device):
+            if not (torch.is_tensor(boxes) and boxes.is_cuda):
+                if packed_out is None:
+                    y_off, c_off, ny, ncc = packed_offsets(_check_boxes(boxes, n, plan.grid))
+                    packed_out = (y_off.to(Y.device, non_blocking=True), c_off.to(Y.device, non_blocking=True), ny, ncc)
+                boxes = torch.as_tensor(boxes).to(device="cpu", dtype=torch.int32).contiguous().to(Y.device, non_blocking=True)
+            elif packed_out is None:
+                raise ValueError("device boxes need packed_out=(y_off, c_off, y_elems, c_elems)")
+            y_off, c_off, ny, ncc = packed_out
+            L.require_cuda(boxes, y_off, c_off)
+            if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, 4) or not boxes.is_contiguous():
+                raise L.RgbnmError("boxes must be int32 (n, 4)")
+            if any(t.dtype != torch.int64 or t.numel() != n or not t.is_contiguous() for t in (y_off, c_off)):
+                raise L.RgbnmError("y_off and c_off must be int64 [n]")
+            if Y.dim() != 1 or CbCr.dim() != 1 or Y.dtype != torch.int16 or CbCr.dtype != torch.int16 or not Y.is_contiguous() \
+                    or not CbCr.is_contiguous() or int(ny) > Y.numel() or int(ncc) > CbCr.numel() or status.numel() != n \
+                    or status.dtype != torch.int32:
+                raise L.RgbnmError("out tensors do not match the boxes (alloc_jpeg_packed)")
+            if walked is not None:
+                L.require_cuda(walked)
+                if walked.dtype != torch.int32 or walked.numel() < plan.nruns or not walked.is_contiguous():
+                    raise L.RgbnmError("walked must be int32 [plan.nruns]")
+            dp = L.JpegDevicePlan(stream=dev[0].data_ptr(), stream_bytes=plan.stream_bytes, runs=dev[1].data_ptr(), images=dev[2].data_ptr(),
+                                  tables=dev[3].data_ptr(), nruns=plan.nruns, ntables=plan.ntables)
+            L.check(L.lib().rgbnm_jpeg_decode_batch_crop(C.byref(dp), n, hb, wb, (hb + 1) // 2, (wb + 1) // 2, boxes.data_ptr(),
+                                                         y_off.data_ptr(), c_off.data_ptr(), Y.data_ptr(), int(ny), CbCr.data_ptr(), int(ncc),
+                                                         status.data_ptr(), walked.data_ptr() if walked is not None else None, L.stream()),
+                    "jpeg_decode_batch_crop")
+        return y_off, c_off
+    if packed_out is not None or walked is not None:
+        raise ValueError("packed_out and walked belong to boxes")
     L.require_cuda(Y, CbCr, status, *dev[:4])
     if tuple(Y.shape) != (n, 1, hb, wb, 8, 8) or tuple(CbCr.shape) != (n, 2, (hb + 1) // 2, (wb + 1) // 2, 8, 8) or status.numel() != n \
             or Y.dtype != torch.int16 or CbCr.dtype != torch.int16 or status.dtype != torch.int32:
@@ -374,16 +440,37 @@ def launch_jpeg_decode(plan, dev, out, split=False, seg_bits=None, rounds=None, 
     return path
 
 
-def decode_jpeg_batch(plan, device="cuda", out=None, split=False, seg_bits=None, rounds=None, return_path=False):
+def decode_jpeg_batch(plan, device="cuda", out=None, split=False, seg_bits=None, rounds=None, return_path=False, boxes=None):
     """Device half: one H2D copy per plan buffer on the current stream, then ONE launch that walks every run with one lane (there is
     no CPU fallback).  Returns (Y, CbCr, quant, status) on the device: the int16 tensors of read_coefficients_batch, bit for bit, and
     int32 status per file -- the plan's host status, lowered to a negative code where the walk met an error in the stream (the file's
     blocks not yet written are then zeros).  Files with a negative HOST status are not written at all.  No host sync.
     split=True: the split decode instead (launch_jpeg_decode), for files without restart markers; the same four tensors, and with
-    return_path=True a fifth, the int32 path per file."""
+    return_path=True a fifth, the int32 path per file.
+    boxes (int (n, 4), luma blocks, even; needs split=False): the crop decode instead (launch_jpeg_decode) -- returns (Ypacked,
+    Cpacked, quant, status, y_off, c_off): the flat tensors of read_coefficients_batch_crop trimmed to packed_offsets(boxes)' totals,
+    y_off / c_off int64 on the device: what custom_transforms.apply_packed(..., y_off=, c_off=, grid=) takes.  out: alloc_jpeg_packed's.
+    A status of 0 then says nothing about the stream bytes behind the last MCU a file's box needed."""
     if return_path and not split:
         raise ValueError("return_path belongs to split=True")
     n = plan.n
+    if boxes is not None:
+        if split:
+            raise ValueError("boxes need split=False: the split decode's scout and sync passes must see the whole run whatever the box")
+        bx = _check_boxes(boxes, n, plan.grid)
+        y_off, c_off, ny, ncc = packed_offsets(bx)
+        if out is None:
+            out = alloc_jpeg_packed(n, plan.grid, device)
+        dev = upload_jpeg_plan(plan, out[0].device)
+        out = (out[0], out[1], out[2][:n], out[3][:n])
+        out[2].copy_(dev[4], non_blocking=True)
+        out[3].copy_(dev[5], non_blocking=True)
+        d = out[0].device
+        packed = (y_off.to(d, non_blocking=True), c_off.to(d, non_blocking=True), ny, ncc)
+        launch_jpeg_decode(plan, dev, out, boxes=bx.to(d, non_blocking=True), packed_out=packed)
+        for t in dev[:4]:
+            t.record_stream(torch.cuda.current_stream(d))
+        return out[0][:ny], out[1][:ncc], out[2], out[3], packed[0], packed[1]
     if out is None:
         out = alloc_jpeg_out(n, plan.grid, device)
     out = tuple(t[:n] for t in out)
@@ -412,6 +499,21 @@ def read_coefficients_batch_device(paths_or_bytes, grid=(64, 64), device="cuda",
         raise libjpeg_exception(f"{plan.names[i]}: device decode refused the file: {jpeg_status_text(st[i])}"
                                 f"{' (' + plan.messages[i] + ')' if plan.messages[i] else ''} ({int((st != 0).sum())} of {plan.n} files failed)")
     return Y, CbCr, quant
+
+
+def read_coefficients_batch_crop_device(paths_or_bytes, boxes, grid=(64, 64), device="cuda"):
+    """read_coefficients_batch_crop with the entropy decode on the device: (Ypacked, Cpacked, quant, y_off, c_off), all DEVICE
+    tensors.  A bad box raises the host crop reader's ValueError; a file the device cannot decode raises, naming it (synchronises to
+    read the device status)."""
+    bx = _check_boxes(boxes, len(paths_or_bytes), grid)
+    plan = prepare_jpeg_batch(paths_or_bytes, grid)
+    Yp, Cp, quant, status, y_off, c_off = decode_jpeg_batch(plan, device, boxes=bx)
+    st = status.cpu()
+    if int((st != 0).sum()):
+        i = int((st != 0).nonzero()[0])
+        raise libjpeg_exception(f"{plan.names[i]}: device decode refused the file: {jpeg_status_text(st[i])}"
+                                f"{' (' + plan.messages[i] + ')' if plan.messages[i] else ''} ({int((st != 0).sum())} of {plan.n} files failed)")
+    return Yp, Cp, quant, y_off, c_off
 
 
 # ---- pixels <-> coefficients on the device (csrc/pixel_dct.hip) --------------------------------------------------------------

@@ -126,7 +126,7 @@ JPEG_STATUS = {-10: "truncated", -11: "inconsistent marker segment", -12: "unsup
                -14: "restart markers inconsistent", -15: "plan buffers too small", -20: "unassigned Huffman code",
                -21: "coefficient index past 63", -22: "more bits consumed than the run holds",
                -23: "more than a byte of bits left over", -24: "inconsistent run record",
-               -25: "DCT coefficient out of range"}
+               -25: "DCT coefficient out of range", -26: "crop box or packed offset does not fit"}
 
 ABI_VERSION = 3      # include/rgbnm.h RGBNM_ABI_VERSION this binding was written against
 
@@ -180,6 +180,7 @@ PROTOTYPES = {
     "rgbnm_jpeg_decode_batch": (_i, [_P(JpegDevicePlan), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "rgbnm_jpeg_split_scratch_bytes": (_sz, [_sz, _i, _i]),
     "rgbnm_jpeg_decode_batch_split": (_i, [_P(JpegDevicePlan), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
+    "rgbnm_jpeg_decode_batch_crop": (_i, [_P(JpegDevicePlan), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     "rgbnm_jpeg_encode_bound": (_sz, [_i, _i, _i, _i, _i, _i]),
     "rgbnm_jpeg_encode_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _sz]),
     "rgbnm_jpeg_encode_header": (_i, [_i, _i, _i, _vp, _i, _vp, _sz]),

@@ -33,6 +33,13 @@ batches ahead, each on a stream of its own, without a host sync; the step's stre
 the same whole-grid tensors, bit for bit.  A file the device path refuses (progressive, ...) is decoded by the host reader and
 uploaded into its slot.  The device status of a batch comes back through a pinned copy and is looked at once it has arrived, a
 batch or more later; a negative one raises, naming the file.  Not combinable with crop_on_host.
+`crop_on_device=True` (with decode="device" and the train transform only): crop_on_host's idea on the device's side.  The producer
+draws the batch's boxes and augmentation parameters before it prepares the plan, the boxes travel with it, and the launch is the crop
+decode (dct_manip.launch_jpeg_decode(boxes=...)): restart runs outside a file's box are not walked, the others stop after the last MCU
+the box needs, and only the boxes are stored, packed as the host crop reader packs them; the transform reads them in place
+(apply_packed).  Same output bits as crop_on_host=True at the same seed and epoch.  A file's status then says nothing about stream
+bytes behind the last MCU its box needed.  Files without restart markers are walked by one lane each up to that MCU (jpeg_split takes
+no box: not combinable); the gain comes from restart markers.
 `jpeg_split=True` (with decode="device" only): the launch is the split decode (dct_manip.launch_jpeg_decode(split=True)): runs of
 files without restart markers are cut into bit segments, one lane each; the same tensors, bit for bit.
 
@@ -51,7 +58,8 @@ from . import dct_manip as dm
 
 class DCTBatchLoader:
     def __init__(self, paths, labels, batch_size, device="cuda", grid=(64, 64), threads=None, prefetch=2, shuffle=True,
-                 seed=0, rank=0, world_size=1, drop_last=False, transform=None, crop_on_host=False, decode="host", jpeg_split=False):
+                 seed=0, rank=0, world_size=1, drop_last=False, transform=None, crop_on_host=False, decode="host", jpeg_split=False,
+                 crop_on_device=False):
         if len(paths) != len(labels):
             raise ValueError("paths and labels differ in length")
         if batch_size <= 0 or prefetch < 1:
@@ -70,16 +78,30 @@ class DCTBatchLoader:
                                  "boxes are drawn before the decode; the eval transform reads the whole grid")
         if decode not in ("host", "device"):
             raise ValueError(f'decode must be "host" or "device", got {decode!r}')
+        self.crop_on_device = bool(crop_on_device)
+        if self.crop_on_device and self.crop_on_host:
+            raise ValueError("crop_on_device and crop_on_host are the same crop on the two sides of PCIe: choose one")
         if decode == "device" and self.crop_on_host:
             raise ValueError('decode="device" ships the compressed bytes, a tenth of the coefficients: there is nothing left to crop '
-                             "before PCIe (crop_on_host=True belongs to the host decode)")
+                             "before PCIe (crop_on_host=True belongs to the host decode; crop_on_device=True lets the device decode walk "
+                             "and store only the crop boxes)")
+        if self.crop_on_device:
+            from . import custom_transforms as CT
+            if decode != "device":
+                raise ValueError('crop_on_device=True is the crop of the DEVICE decode: it needs decode="device"')
+            if jpeg_split:
+                raise ValueError("crop_on_device=True cannot be combined with jpeg_split=True: the split decode takes no crop box (its "
+                                 "scout and sync passes must see the whole run)")
+            if not isinstance(transform, CT.TrainTransform_DCT) or transform.eval_mode or self.device.type != "cuda":
+                raise ValueError("crop_on_device needs the fused train transform (TrainTransform_DCT) and a HIP device: the crop "
+                                 "boxes are drawn before the decode; the eval transform reads the whole grid")
         if decode == "device" and self.device.type != "cuda":
             raise ValueError('decode="device" needs a HIP device')
         if jpeg_split and decode != "device":
             raise ValueError('jpeg_split=True cuts the runs of the DEVICE decode into segments: it needs decode="device"')
         self.decode, self.jpeg_split = decode, bool(jpeg_split)
         self.h2d_bytes = 0
-        self.last_packed = None        # crop_on_host: the (packed parameters, nops) of the batch yielded last (tests)
+        self.last_packed = None        # crop_on_host / crop_on_device: the (packed parameters, nops) of the batch yielded last (tests)
         self.epoch = 0
         n = len(self.paths)
         # DistributedSampler(drop_last=False): every rank gets ceil(n / world) indices, the list is padded by wrapping
@@ -147,6 +169,57 @@ class DCTBatchLoader:
             fallback.append((k, y, c, q3))
         return plan, fallback
 
+    def _prepare_crop(self, sampler, plan, fallback):
+        """crop_on_device, producer side: the batch's parameters, drawn as the crop_on_host path draws them, and what the crop launch
+        needs of them in ONE pinned tensor (boxes int32 [n, 4] | y_off int64 [n] | c_off int64 [n]).  A file the host reader decoded
+        is cut to its box here."""
+        n = plan.n
+        packed, nops = sampler.sample(n, self.grid[0], self.grid[1])
+        bx = torch.from_numpy(packed["crop"].astype("int32"))
+        y_off, c_off, ny, ncc = dm.packed_offsets(bx)
+        meta = torch.empty(4 * n, dtype=torch.int64).pin_memory()
+        meta[:2 * n].view(torch.int32).copy_(bx.reshape(-1))
+        meta[2 * n:3 * n] = y_off
+        meta[3 * n:] = c_off
+        cut = []
+        for k, y, c, q in fallback:
+            t, l, h, w = bx[k].tolist()
+            yc = y[0, t:t + h, l:l + w].contiguous().view(-1)
+            cc = None if c is None else c[:, t // 2:(t + h) // 2, l // 2:(l + w) // 2].contiguous().view(-1)
+            cut.append((k, int(y_off[k]), yc, int(c_off[k]), 2 * (h // 2) * (w // 2) * 64, cc, q))
+        return packed, nops, meta, ny, ncc, cut
+
+    def _launch_device_crop(self, plan, crop, lab, stream):
+        """Consumer side of crop_on_device: uploads and the crop launch on a side stream; nothing here waits for the device."""
+        packed, nops, meta, ny, ncc, cut = crop
+        n = plan.n
+        with torch.cuda.stream(stream):
+            dev = dm.upload_jpeg_plan(plan, self.device)
+            mdev = meta.to(self.device, non_blocking=True)
+            boxes, yo, co = mdev[:2 * n].view(torch.int32).view(n, 4), mdev[2 * n:3 * n], mdev[3 * n:]
+            Yp = torch.empty(ny, dtype=torch.int16, device=self.device)
+            Cp = torch.empty(ncc, dtype=torch.int16, device=self.device)
+            Q, st = dev[4], dev[5]
+            dm.launch_jpeg_decode(plan, dev, (Yp, Cp, Q, st), boxes=boxes, packed_out=(yo, co, ny, ncc))
+            for t in dev[:4]:
+                t.record_stream(stream)
+            for k, y0, yc, c0, csz, cc, q in cut:      # refused by prepare: the kernel leaves these slots alone
+                Yp[y0:y0 + yc.numel()].copy_(yc, non_blocking=True)
+                if cc is None:
+                    Cp[c0:c0 + csz].zero_()
+                else:
+                    Cp[c0:c0 + csz].copy_(cc, non_blocking=True)
+                Q[k].copy_(q, non_blocking=True)
+                st[k] = 0
+            ld = lab.to(self.device, non_blocking=True)
+            st_host = torch.empty(n, dtype=torch.int32, pin_memory=True)
+            st_host.copy_(st, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(stream)
+        plan.busy = done
+        self.h2d_bytes = plan.h2d_bytes() + meta.numel() * 8
+        return (Yp, Cp, Q, ld, (packed, nops, yo, co)), (done, st_host, list(plan.names))
+
     def _launch_device(self, plan, fallback, lab, stream):
         """Consumer side: uploads and the decode launch on a side stream; nothing here waits for the device."""
         with torch.cuda.stream(stream):
@@ -166,7 +239,7 @@ class DCTBatchLoader:
             done.record(stream)
         plan.busy = done
         self.h2d_bytes = plan.h2d_bytes()
-        return (Y, C, Q, ld), (done, st_host, list(plan.names))
+        return (Y, C, Q, ld, None), (done, st_host, list(plan.names))
 
     @staticmethod
     def _check_status(pending, wait):
@@ -188,7 +261,7 @@ class DCTBatchLoader:
         q = queue.Queue(maxsize=self.prefetch)
         stop = threading.Event()
         sampler = None
-        if self.crop_on_host:
+        if self.crop_on_host or self.crop_on_device:
             from . import custom_transforms as CT
             # one stream of draws per (seed, epoch, rank): the producer samples a batch's parameters before decoding it
             sampler = CT.FastParamSampler(self.transform, seed=[self.seed, self.epoch, self.rank])
@@ -200,7 +273,9 @@ class DCTBatchLoader:
                         return
                     buf = ring[k % len(ring)]
                     if self.decode == "device":
-                        item = (self._prepare_device(buf, bi), self.labels[bi])
+                        plan, fallback = self._prepare_device(buf, bi)
+                        crop = self._prepare_crop(sampler, plan, fallback) if self.crop_on_device else None
+                        item = ((plan, fallback, crop), self.labels[bi])
                     elif sampler is not None:
                         packed, nops = sampler.sample(len(bi), self.grid[0], self.grid[1])
                         Yp, Cp, Qp, yo, co = dm.read_coefficients_batch_crop([self.paths[i] for i in bi], packed["crop"],
@@ -240,20 +315,27 @@ class DCTBatchLoader:
                             break
                         if isinstance(item, BaseException):
                             raise item
-                        (plan, fallback), lab = item
+                        (plan, fallback, crop), lab = item
                         st = streams[launched % len(streams)]
                         launched += 1
-                        inflight.append((st,) + self._launch_device(plan, fallback, lab, st))
+                        inflight.append((st,) + (self._launch_device_crop(plan, crop, lab, st) if crop is not None else
+                                                 self._launch_device(plan, fallback, lab, st)))
                     if not inflight:
                         self._check_status(pending, wait=True)
                         return
-                    st, (Yd, Cd, Qd, ld), check = inflight.pop(0)
+                    st, (Yd, Cd, Qd, ld, crop), check = inflight.pop(0)
                     cur = torch.cuda.current_stream(self.device)
                     cur.wait_event(check[0])
-                    for t in (Yd, Cd, Qd, ld):
+                    for t in (Yd, Cd, Qd, ld) + (crop[2:] if crop is not None else ()):
                         t.record_stream(cur)
                     self._check_status(pending, wait=False)      # the batches before this one, as far as their status has arrived
                     pending.append(check)
+                    if crop is not None:
+                        from . import custom_transforms as CT
+                        self.last_packed = crop[:2]
+                        yield tuple(CT.apply_packed(self.transform, Yd, Cd, Qd, crop[0], crop[1], y_off=crop[2], c_off=crop[3],
+                                                    grid=self.grid)), ld
+                        continue
                     yield self._finish(Yd, Cd, Qd, ld)
             while True:
                 item = q.get()

@@ -17,10 +17,19 @@ tests/test_loader_gpu.py makes them (16 x 16 random colours upsampled bicubic, p
       MCU row, beside --decode host at 16 threads and plain --decode device; each a process of its own per round.
   (s) and (p) go to profiles/jpeg_split.json, (a) - (c) to profiles/jpeg_decode.json.
 
+  (x) the CROP decode launch (dct_manip.launch_jpeg_decode(boxes=...): runs outside an image's crop box are skipped, the others stop
+      after the last MCU the box needs, only the boxes are stored) beside the plain whole-grid launch on the same plans in the same
+      interleaved rounds: no restart markers, one per MCU row, one per 4 MCUs.  The boxes are FastParamSampler's at the defaults of
+      TrainTransform_DCT; reported with the time: the mean share of MCUs walked (from the launch's `walked` array), the share of runs
+      skipped, the bytes written, and the crop launch with one run per wave ("jpeg_lanes" = 1).
+  (y) tools/pipeline_bench.py images/s with --decode device --crop-on-device beside plain --decode device, on the marker-less files
+      and on those with a marker per MCU row; each a process of its own per round.
+  (x) and (y) go to profiles/jpeg_crop.json.
+
 Protocol of the other step tools: warm-up, then ROUNDS interleaved rounds (order reversed every other round); median and min - max.
-Writes profiles/jpeg_decode.json, or profiles/jpeg_split.json for parts s / p (parts given with --parts are replaced, the others
-kept), and prints it.
-usage: python tools/jpeg_decode_step.py [--parts a,b,c | s,p] [--rounds 6] [--batch 256]"""
+Writes profiles/jpeg_decode.json, or profiles/jpeg_split.json for parts s / p, or profiles/jpeg_crop.json for parts x / y (parts
+given with --parts are replaced, the others kept), and prints it.
+usage: python tools/jpeg_decode_step.py [--parts a,b,c | s,p | x,y] [--rounds 6] [--batch 256]"""
 import argparse
 import io
 import json
@@ -164,12 +173,75 @@ def part_s(B, rounds, iters, warmup, sets):
     return out
 
 
+CROP_SETS = ("q90", "q90_rst_row", "q90_rst_4mcu")
+
+
+def part_x(B, rounds, iters, warmup):
+    from rgb_no_more_amd import custom_transforms as CT
+    dev = torch.device("cuda", 0)
+    packed, _ = CT.FastParamSampler(CT.TrainTransform_DCT(out_dtype=torch.bfloat16), seed=1234).sample(B, 64, 64)
+    boxes = torch.from_numpy(packed["crop"].astype("int32"))
+    y_off, c_off, ny, ncc = DM.packed_offsets(boxes)
+    bdev, yo, co = boxes.to(dev), y_off.to(dev), c_off.to(dev)
+    fns, meta, keep = {}, {}, []
+    for name in CROP_SETS:
+        files = synth(64, **SETS[name])
+        batch = [files[i % 64] for i in range(B)]
+        plan = DM.prepare_jpeg_batch(batch, grid=(64, 64))
+        assert plan.nbad == 0
+        up = DM.upload_jpeg_plan(plan, dev)
+        out = DM.alloc_jpeg_out(B, (64, 64), dev)
+        out[2].copy_(up[4])
+        out[3].copy_(up[5])
+        DM.launch_jpeg_decode(plan, up, out)
+        pk = (torch.full((ny,), 0x5555, dtype=torch.int16, device=dev), torch.full((ncc,), 0x5555, dtype=torch.int16, device=dev),
+              out[2].clone(), up[5].clone())
+        walked = torch.full((plan.nruns,), -1, dtype=torch.int32, device=dev)
+        DM.launch_jpeg_decode(plan, up, pk, boxes=bdev, packed_out=(yo, co, ny, ncc), walked=walked)
+        torch.cuda.synchronize()
+        # the bits that are timed: the boxes cut out of the whole-grid launch's output
+        for i in range(B):
+            t, l, h, w = boxes[i].tolist()
+            assert torch.equal(pk[0][int(y_off[i]):int(y_off[i]) + h * w * 64], out[0][i, 0, t:t + h, l:l + w].reshape(-1)), (name, i)
+            assert torch.equal(pk[1][int(c_off[i]):int(c_off[i]) + h * w * 32],
+                               out[1][i, :, t // 2:(t + h) // 2, l // 2:(l + w) // 2].reshape(-1)), (name, i)
+        assert int(pk[3].min()) == 0 and int(out[3].min()) == 0
+        nmcu = plan.runs[:plan.nruns, 4].to(torch.int64)
+        wk = walked.cpu().to(torch.int64)
+        assert bool((wk >= 0).all()) and bool((wk <= nmcu).all())
+        keep.append((plan, up, out, pk, walked))
+        fns[name] = lambda plan=plan, up=up, out=out: DM.launch_jpeg_decode(plan, up, out)
+        meta[name] = {"runs": plan.nruns, "bytes_written": 2 * (out[0].numel() + out[1].numel())}
+        crop = lambda plan=plan, up=up, pk=pk: DM.launch_jpeg_decode(plan, up, pk, boxes=bdev, packed_out=(yo, co, ny, ncc))  # noqa: E731
+        cm = {"runs": plan.nruns, "bytes_written": 2 * (ny + ncc), "walked_share_of_mcus": float(wk.sum()) / float(nmcu.sum()),
+              "runs_skipped_share": float((wk == 0).sum()) / plan.nruns,
+              "runs_stopped_early_share": float(((wk > 0) & (wk < nmcu)).sum()) / plan.nruns,
+              "box_share_of_grid": ny / (B * 64 * 64 * 64)}
+        fns[name + "_crop"] = crop
+        meta[name + "_crop"] = cm
+        fns[name + "_crop_1_per_wave"] = crop
+        meta[name + "_crop_1_per_wave"] = dict(cm, runs_per_wave=1)
+    out = summary(timed(list(fns), fns, warmup, rounds, iters,
+                        before=lambda cfg: L.set_option("jpeg_lanes", 1 if cfg.endswith("_1_per_wave") else 0)))
+    L.set_option("jpeg_lanes", 0)
+    for k, v in out.items():
+        v.update(meta[k])
+        v["images_per_s"] = B / v["ms_median"] * 1e3
+        print(f"(x) {k}: {v['ms_median']:.3f} ms ({v['ms_min']:.3f} - {v['ms_max']:.3f}) per batch, {v['bytes_written'] / 1e6:.1f} MB written, "
+              f"walked share {v.get('walked_share_of_mcus')}", file=sys.stderr)
+    return out
+
+
 PIPELINE = {"host_16_threads": ["--decode", "host", "--threads", "16"],
             "device": ["--decode", "device", "--threads", "16", "--prefetch", "4"],
             "device_rst_row": ["--decode", "device", "--threads", "16", "--prefetch", "4", "--restart-rows", "1"]}
 PIPELINE_SPLIT = {"host_16_threads": PIPELINE["host_16_threads"], "device": PIPELINE["device"],
                   "device_split": PIPELINE["device"] + ["--jpeg-split"], "device_rst_row": PIPELINE["device_rst_row"],
                   "device_rst_row_split": PIPELINE["device_rst_row"] + ["--jpeg-split"]}
+
+
+PIPELINE_CROP = {"device": PIPELINE["device"], "device_crop": PIPELINE["device"] + ["--crop-on-device"],
+                 "device_rst_row": PIPELINE["device_rst_row"], "device_rst_row_crop": PIPELINE["device_rst_row"] + ["--crop-on-device"]}
 
 
 def part_c(B, rounds, steps, warmup, cfgs=PIPELINE):
@@ -203,10 +275,11 @@ def main():
     ap.add_argument("--out", default=None, help="default: profiles/jpeg_split.json for parts s / p, else profiles/jpeg_decode.json")
     a = ap.parse_args()
     parts = a.parts.split(",")
-    if bool(set(parts) & {"s", "p"}) and bool(set(parts) & {"a", "b", "c"}):
-        raise SystemExit("parts s / p and a / b / c write different files: run them separately")
+    groups = [g for g in ({"a", "b", "c"}, {"s", "p"}, {"x", "y"}) if set(parts) & g]
+    if len(groups) != 1:
+        raise SystemExit("parts a / b / c, s / p and x / y write different files: run them separately")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "jpeg_split.json" if set(parts) & {"s", "p"} else "jpeg_decode.json")
+        a.out = os.path.join(ROOT, "profiles", {"a": "jpeg_decode.json", "s": "jpeg_split.json", "x": "jpeg_crop.json"}[min(groups[0])])
     assert torch.cuda.is_available(), "needs the GPU"
     torch.cuda.set_device(0)
     res = {}
@@ -227,6 +300,10 @@ def main():
     if "p" in parts:
         res["p_pipeline"] = part_c(a.batch, a.rounds, a.steps, 8, PIPELINE_SPLIT)
         res["split_defaults"] = {"seg_bits": DM.JPEG_SPLIT_SEG_BITS, "rounds": DM.JPEG_SPLIT_ROUNDS, "min_seg": 16}
+    if "x" in parts:
+        res["x_crop_launch"] = part_x(a.batch, a.rounds, a.iters, a.warmup)
+    if "y" in parts:
+        res["y_pipeline"] = part_c(a.batch, a.rounds, a.steps, 8, PIPELINE_CROP)
     line = json.dumps(res)
     with open(a.out, "w") as fh:
         fh.write(line + "\n")

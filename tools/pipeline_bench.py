@@ -50,9 +50,14 @@ def main():
     ap.add_argument("--prefetch", type=int, default=2, help="batches the loader keeps ahead of the step")
     ap.add_argument("--jpeg-split", action="store_true",
                     help="with --decode device: long runs are cut into bit segments, one lane each (loader jpeg_split)")
+    ap.add_argument("--crop-on-device", action="store_true",
+                    help="with --decode device: the decode walks and stores only each image's crop box (loader crop_on_device)")
     a = ap.parse_args()
     if a.decode == "device":
         a.crop_on_host = 0
+    if a.crop_on_device and a.decode != "device":
+        ap.error("--crop-on-device needs --decode device")
+    fused = bool(a.crop_on_host or a.crop_on_device)         # the loader draws the parameters and applies the transform itself
     dev = "cuda:0"
     torch.cuda.set_device(0)
     tmp = tempfile.mkdtemp(prefix="sjpeg_")
@@ -88,13 +93,13 @@ def main():
     nb = a.warmup + a.steps + 4
     loader = DCTBatchLoader([batch_paths[i % B] for i in range(nb * B)], [int(v) for v in torch.randint(0, 999, (nb * B,))], B,
                             device=dev, threads=a.threads, prefetch=a.prefetch, shuffle=False,
-                            transform=aug if a.crop_on_host else None, crop_on_host=bool(a.crop_on_host), decode=a.decode,
-                            jpeg_split=a.jpeg_split)
+                            transform=aug if fused else None, crop_on_host=bool(a.crop_on_host), decode=a.decode,
+                            jpeg_split=a.jpeg_split, crop_on_device=a.crop_on_device)
     it = iter(loader)
 
     def step():
         opt.zero_grad(set_to_none=True)
-        if a.crop_on_host:
+        if fused:
             (y, c), labd = next(it)
         else:
             (Yd, Cd, Qd), labd = next(it)
@@ -124,7 +129,7 @@ def main():
            "ms_per_step": round(1e3 * dt / a.steps, 3), "per_gpu_batch": B, "host_threads": a.threads,
            "host_decode_only_images_per_sec": round(dec, 1), "avg_jpeg_bytes": round(fsize),
            "h2d_bytes_per_image": round(h2d),
-           "crop_on_host": bool(a.crop_on_host),
+           "crop_on_host": bool(a.crop_on_host), "crop_on_device": bool(a.crop_on_device),
            "loss": round(float(loss.item()), 4),
            "note": "one process; decoder thread (pthread pool inside librgbnm_reader.so, GIL released) runs two batches "
                    "ahead; bounded by the host Huffman decode when value ~ host_decode_only"}
