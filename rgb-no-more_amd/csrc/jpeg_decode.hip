@@ -1,8 +1,9 @@
 // Entropy decoding of baseline JPEG files on the device (include/rgbnm.h: rgbnm_jpeg_prepare, rgbnm_jpeg_decode_batch).
 //
 // The host finds the independent bit streams ("runs": the scan, or one per restart interval) -- jpeg_scan.h, a byte scan -- and the
-// kernel below walks them, ONE LANE PER RUN, grid-strided over the run records (1 to 64 runs per wave, see the launch).  The walk
-// itself is jpeg_walk.h, shared with the stand-alone host check.  What this file adds is the wave's side of it:
+// kernel below walks them, ONE LANE PER RUN, grid-strided over the run records (1 to 64 runs per wave, see lanes_per_wave).  The walk
+// itself is jpeg_walk.h, shared with the stand-alone host checks.  What this file adds is the wave's side of it: wave_tile opens
+// the three wave kernels, stage_tables stages the tables for the split passes (the one-lane kernels keep that text written out).
 //   - workgroup = one wave of 64 lanes; each lane owns a 128-byte block tile in LDS (pitch 144 bytes, so that the 16-byte moves stay
 //     aligned and neighbouring lanes start 36 banks apart).  The walk scatters 2-byte coefficients into the tile; a finished block
 //     leaves as eight 16-byte stores -- whole 128-byte lines, zeros included, so no fill launch precedes the kernel -- and the tile
@@ -29,6 +30,45 @@ constexpr int TAB_PIECES = (int)(sizeof(rgbnm_jpeg_hufftab) / 16);
 
 __device__ const uint8_t d_zigzag[64] = {JPEGSCAN_ZIGZAG_VALUES};
 
+// A wave kernel's opening: the lane's tile inside s_tile (LANES * PITCH bytes), zeroed, and the zig-zag table in s_zz, behind a
+// barrier.  TILE = false (the split passes that store nothing): neither is set up and every lane gets s_tile itself.
+template <bool TILE = true>
+__device__ __forceinline__ int16_t* wave_tile(uint8_t* s_tile, uint8_t* s_zz) {
+  const int lane = threadIdx.x;
+  int16_t* tile = reinterpret_cast<int16_t*>(s_tile + (TILE ? lane * PITCH : 0));
+  if (TILE) {
+    s_zz[lane] = d_zigzag[lane];
+    jpegwalk::zero_tile(tile);
+  }
+  __syncthreads();
+  return tile;
+}
+
+// One table set for the live lanes of the wave?  Then their six tables go to s_tab (SLOTS entries) between two barriers and the
+// result is true: those lanes walk with staged(L) behind s_tab.  Every lane of the wave calls this, live or not.
+__device__ __forceinline__ bool stage_tables(bool live, const jpegwalk::Lane& L, const rgbnm_jpeg_hufftab* tables, rgbnm_jpeg_hufftab* s_tab) {
+  using jpegwalk::V16;
+  const unsigned long long mask = __ballot(live);
+  if (mask == 0) return false;
+  const int lane = threadIdx.x, first = __ffsll((long long)mask) - 1;
+  const uint64_t dc0 = __shfl((unsigned long long)L.dcsel, first, LANES), ac0 = __shfl((unsigned long long)L.acsel, first, LANES);
+  if (!__all(!live || (L.dcsel == dc0 && L.acsel == ac0))) return false;
+  __syncthreads();                         // the previous round's readers of s_tab are done
+  for (int j = lane; j < SLOTS * TAB_PIECES; j += LANES) {
+    const int slot = j / TAB_PIECES, piece = j - slot * TAB_PIECES;
+    const uint32_t t = (uint32_t)(((slot & 1) ? ac0 : dc0) >> (16 * (slot >> 1))) & 0xFFFFu;   // < ntables: check_run
+    reinterpret_cast<V16*>(&s_tab[slot])[piece] = reinterpret_cast<const V16*>(&tables[t])[piece];
+  }
+  __syncthreads();
+  return true;
+}
+// the lane record whose table indices are the staged slots
+__device__ __forceinline__ jpegwalk::Lane staged(jpegwalk::Lane L) {
+  L.dcsel = 0ull | (2ull << 16) | (4ull << 32);
+  L.acsel = 1ull | (3ull << 16) | (5ull << 32);
+  return L;
+}
+
 struct Args {
   rgbnm_jpeg_device_plan p;
   jpegwalk::Out g;
@@ -46,14 +86,7 @@ __global__ __launch_bounds__(LANES) void decode_kernel(Args a) {
   __shared__ alignas(16) rgbnm_jpeg_hufftab s_tab[SLOTS];
   __shared__ uint8_t s_zz[64];
   const int lane = threadIdx.x;
-  int16_t* tile = reinterpret_cast<int16_t*>(s_tile + lane * PITCH);
-  s_zz[lane] = d_zigzag[lane];
-  {
-    V16* t = reinterpret_cast<V16*>(tile);
-    const V16 zero = {0, 0, 0, 0};
-    for (int j = 0; j < 8; ++j) t[j] = zero;
-  }
-  __syncthreads();
+  int16_t* tile = wave_tile(s_tile, s_zz);
   const int nruns = a.p.nruns, per = a.lanes;
   for (long long base = (long long)blockIdx.x * per; base < nruns; base += (long long)gridDim.x * per) {
     const int ri = (int)base + lane;
@@ -71,13 +104,15 @@ __global__ __launch_bounds__(LANES) void decode_kernel(Args a) {
         live = false;
       }
     }
-    // one table set for the whole wave?
+    // One table set for the whole wave?  Written out, not stage_tables: with the helper the launches on files with a restart marker
+    // per MCU row measured 1 - 3 % slower (crop: more), against a run-to-run disagreement below 1 %.  Two calls of the walk, not one
+    // behind `shared ? s_tab : tables`: that pointer would lose its address space and every table read become a flat load.
+    int err = 0;
     const unsigned long long mask = __ballot(live);
     if (mask == 0) continue;
     const int first = __ffsll((long long)mask) - 1;
     const uint64_t dc0 = __shfl((unsigned long long)L.dcsel, first, LANES), ac0 = __shfl((unsigned long long)L.acsel, first, LANES);
     const bool shared = __all(!live || (L.dcsel == dc0 && L.acsel == ac0));
-    int err = 0;
     if (shared) {
       __syncthreads();                     // the previous round's readers of s_tab are done
       for (int j = lane; j < SLOTS * TAB_PIECES; j += LANES) {
@@ -86,12 +121,7 @@ __global__ __launch_bounds__(LANES) void decode_kernel(Args a) {
         reinterpret_cast<V16*>(&s_tab[slot])[piece] = reinterpret_cast<const V16*>(&a.p.tables[t])[piece];
       }
       __syncthreads();
-      if (live) {
-        Lane S = L;
-        S.dcsel = 0ull | (2ull << 16) | (4ull << 32);
-        S.acsel = 1ull | (3ull << 16) | (5ull << 32);
-        err = decode_run(a.p.stream, r, S, s_tab, s_zz, a.g, tile);
-      }
+      if (live) err = decode_run(a.p.stream, r, staged(L), s_tab, s_zz, a.g, tile);
     } else if (live) {
       err = decode_run(a.p.stream, r, L, a.p.tables, s_zz, a.g, tile);
     }
@@ -126,14 +156,7 @@ __global__ __launch_bounds__(LANES) void decode_crop_kernel(CArgs a) {
   __shared__ alignas(16) rgbnm_jpeg_hufftab s_tab[SLOTS];
   __shared__ uint8_t s_zz[64];
   const int lane = threadIdx.x;
-  int16_t* tile = reinterpret_cast<int16_t*>(s_tile + lane * PITCH);
-  s_zz[lane] = d_zigzag[lane];
-  {
-    V16* t = reinterpret_cast<V16*>(tile);
-    const V16 zero = {0, 0, 0, 0};
-    for (int j = 0; j < 8; ++j) t[j] = zero;
-  }
-  __syncthreads();
+  int16_t* tile = wave_tile(s_tile, s_zz);
   const int nruns = a.p.nruns, per = a.lanes;
   for (long long base = (long long)blockIdx.x * per; base < nruns; base += (long long)gridDim.x * per) {
     const int ri = (int)base + lane;
@@ -159,9 +182,8 @@ __global__ __launch_bounds__(LANES) void decode_crop_kernel(CArgs a) {
       }
     }
     const bool live = nwalk != 0;          // only these lanes walk
-    // one table set for the walking lanes of the wave?
+    int err = 0;                           // staging written out and two calls of the walk: as in decode_kernel
     const unsigned long long mask = __ballot(live);
-    int err = 0;
     if (mask != 0) {
       const int first = __ffsll((long long)mask) - 1;
       const uint64_t dc0 = __shfl((unsigned long long)L.dcsel, first, LANES), ac0 = __shfl((unsigned long long)L.acsel, first, LANES);
@@ -174,12 +196,7 @@ __global__ __launch_bounds__(LANES) void decode_crop_kernel(CArgs a) {
           reinterpret_cast<V16*>(&s_tab[slot])[piece] = reinterpret_cast<const V16*>(&a.p.tables[t])[piece];
         }
         __syncthreads();
-        if (live) {
-          Lane S = L;
-          S.dcsel = 0ull | (2ull << 16) | (4ull << 32);
-          S.acsel = 1ull | (3ull << 16) | (5ull << 32);
-          err = decode_run_crop(a.p.stream, r, S, s_tab, s_zz, B, nwalk, tile);
-        }
+        if (live) err = decode_run_crop(a.p.stream, r, staged(L), s_tab, s_zz, B, nwalk, tile);
       } else if (live) {
         err = decode_run_crop(a.p.stream, r, L, a.p.tables, s_zz, B, nwalk, tile);
       }
@@ -231,7 +248,7 @@ __global__ __launch_bounds__(LANES) void split_map_kernel(SArgs a) {
 }
 
 // MODE 0 scout, 1 sync, 2 write.  Workgroup = one wave; lanes = consecutive slots, so normally consecutive segments of one run, and
-// the tables are staged in LDS when every live lane of the wave uses the same six, as in decode_kernel.
+// the tables are staged as in decode_kernel; the walks here are one call each behind a generic table pointer.
 template <int MODE>
 __global__ __launch_bounds__(LANES) void split_seg_kernel(SArgs a) {
   using namespace jpegsplit;
@@ -239,14 +256,7 @@ __global__ __launch_bounds__(LANES) void split_seg_kernel(SArgs a) {
   __shared__ alignas(16) rgbnm_jpeg_hufftab s_tab[SLOTS];
   __shared__ uint8_t s_zz[64];
   const int lane = threadIdx.x;
-  int16_t* tile = reinterpret_cast<int16_t*>(s_tile + (MODE == 2 ? lane * PITCH : 0));
-  if (MODE == 2) {
-    s_zz[lane] = d_zigzag[lane];
-    V16* t = reinterpret_cast<V16*>(tile);
-    const V16 zero = {0, 0, 0, 0};
-    for (int j = 0; j < 8; ++j) t[j] = zero;
-  }
-  __syncthreads();
+  int16_t* tile = wave_tile<MODE == 2>(s_tile, s_zz);
   const uint32_t nslots = a.s.nslots;
   const int per = a.lanes, nxt = a.cur ^ 1;
   for (long long base = (long long)blockIdx.x * per; base < (long long)nslots; base += (long long)gridDim.x * per) {
@@ -285,24 +295,11 @@ __global__ __launch_bounds__(LANES) void split_seg_kernel(SArgs a) {
       live = a.path[r.image] == 1;
       state = a.s.entry[slot];
     }
-    const unsigned long long mask = __ballot(live);
-    if (mask == 0) continue;
-    const int first = __ffsll((long long)mask) - 1;
-    const uint64_t dc0 = __shfl((unsigned long long)L.dcsel, first, LANES), ac0 = __shfl((unsigned long long)L.acsel, first, LANES);
-    const bool shared = __all(!live || (L.dcsel == dc0 && L.acsel == ac0));
     const rgbnm_jpeg_hufftab* tabs = a.p.tables;
     Lane S = L;
-    if (shared) {
-      __syncthreads();                     // the previous round's readers of s_tab are done
-      for (int q = lane; q < SLOTS * TAB_PIECES; q += LANES) {
-        const int slot_t = q / TAB_PIECES, piece = q - slot_t * TAB_PIECES;
-        const uint32_t t = (uint32_t)(((slot_t & 1) ? ac0 : dc0) >> (16 * (slot_t >> 1))) & 0xFFFFu;   // < ntables: check_run
-        reinterpret_cast<V16*>(&s_tab[slot_t])[piece] = reinterpret_cast<const V16*>(&a.p.tables[t])[piece];
-      }
-      __syncthreads();
-      S.dcsel = 0ull | (2ull << 16) | (4ull << 32);
-      S.acsel = 1ull | (3ull << 16) | (5ull << 32);
+    if (stage_tables(live, L, a.p.tables, s_tab)) {
       tabs = s_tab;
+      S = staged(L);
     }
     if (!live) continue;
     const uint32_t end = seg_end(r, j, a.seg_bits);
@@ -371,6 +368,32 @@ __global__ __launch_bounds__(LANES) void split_verify_kernel(SArgs a) {
   }
 }
 
+// ---- the host side of the three entries -----------------------------------------------------------------------------------------------
+// What all three refuse: the plan, n, the grids, the outputs and the status and their alignment, and the plan's buffers where it has runs.
+static bool bad_call(const rgbnm_jpeg_device_plan* plan, int n, int Hb, int Wb, int Hbc, int Wbc, const void* Y, const void* C, const void* status) {
+  if (!plan || !Y || !C || !status || n <= 0 || Hb < 1 || Wb < 1 || Hbc < 1 || Wbc < 1 || Hb > 4096 || Wb > 4096 || Hbc > 4096 ||
+      Wbc > 4096 || plan->nruns < 0 || plan->ntables < 0)
+    return true;
+  if (((uintptr_t)Y & 15) || ((uintptr_t)C & 15) || ((uintptr_t)status & 3)) return true;
+  return plan->nruns && (!plan->stream || !plan->runs || !plan->images || !plan->tables || ((uintptr_t)plan->stream & 3) ||
+                         ((uintptr_t)plan->tables & 15) || ((uintptr_t)plan->runs & 3) || ((uintptr_t)plan->images & 3));
+}
+
+// Runs (or segments) per wave.  What is rare for a lane -- a code longer than 9 bits, a refill, the end of a block -- happens in almost
+// every trip of a wave whose 64 lanes all walk, and the wave pays for each.  A batch rarely has runs for every SIMD of the device
+// (256 without restart markers, 8192 with one per MCU row), so the items are spread over about 2048 waves first and the waves fill
+// up only beyond that.  Option "jpeg_lanes" (1..64) fixes the number instead.  (The runs a crop box lets skip are not known here.)
+static int lanes_per_wave(long long items) {
+  const int opt = rgbnm_get_option("jpeg_lanes");
+  const long long per = opt >= 1 && opt <= LANES ? opt : cdivl(items, 2048);
+  return (int)(per < 1 ? 1 : per > LANES ? LANES : per);
+}
+
+static jpegwalk::Out out_of(int n, int Hb, int Wb, int Hbc, int Wbc, int16_t* Y, int16_t* C) {
+  const jpegwalk::Out g = {n, Hb, Wb, Hbc, Wbc, Y, C};
+  return g;
+}
+
 }  // namespace jpegdec
 
 extern "C" {
@@ -382,29 +405,16 @@ int rgbnm_jpeg_prepare(const uint8_t* const* bufs, const size_t* lens, int n, in
 int rgbnm_jpeg_decode_batch(const rgbnm_jpeg_device_plan* plan, int n, int Hb, int Wb, int Hbc, int Wbc, int16_t* Y, int16_t* CbCr,
                             int32_t* status, void* stream) {
   using namespace jpegdec;
-  if (!plan || !Y || !CbCr || !status || n <= 0 || Hb < 1 || Wb < 1 || Hbc < 1 || Wbc < 1 || Hb > 4096 || Wb > 4096 || Hbc > 4096 ||
-      Wbc > 4096 || plan->nruns < 0 || plan->ntables < 0)
-    return RGBNM_EINVAL;
-  if (((uintptr_t)Y & 15) || ((uintptr_t)CbCr & 15) || ((uintptr_t)status & 3)) return RGBNM_EINVAL;
+  if (bad_call(plan, n, Hb, Wb, Hbc, Wbc, Y, CbCr, status)) return RGBNM_EINVAL;
   if (plan->nruns == 0) return RGBNM_OK;
-  if (!plan->stream || !plan->runs || !plan->images || !plan->tables || ((uintptr_t)plan->stream & 3) || ((uintptr_t)plan->tables & 15) ||
-      ((uintptr_t)plan->runs & 3) || ((uintptr_t)plan->images & 3))
-    return RGBNM_EINVAL;
   Args a;
   a.p = *plan;
-  a.g.n = n; a.g.Hb = Hb; a.g.Wb = Wb; a.g.Hbc = Hbc; a.g.Wbc = Wbc; a.g.Y = Y; a.g.C = CbCr;
+  a.g = out_of(n, Hb, Wb, Hbc, Wbc, Y, CbCr);
   a.status = status;
   a.info = nullptr;
   a.path = nullptr;
-  // Runs per wave.  What is rare for a lane -- a code longer than 9 bits, a refill, the end of a block -- happens in almost every
-  // trip of a wave whose 64 lanes all walk, and the wave pays for each.  A batch rarely has runs for every SIMD of the device
-  // (256 without restart markers, 8192 with one per MCU row), so the runs are spread over about 2048 waves first and the waves fill
-  // up only beyond that.  Option "jpeg_lanes" (1..64) fixes the number instead.
-  const int opt = rgbnm_get_option("jpeg_lanes");
-  int per = opt >= 1 && opt <= LANES ? opt : cdiv(plan->nruns, 2048);
-  per = per < 1 ? 1 : per > LANES ? LANES : per;
-  a.lanes = per;
-  const int groups = cdiv(plan->nruns, per);
+  a.lanes = lanes_per_wave(plan->nruns);
+  const int groups = cdiv(plan->nruns, a.lanes);
   decode_kernel<<<groups < MAX_WGS ? groups : MAX_WGS, LANES, 0, (hipStream_t)stream>>>(a);
   LAUNCH_CHECK();
   return RGBNM_OK;
@@ -414,17 +424,10 @@ int rgbnm_jpeg_decode_batch_crop(const rgbnm_jpeg_device_plan* plan, int n, int 
                                  const long long* y_off, const long long* c_off, int16_t* Ypacked, size_t y_elems, int16_t* Cpacked,
                                  size_t c_elems, int32_t* status, uint32_t* walked, void* stream) {
   using namespace jpegdec;
-  if (!plan || !Ypacked || !Cpacked || !status || n <= 0 || Hb < 1 || Wb < 1 || Hbc < 1 || Wbc < 1 || Hb > 4096 || Wb > 4096 || Hbc > 4096 ||
-      Wbc > 4096 || plan->nruns < 0 || plan->ntables < 0)
-    return RGBNM_EINVAL;
+  if (bad_call(plan, n, Hb, Wb, Hbc, Wbc, Ypacked, Cpacked, status)) return RGBNM_EINVAL;
   if (!boxes || !y_off || !c_off || y_elems == 0 || c_elems == 0) return RGBNM_EINVAL;
-  if (((uintptr_t)Ypacked & 15) || ((uintptr_t)Cpacked & 15) || ((uintptr_t)status & 3) || ((uintptr_t)boxes & 3) || ((uintptr_t)y_off & 7) ||
-      ((uintptr_t)c_off & 7) || ((uintptr_t)walked & 3))
-    return RGBNM_EINVAL;
+  if (((uintptr_t)boxes & 3) || ((uintptr_t)y_off & 7) || ((uintptr_t)c_off & 7) || ((uintptr_t)walked & 3)) return RGBNM_EINVAL;
   if (plan->nruns == 0) return RGBNM_OK;
-  if (!plan->stream || !plan->runs || !plan->images || !plan->tables || ((uintptr_t)plan->stream & 3) || ((uintptr_t)plan->tables & 15) ||
-      ((uintptr_t)plan->runs & 3) || ((uintptr_t)plan->images & 3))
-    return RGBNM_EINVAL;
   CArgs a;
   a.p = *plan;
   a.n = n; a.Hb = Hb; a.Wb = Wb; a.Hbc = Hbc; a.Wbc = Wbc;
@@ -432,12 +435,8 @@ int rgbnm_jpeg_decode_batch_crop(const rgbnm_jpeg_device_plan* plan, int n, int 
   a.Y = Ypacked; a.C = Cpacked; a.y_elems = y_elems; a.c_elems = c_elems;
   a.status = status;
   a.walked = walked;
-  // runs per wave: the plain launch's rule (the runs a box lets skip are not known on the host)
-  const int opt = rgbnm_get_option("jpeg_lanes");
-  int per = opt >= 1 && opt <= LANES ? opt : cdiv(plan->nruns, 2048);
-  per = per < 1 ? 1 : per > LANES ? LANES : per;
-  a.lanes = per;
-  const int groups = cdiv(plan->nruns, per);
+  a.lanes = lanes_per_wave(plan->nruns);
+  const int groups = cdiv(plan->nruns, a.lanes);
   decode_crop_kernel<<<groups < MAX_WGS ? groups : MAX_WGS, LANES, 0, (hipStream_t)stream>>>(a);
   LAUNCH_CHECK();
   return RGBNM_OK;
@@ -451,21 +450,14 @@ int rgbnm_jpeg_decode_batch_split(const rgbnm_jpeg_device_plan* plan, int n, int
                                   int32_t* status, int32_t* path, void* scratch, size_t scratch_bytes, int seg_bits, int rounds,
                                   void* stream) {
   using namespace jpegdec;
-  if (!plan || !Y || !CbCr || !status || !path || n <= 0 || Hb < 1 || Wb < 1 || Hbc < 1 || Wbc < 1 || Hb > 4096 || Wb > 4096 ||
-      Hbc > 4096 || Wbc > 4096 || plan->nruns < 0 || plan->ntables < 0)
-    return RGBNM_EINVAL;
-  if (((uintptr_t)Y & 15) || ((uintptr_t)CbCr & 15) || ((uintptr_t)status & 3) || ((uintptr_t)path & 3)) return RGBNM_EINVAL;
-  if (rounds < 0 || rounds > jpegsplit::ROUNDS_MAX) return RGBNM_EINVAL;
+  if (bad_call(plan, n, Hb, Wb, Hbc, Wbc, Y, CbCr, status)) return RGBNM_EINVAL;
+  if (!path || ((uintptr_t)path & 3) || rounds < 0 || rounds > jpegsplit::ROUNDS_MAX) return RGBNM_EINVAL;
   const size_t need = jpegsplit::scratch_bytes(plan->stream_bytes, plan->nruns, seg_bits);   // 0: seg_bits out of range
   if (need == 0 || !scratch || ((uintptr_t)scratch & 15) || scratch_bytes < need) return RGBNM_EINVAL;
-  if (plan->nruns &&
-      (!plan->stream || !plan->runs || !plan->images || !plan->tables || ((uintptr_t)plan->stream & 3) || ((uintptr_t)plan->tables & 15) ||
-       ((uintptr_t)plan->runs & 3) || ((uintptr_t)plan->images & 3)))
-    return RGBNM_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   SArgs s;
   s.p = *plan;
-  s.g.n = n; s.g.Hb = Hb; s.g.Wb = Wb; s.g.Hbc = Hbc; s.g.Wbc = Wbc; s.g.Y = Y; s.g.C = CbCr;
+  s.g = out_of(n, Hb, Wb, Hbc, Wbc, Y, CbCr);
   s.path = path;
   s.s = jpegsplit::carve(scratch, plan->stream_bytes, plan->nruns, seg_bits);
   s.seg_bits = seg_bits;
@@ -480,12 +472,8 @@ int rgbnm_jpeg_decode_batch_split(const rgbnm_jpeg_device_plan* plan, int n, int
   split_init_kernel<<<grid(cdivl(nslots > n ? nslots : n, 256)), 256, 0, st>>>(s);
   LAUNCH_CHECK();
   if (plan->nruns == 0) return RGBNM_OK;
-  // Segments per wave: as for the runs of the plain launch, about 2048 waves first ("jpeg_lanes" fixes the number).
-  const int opt = rgbnm_get_option("jpeg_lanes");
-  int per = opt >= 1 && opt <= LANES ? opt : (int)cdivl(nslots, 2048);
-  per = per < 1 ? 1 : per > LANES ? LANES : per;
-  s.lanes = per;
-  const unsigned seg_grid = grid(cdivl(nslots, per)), run_grid = grid(plan->nruns);
+  s.lanes = lanes_per_wave(nslots);
+  const unsigned seg_grid = grid(cdivl(nslots, s.lanes)), run_grid = grid(plan->nruns);
   split_map_kernel<<<run_grid, LANES, 0, st>>>(s);
   LAUNCH_CHECK();
   split_seg_kernel<0><<<seg_grid, LANES, 0, st>>>(s);
@@ -507,10 +495,8 @@ int rgbnm_jpeg_decode_batch_split(const rgbnm_jpeg_device_plan* plan, int n, int
   a.status = status;
   a.info = s.s.info;
   a.path = path;
-  int rper = opt >= 1 && opt <= LANES ? opt : cdiv(plan->nruns, 2048);
-  rper = rper < 1 ? 1 : rper > LANES ? LANES : rper;
-  a.lanes = rper;
-  decode_kernel<<<grid(cdiv(plan->nruns, rper)), LANES, 0, st>>>(a);
+  a.lanes = lanes_per_wave(plan->nruns);
+  decode_kernel<<<grid(cdiv(plan->nruns, a.lanes)), LANES, 0, st>>>(a);
   LAUNCH_CHECK();
   return RGBNM_OK;
 }

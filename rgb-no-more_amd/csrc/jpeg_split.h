@@ -37,9 +37,13 @@
 
 namespace jpegsplit {
 
+using jpegwalk::Bits;                                      // the symbol reader is jpeg_walk.h's
+using jpegwalk::bits_open;
 using jpegwalk::Lane;
+using jpegwalk::next_symbol;
 using jpegwalk::Out;
-using jpegwalk::V16;
+using jpegwalk::Sym;
+using jpegwalk::table_of;
 
 constexpr int SEG_BITS_MIN = 128, SEG_BITS_MAX = 65536;    // a multiple of 32 in this range
 constexpr int ROUNDS_MAX = 64;
@@ -99,73 +103,6 @@ __host__ __device__ inline RunInfo map_run(const rgbnm_jpeg_run& r, int ri, int 
   RunInfo i = {(uint32_t)(base < nslots ? base : 0), 0u};
   if (nseg >= (uint64_t)(min_seg < 2 ? 2 : min_seg) && base + nseg <= (uint64_t)nslots) i.nseg = (uint32_t)nseg;
   return i;
-}
-
-// ---- the bit reader: decode_run's, opened at any bit of the run ---------------------------------------------------------------------
-struct Bits {
-  const uint32_t* words;
-  uint32_t nwords, next;   // next: index of the word behind nextw
-  uint32_t nextw;
-  uint64_t buf;
-  int have;
-};
-
-__host__ __device__ inline void bits_open(Bits& B, const uint8_t* stream, const rgbnm_jpeg_run& r, uint32_t pos) {
-  B.words = reinterpret_cast<const uint32_t*>(stream + r.offset);
-  B.nwords = (r.nbytes + 3u) >> 2;
-  const uint32_t w = pos >> 5, off = pos & 31u;
-  const uint32_t first = w < B.nwords ? B.words[w] : 0u;
-  B.buf = ((uint64_t)__builtin_bswap32(first) << 32) << off;
-  B.have = 32 - (int)off;
-  B.nextw = w + 1 < B.nwords ? B.words[w + 1] : 0u;
-  B.next = w + 2;
-}
-
-struct Sym { int len, s, rr, val; bool bad; };             // len: bits consumed in all (code and value)
-
-// The next symbol behind table T, exactly as decode_run reads it.  bad: no code of the table matches; ONE bit is consumed then.
-__host__ __device__ inline Sym next_symbol(Bits& B, const rgbnm_jpeg_hufftab* T) {
-  if (B.have <= 32) {
-    B.buf |= (uint64_t)__builtin_bswap32(B.nextw) << (32 - B.have);
-    B.have += 32;
-    B.nextw = B.next < B.nwords ? B.words[B.next] : 0u;
-    ++B.next;
-  }
-  const uint32_t e = T->look[B.buf >> 55];
-  int len = (int)(e >> 8), sym = (int)(e & 255u);
-  bool bad = false;
-  if (len == 0) {
-    int idx = -1;
-    for (int l = 10; l <= 16; ++l) {
-      const int code = (int)(B.buf >> (64 - l));
-      if (len == 0 && code <= T->maxcode[l]) {
-        len = l;
-        idx = code + T->valoff[l];
-      }
-    }
-    if (idx < 0 || idx > 255) {
-      bad = true;
-      len = 1;
-      sym = 0;
-    } else {
-      sym = T->vals[idx];
-    }
-  }
-  Sym o;
-  o.s = sym & 15;
-  o.rr = sym >> 4;
-  B.buf <<= len;
-  const uint32_t bits = (uint32_t)((B.buf >> 32) >> (32 - o.s));
-  B.buf <<= o.s;
-  B.have -= len + o.s;
-  o.len = len + o.s;
-  o.val = (o.s && bits < (1u << (o.s - 1))) ? (int)bits - (1 << o.s) + 1 : (int)bits;
-  o.bad = bad;
-  return o;
-}
-
-__host__ __device__ inline const rgbnm_jpeg_hufftab* table_of(const Lane& L, const rgbnm_jpeg_hufftab* tabs, int comp, bool isdc) {
-  return tabs + ((uint32_t)((isdc ? L.dcsel : L.acsel) >> (16 * comp)) & 0xFFFFu);
 }
 
 // scout / sync: walk from `state` until at or past `end` (a bit position of the run, <= its bit count); stores nothing.  Returns the
@@ -287,22 +224,14 @@ __host__ __device__ inline int write_walk(const uint8_t* stream, const rgbnm_jpe
       if (!skipping) {
         jpegwalk::flush_block(tile, g, L, r.image, blk, mx, my);
         ++b;
-        if (++bi == L.nblk) {
-          bi = 0;
-          if (++mx == L.mcus_x) {
-            mx = 0;
-            ++my;
-          }
-        }
+        jpegwalk::next_block(L, bi, mx, my);
       }
       skipping = false;
       blk = blk + 1 == L.nblk ? 0 : blk + 1;
     }
   }
   if (fail || (k != 0 && !skipping)) {                     // a block half written: the tile goes back to zero
-    V16* t = reinterpret_cast<V16*>(tile);
-    const V16 zero = {0, 0, 0, 0};
-    for (int j = 0; j < 8; ++j) t[j] = zero;
+    jpegwalk::zero_tile(tile);
     return -1;
   }
   return 0;
@@ -311,12 +240,9 @@ __host__ __device__ inline int write_walk(const uint8_t* stream, const rgbnm_jpe
 // A one-component file's zero chroma: segment j of nseg takes its part of the run's share (jpegwalk::zero_chroma_share).
 __host__ __device__ inline void zero_chroma_part(const Out& g, int image, uint32_t mcu0, uint32_t nmcu, uint32_t total, uint32_t j, uint32_t nseg) {
   if (!g.C) return;
-  const uint64_t pieces = (uint64_t)2 * (uint64_t)g.Hbc * (uint64_t)g.Wbc * 8u;
-  const uint64_t lo = pieces * mcu0 / total, hi = pieces * ((uint64_t)mcu0 + nmcu) / total;
-  const uint64_t a = lo + (hi - lo) * j / nseg, b = lo + (hi - lo) * ((uint64_t)j + 1) / nseg;
-  V16* dst = reinterpret_cast<V16*>(g.C + (size_t)image * 2 * (size_t)g.Hbc * (size_t)g.Wbc * 64);
-  const V16 zero = {0, 0, 0, 0};
-  for (uint64_t q = a; q < b; ++q) dst[q] = zero;
+  const jpegwalk::Pieces run = jpegwalk::chroma_share(jpegwalk::chroma_pieces(g), mcu0, nmcu, total);
+  const jpegwalk::Pieces seg = {run.lo + (run.hi - run.lo) * j / nseg, run.lo + (run.hi - run.lo) * ((uint64_t)j + 1) / nseg};
+  jpegwalk::zero_pieces(jpegwalk::chroma_slot(g, image), seg);
 }
 
 }  // namespace jpegsplit

@@ -3,6 +3,9 @@
 // host sanitizers (it defines __host__ / __device__ away).  It is libjpeg's sequential decode (jdhuff.c, decode_mcu) reshaped to one
 // symbol per loop trip: the lanes of a wave are at different places of different files, and a trip that handles "the next symbol,
 // whatever it is" with selects keeps them on one instruction stream; only the end of a block (store 128 bytes) is a masked branch.
+// The symbol reader (Bits, next_symbol) serves the split walks of jpeg_split.h; decode_run keeps the same read written out (the comment
+// above it says what the shared one cost).  A fix to one goes to the other.  Shared by every walk: the tile (zero_tile, store_tile), the
+// step to the next block, the share of a one-component file's zero chroma.
 //
 // Safety (the bytes are untrusted):  every trip consumes at least one bit of the run or ends it with an error; the trips are bounded
 // by MCUs x blocks x 64 (a trip advances the coefficient index); reads of the stream are clamped to the run's words, which
@@ -71,16 +74,14 @@ __host__ __device__ inline int check_run(const rgbnm_jpeg_run& r, const rgbnm_jp
   return 0;
 }
 
-// Store the lane's block tile (128 bytes, eight 16-byte stores) to block `blk` of MCU (my, mx) if that lies inside the kept grid,
-// and leave the tile zero for the next block.
-__host__ __device__ inline void flush_block(int16_t* tile, const Out& g, const Lane& L, int image, int blk, int mx, int my) {
-  const int desc = (int)(L.layout >> (6 * blk)) & 63, comp = desc & 3;
-  const int h = (int)(L.hv >> (8 * comp)) & 15, v = (int)(L.hv >> (8 * comp + 4)) & 15;
-  const int bx = mx * h + ((desc >> 2) & 3), by = my * v + (desc >> 4);
-  const int W = comp ? g.Wbc : g.Wb, H = comp ? g.Hbc : g.Hb;
-  const bool ok = bx < W && by < H && (comp == 0 || g.C != nullptr);
-  const size_t row = comp ? ((size_t)image * 2 + (size_t)(comp - 1)) * (size_t)H + (size_t)by : (size_t)image * (size_t)H + (size_t)by;
-  V16* dst = reinterpret_cast<V16*>((comp && ok ? g.C : g.Y) + (ok ? (row * (size_t)W + (size_t)bx) * 64 : 0));
+// The lane's block tile: 128 bytes, moved as eight 16-byte pieces.
+__host__ __device__ inline void zero_tile(int16_t* tile) {
+  V16* t = reinterpret_cast<V16*>(tile);
+  const V16 zero = {0, 0, 0, 0};
+  for (int j = 0; j < 8; ++j) t[j] = zero;
+}
+// Move the tile to dst if `ok` and leave it zero for the next block (dst is read only if ok).
+__host__ __device__ inline void store_tile(int16_t* tile, V16* dst, bool ok) {
   V16* t = reinterpret_cast<V16*>(tile);
   const V16 zero = {0, 0, 0, 0};
   for (int j = 0; j < 8; ++j) {
@@ -88,6 +89,28 @@ __host__ __device__ inline void flush_block(int16_t* tile, const Out& g, const L
     if (ok) dst[j] = x;
     t[j] = zero;
   }
+}
+
+// Store the tile to block `blk` of MCU (my, mx) if that lies inside the kept grid.
+__host__ __device__ inline void flush_block(int16_t* tile, const Out& g, const Lane& L, int image, int blk, int mx, int my) {
+  const int desc = (int)(L.layout >> (6 * blk)) & 63, comp = desc & 3;
+  const int h = (int)(L.hv >> (8 * comp)) & 15, v = (int)(L.hv >> (8 * comp + 4)) & 15;
+  const int bx = mx * h + ((desc >> 2) & 3), by = my * v + (desc >> 4);
+  const int W = comp ? g.Wbc : g.Wb, H = comp ? g.Hbc : g.Hb;
+  const bool ok = bx < W && by < H && (comp == 0 || g.C != nullptr);
+  const size_t row = comp ? ((size_t)image * 2 + (size_t)(comp - 1)) * (size_t)H + (size_t)by : (size_t)image * (size_t)H + (size_t)by;
+  store_tile(tile, reinterpret_cast<V16*>((comp && ok ? g.C : g.Y) + (ok ? (row * (size_t)W + (size_t)bx) * 64 : 0)), ok);
+}
+
+// The block behind block `blk` of MCU (my, mx), in scan order.  true: it is the first of the next MCU.
+__host__ __device__ inline bool next_block(const Lane& L, int& blk, int& mx, int& my) {
+  if (++blk != L.nblk) return false;
+  blk = 0;
+  if (++mx == L.mcus_x) {
+    mx = 0;
+    ++my;
+  }
+  return true;
 }
 
 // ---- the crop form: only a box of each image is wanted (rgbnm_jpeg_decode_batch_crop) ---------------------------------------------
@@ -154,16 +177,76 @@ __host__ __device__ inline void flush_block_crop(int16_t* tile, const Crop B, co
   const int x = mx * h + ((desc >> 2) & 3) - bl, y = my * v + (desc >> 4) - bt;
   const bool ok = x >= 0 && x < bw && y >= 0 && y < bh;
   const size_t row = comp ? (size_t)(comp - 1) * (size_t)bh + (size_t)y : (size_t)y;
-  int16_t* const py = B.Y;
-  int16_t* const pc = B.C;
-  V16* dst = reinterpret_cast<V16*>((comp && ok ? pc : py) + (ok ? (row * (size_t)bw + (size_t)x) * 64 : 0));
-  V16* t = reinterpret_cast<V16*>(tile);
-  const V16 zero = {0, 0, 0, 0};
-  for (int j = 0; j < 8; ++j) {
-    const V16 x16 = t[j];
-    if (ok) dst[j] = x16;
-    t[j] = zero;
+  store_tile(tile, reinterpret_cast<V16*>((comp && ok ? B.C : B.Y) + (ok ? (row * (size_t)bw + (size_t)x) * 64 : 0)), ok);
+}
+
+// ---- the symbol reader: the run's bits behind a 64-bit window, opened at any bit of the run ------------------------------------------
+struct Bits {
+  const uint32_t* words;
+  uint32_t nwords, next;   // next: index of the word behind nextw
+  uint32_t nextw;          // read one word ahead: the load's latency hides behind the trips that use the last one
+  uint64_t buf;
+  int have;
+};
+
+__host__ __device__ inline void bits_open(Bits& B, const uint8_t* stream, const rgbnm_jpeg_run& r, uint32_t pos) {
+  B.words = reinterpret_cast<const uint32_t*>(stream + r.offset);
+  B.nwords = (r.nbytes + 3u) >> 2;
+  const uint32_t w = pos >> 5, off = pos & 31u;
+  const uint32_t first = w < B.nwords ? B.words[w] : 0u;
+  B.buf = ((uint64_t)__builtin_bswap32(first) << 32) << off;
+  B.have = 32 - (int)off;
+  B.nextw = w + 1 < B.nwords ? B.words[w + 1] : 0u;
+  B.next = w + 2;
+}
+
+struct Sym { int len, s, rr, val; bool bad; };             // len: bits consumed in all (code and value)
+
+// The next symbol behind table T: a 9-bit look-up, libjpeg's canonical search for the (rare) codes of 10 to 16 bits, then the s value
+// bits.  bad: no code of the table matches; ONE bit is consumed then, and what the caller makes of it is the caller's.
+__host__ __device__ inline Sym next_symbol(Bits& B, const rgbnm_jpeg_hufftab* T) {
+  if (B.have <= 32) {
+    B.buf |= (uint64_t)__builtin_bswap32(B.nextw) << (32 - B.have);
+    B.have += 32;
+    B.nextw = B.next < B.nwords ? B.words[B.next] : 0u;
+    ++B.next;
   }
+  const uint32_t e = T->look[B.buf >> 55];
+  int len = (int)(e >> 8), sym = (int)(e & 255u);
+  bool bad = false;
+  if (len == 0) {
+    int idx = -1;
+    for (int l = 10; l <= 16; ++l) {
+      const int code = (int)(B.buf >> (64 - l));
+      if (len == 0 && code <= T->maxcode[l]) {
+        len = l;
+        idx = code + T->valoff[l];
+      }
+    }
+    if (idx < 0 || idx > 255) {
+      bad = true;
+      len = 1;
+      sym = 0;
+    } else {
+      sym = T->vals[idx];
+    }
+  }
+  Sym o;
+  o.s = sym & 15;
+  o.rr = sym >> 4;
+  B.buf <<= len;
+  const uint32_t bits = (uint32_t)((B.buf >> 32) >> (32 - o.s));   // the next s bits (s = 0: none)
+  B.buf <<= o.s;
+  B.have -= len + o.s;
+  o.len = len + o.s;
+  // HUFF_EXTEND: a value below 2^(s-1) stands for value - 2^s + 1
+  o.val = (o.s && bits < (1u << (o.s - 1))) ? (int)bits - (1 << o.s) + 1 : (int)bits;
+  o.bad = bad;
+  return o;
+}
+
+__host__ __device__ inline const rgbnm_jpeg_hufftab* table_of(const Lane& L, const rgbnm_jpeg_hufftab* tabs, int comp, bool isdc) {
+  return tabs + ((uint32_t)((isdc ? L.dcsel : L.acsel) >> (16 * comp)) & 0xFFFFu);
 }
 
 // Walk one run.  tile: 64 int16 of the lane's own, 16-byte aligned, ZERO on entry and zero again on return.  tabs: the table array
@@ -172,6 +255,8 @@ __host__ __device__ inline void flush_block_crop(int16_t* tile, const Crop B, co
 // CROP (a compile-time choice: the plain walk carries no trace of it): only the first nwalk MCUs (crop_mcus) are walked and the
 // blocks go through flush_block_crop.  A walk that stops before the run's end has not seen the run's tail, so the two checks behind
 // the loop are not made for it; the errors it does meet are the ones the plain walk meets first, with the same codes.
+// The symbol read is written out here and not taken from next_symbol below: on top of next_symbol the one-lane launches measured up to
+// 2.6 % (plain, no restart markers) and 6 - 8 % (crop) slower than with this text, against a run-to-run disagreement below 1 %.
 // The template is the function itself, with defaults, and not a body behind a decode_run wrapper: with the wrapper the plain kernel's
 // assembly differed in four instruction encodings and the launch time moved by 1 - 8 %; this way it is what it was without the crop form.
 template <bool CROP = false>
@@ -290,25 +375,27 @@ __host__ __device__ inline int decode_run_crop(const uint8_t* stream, const rgbn
   return decode_run<true>(stream, r, L, tabs, zz, none, tile, B, nwalk);
 }
 
-// A one-component file has no chroma to decode: its CbCr slot is zeros.  The run over MCUs [mcu0, mcu0 + nmcu) of `total` writes
-// the same share of the slot's 16-byte pieces, so that the runs of the image cover it exactly once.
-__host__ __device__ inline void zero_chroma_share(const Out& g, int image, uint32_t mcu0, uint32_t nmcu, uint32_t total) {
-  if (!g.C) return;
-  const uint64_t pieces = (uint64_t)2 * (uint64_t)g.Hbc * (uint64_t)g.Wbc * 8u;
-  const uint64_t lo = pieces * mcu0 / total, hi = pieces * ((uint64_t)mcu0 + nmcu) / total;
-  V16* dst = reinterpret_cast<V16*>(g.C + (size_t)image * 2 * (size_t)g.Hbc * (size_t)g.Wbc * 64);
-  const V16 zero = {0, 0, 0, 0};
-  for (uint64_t j = lo; j < hi; ++j) dst[j] = zero;
+// A one-component file has no chroma to decode: its CbCr slot is zeros, written as 16-byte pieces.  The run over MCUs
+// [mcu0, mcu0 + nmcu) of `total` takes the same share [lo, hi) of the slot's `pieces`, so that the runs of the image cover it exactly once.
+struct Pieces { uint64_t lo, hi; };
+__host__ __device__ inline Pieces chroma_share(uint64_t pieces, uint32_t mcu0, uint32_t nmcu, uint32_t total) {
+  const Pieces p = {pieces * mcu0 / total, pieces * ((uint64_t)mcu0 + nmcu) / total};
+  return p;
 }
-
-// The same for the packed chroma crop of a one-component file: every run of the image takes its share of the slot's pieces, whether
-// it is walked or skipped, so that they are written exactly once.
-__host__ __device__ inline void zero_chroma_share_crop(const Crop& B, uint32_t mcu0, uint32_t nmcu, uint32_t total) {
-  const uint64_t pieces = (uint64_t)2 * (uint64_t)(B.h / 2) * (uint64_t)(B.w / 2) * 8u;
-  const uint64_t lo = pieces * mcu0 / total, hi = pieces * ((uint64_t)mcu0 + nmcu) / total;
-  V16* dst = reinterpret_cast<V16*>(B.C);
+__host__ __device__ inline void zero_pieces(int16_t* slot, Pieces p) {
+  V16* dst = reinterpret_cast<V16*>(slot);
   const V16 zero = {0, 0, 0, 0};
-  for (uint64_t j = lo; j < hi; ++j) dst[j] = zero;
+  for (uint64_t j = p.lo; j < p.hi; ++j) dst[j] = zero;
+}
+__host__ __device__ inline uint64_t chroma_pieces(const Out& g) { return (uint64_t)2 * (uint64_t)g.Hbc * (uint64_t)g.Wbc * 8u; }
+__host__ __device__ inline int16_t* chroma_slot(const Out& g, int image) { return g.C + (size_t)image * 2 * (size_t)g.Hbc * (size_t)g.Wbc * 64; }
+
+__host__ __device__ inline void zero_chroma_share(const Out& g, int image, uint32_t mcu0, uint32_t nmcu, uint32_t total) {
+  if (g.C) zero_pieces(chroma_slot(g, image), chroma_share(chroma_pieces(g), mcu0, nmcu, total));
+}
+// The packed chroma crop: every run of the image takes its share, whether it is walked or skipped.
+__host__ __device__ inline void zero_chroma_share_crop(const Crop& B, uint32_t mcu0, uint32_t nmcu, uint32_t total) {
+  zero_pieces(B.C, chroma_share((uint64_t)2 * (uint64_t)(B.h / 2) * (uint64_t)(B.w / 2) * 8u, mcu0, nmcu, total));
 }
 
 }  // namespace jpegwalk

@@ -372,7 +372,13 @@ def launch_jpeg_decode(plan, dev, out, split=False, seg_bits=None, rounds=None, 
     from . import lib as L
     Y, CbCr, _, status = out
     hb, wb = plan.grid
+    hbc, wbc = (hb + 1) // 2, (wb + 1) // 2
     n = plan.n
+
+    def device_plan():                       # after require_cuda(*dev[:4]): a bad `dev` raises there
+        return L.JpegDevicePlan(stream=dev[0].data_ptr(), stream_bytes=plan.stream_bytes, runs=dev[1].data_ptr(), images=dev[2].data_ptr(),
+                                tables=dev[3].data_ptr(), nruns=plan.nruns, ntables=plan.ntables)
+
     if boxes is not None:
         if split:
             raise ValueError("boxes need split=False: the split decode's scout and sync passes must see the whole run whatever the box")
@@ -401,9 +407,8 @@ def launch_jpeg_decode(plan, dev, out, split=False, seg_bits=None, rounds=None, 
                 L.require_cuda(walked)
                 if walked.dtype != torch.int32 or walked.numel() < plan.nruns or not walked.is_contiguous():
                     raise L.RgbnmError("walked must be int32 [plan.nruns]")
-            dp = L.JpegDevicePlan(stream=dev[0].data_ptr(), stream_bytes=plan.stream_bytes, runs=dev[1].data_ptr(), images=dev[2].data_ptr(),
-                                  tables=dev[3].data_ptr(), nruns=plan.nruns, ntables=plan.ntables)
-            L.check(L.lib().rgbnm_jpeg_decode_batch_crop(C.byref(dp), n, hb, wb, (hb + 1) // 2, (wb + 1) // 2, boxes.data_ptr(),
+            dp = device_plan()
+            L.check(L.lib().rgbnm_jpeg_decode_batch_crop(C.byref(dp), n, hb, wb, hbc, wbc, boxes.data_ptr(),
                                                          y_off.data_ptr(), c_off.data_ptr(), Y.data_ptr(), int(ny), CbCr.data_ptr(), int(ncc),
                                                          status.data_ptr(), walked.data_ptr() if walked is not None else None, L.stream()),
                     "jpeg_decode_batch_crop")
@@ -411,16 +416,15 @@ def launch_jpeg_decode(plan, dev, out, split=False, seg_bits=None, rounds=None, 
     if packed_out is not None or walked is not None:
         raise ValueError("packed_out and walked belong to boxes")
     L.require_cuda(Y, CbCr, status, *dev[:4])
-    if tuple(Y.shape) != (n, 1, hb, wb, 8, 8) or tuple(CbCr.shape) != (n, 2, (hb + 1) // 2, (wb + 1) // 2, 8, 8) or status.numel() != n \
+    if tuple(Y.shape) != (n, 1, hb, wb, 8, 8) or tuple(CbCr.shape) != (n, 2, hbc, wbc, 8, 8) or status.numel() != n \
             or Y.dtype != torch.int16 or CbCr.dtype != torch.int16 or status.dtype != torch.int32:
         raise L.RgbnmError("out tensors do not match the plan (alloc_jpeg_out)")
-    dp = L.JpegDevicePlan(stream=dev[0].data_ptr(), stream_bytes=plan.stream_bytes, runs=dev[1].data_ptr(), images=dev[2].data_ptr(),
-                          tables=dev[3].data_ptr(), nruns=plan.nruns, ntables=plan.ntables)
+    dp = device_plan()
     if not split:
         if seg_bits is not None or rounds is not None or path is not None or scratch is not None:
             raise ValueError("seg_bits, rounds, path and scratch belong to split=True")
         with torch.cuda.device(Y.device):
-            L.check(L.lib().rgbnm_jpeg_decode_batch(C.byref(dp), n, hb, wb, (hb + 1) // 2, (wb + 1) // 2, Y.data_ptr(), CbCr.data_ptr(),
+            L.check(L.lib().rgbnm_jpeg_decode_batch(C.byref(dp), n, hb, wb, hbc, wbc, Y.data_ptr(), CbCr.data_ptr(),
                                                     status.data_ptr(), L.stream()), "jpeg_decode_batch")
         return None
     seg_bits = JPEG_SPLIT_SEG_BITS if seg_bits is None else int(seg_bits)
@@ -434,7 +438,7 @@ def launch_jpeg_decode(plan, dev, out, split=False, seg_bits=None, rounds=None, 
         if path.dtype != torch.int32 or path.numel() != n or not path.is_contiguous() or scratch.dtype != torch.uint8 \
                 or not scratch.is_contiguous():
             raise L.RgbnmError("path must be int32 [n], scratch uint8 (jpeg_split_scratch)")
-        L.check(L.lib().rgbnm_jpeg_decode_batch_split(C.byref(dp), n, hb, wb, (hb + 1) // 2, (wb + 1) // 2, Y.data_ptr(), CbCr.data_ptr(),
+        L.check(L.lib().rgbnm_jpeg_decode_batch_split(C.byref(dp), n, hb, wb, hbc, wbc, Y.data_ptr(), CbCr.data_ptr(),
                                                       status.data_ptr(), path.data_ptr(), scratch.data_ptr(), scratch.numel(), seg_bits,
                                                       rounds, L.stream()), "jpeg_decode_batch_split")
     return path
@@ -488,16 +492,21 @@ def jpeg_status_text(code):
     return L.JPEG_STATUS.get(int(code), f"status {int(code)}")
 
 
-def read_coefficients_batch_device(paths_or_bytes, grid=(64, 64), device="cuda", split=False):
-    """read_coefficients_batch with the entropy decode on the device: (Y, CbCr, quant) int16 DEVICE tensors.  Raises, naming the file,
-    when one cannot be decoded there (synchronises to read the device status).  split: the split decode (decode_jpeg_batch)."""
-    plan = prepare_jpeg_batch(paths_or_bytes, grid)
-    Y, CbCr, quant, status = decode_jpeg_batch(plan, device, split=split)
+def _raise_device_status(plan, status):
+    """Raise, naming the first file whose device status is not 0 (synchronises to read it)."""
     st = status.cpu()
     if int((st != 0).sum()):
         i = int((st != 0).nonzero()[0])
         raise libjpeg_exception(f"{plan.names[i]}: device decode refused the file: {jpeg_status_text(st[i])}"
                                 f"{' (' + plan.messages[i] + ')' if plan.messages[i] else ''} ({int((st != 0).sum())} of {plan.n} files failed)")
+
+
+def read_coefficients_batch_device(paths_or_bytes, grid=(64, 64), device="cuda", split=False):
+    """read_coefficients_batch with the entropy decode on the device: (Y, CbCr, quant) int16 DEVICE tensors.  Raises, naming the file,
+    when one cannot be decoded there (synchronises to read the device status).  split: the split decode (decode_jpeg_batch)."""
+    plan = prepare_jpeg_batch(paths_or_bytes, grid)
+    Y, CbCr, quant, status = decode_jpeg_batch(plan, device, split=split)
+    _raise_device_status(plan, status)
     return Y, CbCr, quant
 
 
@@ -508,11 +517,7 @@ def read_coefficients_batch_crop_device(paths_or_bytes, boxes, grid=(64, 64), de
     bx = _check_boxes(boxes, len(paths_or_bytes), grid)
     plan = prepare_jpeg_batch(paths_or_bytes, grid)
     Yp, Cp, quant, status, y_off, c_off = decode_jpeg_batch(plan, device, boxes=bx)
-    st = status.cpu()
-    if int((st != 0).sum()):
-        i = int((st != 0).nonzero()[0])
-        raise libjpeg_exception(f"{plan.names[i]}: device decode refused the file: {jpeg_status_text(st[i])}"
-                                f"{' (' + plan.messages[i] + ')' if plan.messages[i] else ''} ({int((st != 0).sum())} of {plan.n} files failed)")
+    _raise_device_status(plan, status)
     return Yp, Cp, quant, y_off, c_off
 
 

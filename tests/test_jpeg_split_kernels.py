@@ -303,6 +303,25 @@ def test_every_grid_stride_loop_goes_round_again(small_grids, setting):
     assert path.count(1) >= 4
 
 
+@pytest.fixture
+def full_waves():
+    L.set_option("jpeg_min_seg", 2)
+    L.set_option("jpeg_lanes", 64)
+    yield 256, 2
+    L.set_option("jpeg_min_seg", 0)
+    L.set_option("jpeg_lanes", 0)
+
+
+def test_segments_behind_two_table_sets_share_a_wave(full_waves):
+    """A file behind the standard tables and one behind long tables of its own, 38 and 20 segments of 256 bits in the 64 lanes of one
+    wave: no table set serves the whole wave, so every pass, the write pass included, reads the tables from global memory (a wave of
+    one file, as in the tests above, stages them)."""
+    files = [JC.standard_420(7, 96, 64, restart=0).data, JC.long_codes().data]
+    plan, path = split_and_compare(files, (8, 12), full_waves, None, "two table sets", certain=True)
+    offset, nbytes = (int(v) for v in plan.runs[1, :2])
+    assert path == [1, 1] and plan.ntables > 4 and offset * 8 // 256 + 1 + -(-nbytes * 8 // 256) <= 64     # the second run's last slot
+
+
 def test_graph_capture_and_replay_with_other_files(setting):
     """One capture; the plan's device buffers are refilled from a second set of files of the same sizes -- the colour files in another
     order, the gray files with other content in runs of the same lengths: as many runs and tables, and no more stream bytes than

@@ -14,50 +14,11 @@
 //   run without such an MCU is not walked at all; the guard bands around both packed slots are untouched; the tile is zero after a run.
 // A box that is odd, outside the grid or whose offset does not fit must be refused with RGBNM_JPEG_EBOX before anything is written.
 // The packed buffers are heap blocks of the exact size.  Exit status 0: clean.
-#define __host__
-#define __device__
-#include "../rgb-no-more_amd/csrc/jpeg_scan.h"
-#include "../rgb-no-more_amd/csrc/jpeg_walk.h"
+#include "jpeg_check_common.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <string>
+using namespace jpegcheck;
 
 static const int BOXES_GIVEN = 12, BOXES_DAMAGED = 2, GUARD = 64;
-static const int16_t SENTINEL = 0x5555;
-
-struct File {
-  std::string name;
-  std::vector<uint8_t> bytes;
-  int Hb = 0, Wb = 0;
-};
-
-static bool grid_of(const std::vector<uint8_t>& d, int* Hb, int* Wb) {
-  for (size_t p = 2; p + 9 < d.size();) {
-    if (d[p] != 0xFF) return false;
-    const int m = d[p + 1], len = (d[p + 2] << 8) | d[p + 3];
-    if (m == 0xC0 || m == 0xC1 || m == 0xC2) {
-      *Hb = (((d[p + 5] << 8) | d[p + 6]) + 7) / 8;
-      *Wb = (((d[p + 7] << 8) | d[p + 8]) + 7) / 8;
-      return true;
-    }
-    p += 2 + (size_t)len;
-  }
-  return false;
-}
-
-static void fail(const char* what) {
-  fprintf(stderr, "%s\n", what);
-  exit(1);
-}
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;             // xorshift64, fixed seed
-static uint64_t next() {
-  rng_state ^= rng_state << 13;
-  rng_state ^= rng_state >> 7;
-  rng_state ^= rng_state << 17;
-  return rng_state;
-}
 
 struct Tally {
   long decoded = 0, refused_host = 0, refused_walk = 0;        // inputs, by the plain walk's verdict
@@ -65,14 +26,6 @@ struct Tally {
   long hidden = 0;                                             // ... while status_whole < 0: the error lay behind the last needed MCU
   long runs = 0, skipped = 0, early = 0;                       // runs seen by a box; not walked; stopped before their end
   long long mcus = 0, walked = 0;
-};
-
-struct Plan {
-  std::vector<uint8_t> stream;
-  std::vector<rgbnm_jpeg_run> runs;
-  std::vector<rgbnm_jpeg_hufftab> tables;
-  rgbnm_jpeg_image image;
-  rgbnm_jpeg_plan p;
 };
 
 // MCUs of the run up to the last one with a block inside its component's box: by looking at every block of every MCU
@@ -178,48 +131,19 @@ static void bad_boxes(int Hb, int Wb) {
 
 // one input: the plain walk, then the crop walk for `nbox` boxes (and the largest one if `largest`)
 static int run_one(const uint8_t* bytes, size_t len, int Hb, int Wb, int nbox, bool largest, Tally* t) {
-  const int Hbc = (Hb + 1) / 2, Wbc = (Wb + 1) / 2;
-  const int runs_cap = Hb * Wb + 1;
   Plan P;
-  P.stream.resize(len + 8 * (size_t)runs_cap + 8);
-  P.runs.resize((size_t)runs_cap);
-  P.tables.resize(8);
-  std::vector<int16_t> quant(192), Y((size_t)Hb * Wb * 64, SENTINEL), C((size_t)2 * Hbc * Wbc * 64, SENTINEL);
-  std::vector<char> msg(128);
-  memset(&P.p, 0, sizeof(P.p));
-  P.p.stream = P.stream.data(); P.p.stream_cap = P.stream.size();
-  P.p.runs = P.runs.data(); P.p.runs_cap = runs_cap;
-  P.p.images = &P.image;
-  P.p.tables = P.tables.data(); P.p.tables_cap = (int)P.tables.size();
-  P.p.quant = quant.data();
-  P.p.messages = msg.data(); P.p.message_len = (int)msg.size();
-  P.p.threads = 1;
-  std::vector<uint8_t> copy(bytes, bytes + len);
-  const uint8_t* bufs[1] = {copy.data()};
-  const size_t lens[1] = {len};
-  if (jpegscan::prepare(bufs, lens, 1, Hb, Wb, Hbc, Wbc, &P.p) < 0) fail("prepare: invalid arguments");
-  if (P.image.status != 0) {
+  if (const int st = prepare(P, bytes, len, Hb, Wb)) {
     ++t->refused_host;
-    return P.image.status;
+    return st;
   }
-  jpegwalk::Out g = {1, Hb, Wb, Hbc, Wbc, Y.data(), C.data()};
-  alignas(16) int16_t tile[64] = {0};
-  int status = 0;
-  for (int ri = 0; ri < P.p.nruns; ++ri) {
-    const rgbnm_jpeg_run& r = P.runs[(size_t)ri];
-    if (r.nmcu == 0) continue;
-    jpegwalk::Lane L;
-    if (jpegwalk::check_run(r, &P.image, 1, P.p.stream_bytes, P.p.ntables, &L) != 0) fail("a run of the parser's fails check_run");
-    const int err = jpegwalk::decode_run(P.stream.data(), r, L, P.tables.data(), jpegscan::ZIGZAG, g, tile);
-    if (L.ncomp == 1) jpegwalk::zero_chroma_share(g, 0, (uint32_t)r.mcu0, (uint32_t)r.nmcu, L.total);
-    if (err < status) status = err;
-  }
+  Grids G(P);
+  const int status = plain_walk(P, G);
   if (status) ++t->refused_walk; else ++t->decoded;
   const int he = Hb & ~1, we = Wb & ~1;
   if (he < 2 || we < 2) return status;                          // no even box fits this grid
   if (largest) {
     const int box[4] = {0, 0, he, we};
-    one_box(P, Hb, Wb, box, Y, C, status, t);
+    one_box(P, Hb, Wb, box, G.Y, G.C, status, t);
   }
   for (int k = 0; k < nbox; ++k) {
     int box[4];
@@ -228,7 +152,7 @@ static int run_one(const uint8_t* bytes, size_t len, int Hb, int Wb, int nbox, b
     if (k % 3 == 0) box[2] = box[2] > 4 ? 2 : box[2], box[3] = box[3] > 4 ? 2 : box[3];     // small boxes skip the most
     box[0] = 2 * (int)(next() % (uint64_t)((he - box[2]) / 2 + 1));
     box[1] = 2 * (int)(next() % (uint64_t)((we - box[3]) / 2 + 1));
-    one_box(P, Hb, Wb, box, Y, C, status, t);
+    one_box(P, Hb, Wb, box, G.Y, G.C, status, t);
   }
   return status;
 }
@@ -240,50 +164,16 @@ static void report(const char* what, const Tally& t) {
 }
 
 int main(int argc, char** argv) {
-  std::vector<File> files;
-  long share = 1;
-  for (int i = 1; i < argc; ++i) {
-    if (std::string(argv[i]) == "--share" && i + 1 < argc) {
-      share = atol(argv[++i]);
-      if (share < 1) fail("--share needs a positive number");
-      continue;
-    }
-    File f;
-    f.name = argv[i];
-    FILE* fp = fopen(argv[i], "rb");
-    if (!fp) { fprintf(stderr, "cannot open %s\n", argv[i]); return 2; }
-    uint8_t buf[65536];
-    size_t n;
-    while ((n = fread(buf, 1, sizeof(buf), fp)) > 0) f.bytes.insert(f.bytes.end(), buf, buf + n);
-    fclose(fp);
-    if (!grid_of(f.bytes, &f.Hb, &f.Wb)) { fprintf(stderr, "%s: no frame header\n", argv[i]); return 2; }
-    files.push_back(f);
-  }
-  if (files.size() < 2) { fprintf(stderr, "usage: jpeg_crop_check [--share D] a.jpg b.jpg ...\n"); return 2; }
-  Tally whole, cut, mut;
-  for (const File& f : files) {
-    bad_boxes(f.Hb, f.Wb);
-    const int st = run_one(f.bytes.data(), f.bytes.size(), f.Hb, f.Wb, BOXES_GIVEN, true, &whole);
-    const bool refuse = f.name.size() >= 12 && f.name.compare(f.name.size() - 12, 12, "_refused.jpg") == 0;
-    if (refuse ? st == 0 : st != 0) {
-      fprintf(stderr, "%s must %s as given\n", f.name.c_str(), refuse ? "be refused by the parser" : "decode");
-      return 1;
-    }
-  }
+  Tally tally[3];                                               // as given, truncations, mutations
+  const int rc = drive(argc, argv, "jpeg_crop_check", [&](Kind kind, const File& f, const uint8_t* bytes, size_t len) {
+    if (kind == AS_GIVEN) bad_boxes(f.Hb, f.Wb);
+    return run_one(bytes, len, f.Hb, f.Wb, kind == AS_GIVEN ? BOXES_GIVEN : BOXES_DAMAGED, kind == AS_GIVEN, &tally[kind]);
+  });
+  if (rc) return rc;
+  const Tally& whole = tally[AS_GIVEN];
   if (whole.crop_clean != whole.boxes || whole.skipped == 0 || whole.early == 0) fail("the files as given: a box failed, or no run was skipped or stopped early");
-  for (size_t k = 0; k < 2; ++k)
-    for (size_t len = 0; len < files[k].bytes.size(); ++len)
-      if (len % (size_t)share == 0) run_one(files[k].bytes.data(), len, files[k].Hb, files[k].Wb, BOXES_DAMAGED, false, &cut);
-  for (int k = 0; k < 6000; ++k) {
-    const File& f = files[next() % files.size()];
-    std::vector<uint8_t> b = f.bytes;
-    // half of the mutations in the first 700 bytes (the marker segments), half anywhere (mostly the scan)
-    const size_t at = (k & 1) ? next() % b.size() : next() % (b.size() < 700 ? b.size() : 700);
-    b[at] = (k % 8 == 0) ? 0xFF : (uint8_t)next();
-    if (k % share == 0) run_one(b.data(), b.size(), f.Hb, f.Wb, BOXES_DAMAGED, false, &mut);
-  }
   report("as given:", whole);
-  report("truncations:", cut);
-  report("mutations:", mut);
+  report("truncations:", tally[TRUNCATION]);
+  report("mutations:", tally[MUTATION]);
   return 0;
 }
