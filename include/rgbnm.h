@@ -555,10 +555,48 @@ int rgbnm_jpeg_decode_batch_split(const rgbnm_jpeg_device_plan* plan, int n, int
  * No allocation, no copy, no synchronisation: capturable, and a captured call reads the boxes and offsets at replay.
  * RGBNM_EINVAL with nothing launched: whatever rgbnm_jpeg_decode_batch refuses (Ypacked / Cpacked for Y / CbCr), NULL boxes, y_off
  * or c_off, boxes misaligned to 4 bytes, offsets to 8, walked to 4, y_elems or c_elems of 0.  nruns == 0 returns 0 without a launch.
- * The split decode takes no box: its scout and sync passes must see the whole run whatever the box. */
+ * rgbnm_jpeg_decode_batch_split takes no box (its scout and sync passes must see the whole run whatever the box); the split decode
+ * for a box per image is rgbnm_jpeg_decode_batch_split_crop below. */
 int rgbnm_jpeg_decode_batch_crop(const rgbnm_jpeg_device_plan* plan, int n, int Hb, int Wb, int Hbc, int Wbc, const int32_t* boxes,
                                  const long long* y_off, const long long* c_off, int16_t* Ypacked, size_t y_elems, int16_t* Cpacked,
                                  size_t c_elems, int32_t* status, uint32_t* walked, void* stream);
+/* The split decode for a CROP BOX per image: for files without restart markers, whose single run the call above can neither skip nor
+ * cut short.  init, map, scout, the `rounds` sync launches and verify's checks are rgbnm_jpeg_decode_batch_split's and look at no box,
+ * so path[] is what that call writes for the same plan, seg_bits, rounds and options, for every input.  Behind verify's scan every
+ * segment knows the blocks that start in it; segment j of a run that passed is LIVE iff one of them belongs to an MCU that holds a
+ * block of the box of some component (the box mapped through the sampling factors, as in the call above).  The wave that verifies a
+ * run lists its live segments in a list shared by the batch (one atomic add per run); the write launch runs over that list, so its
+ * waves are full whatever the boxes, and a segment that is not live reads no word of the stream.  A live segment decodes every block
+ * that starts in it and stores those inside the box, packed as by the call above.  The order of the runs in the list may differ from
+ * call to call; the outputs do not, since every block of a box starts in exactly one segment and that segment alone stores it.
+ * The last launch is the call above's walk for the runs that were not split and for every run of an image with path 2.  In an image
+ * with path 1 a run that was not split is walked to its END, whatever the box.
+ *   boxes, y_off, c_off, Ypacked, y_elems, Cpacked, c_elems, status     as in rgbnm_jpeg_decode_batch_crop
+ *   path, scratch, seg_bits, rounds                                      as in rgbnm_jpeg_decode_batch_split; scratch of at least
+ *             rgbnm_jpeg_split_crop_scratch_bytes(plan->stream_bytes, plan->nruns, seg_bits) bytes: the split call's, plus the list
+ *             (4 bytes per segment), 8 bytes per run and the list's counter
+ *   walked    device uint32 [nruns] or NULL: the MCUs the one-lane walk of the last launch walked of run ri; 0 for a run it skipped,
+ *             a refused one, and a split run of a path 1 image (the segment lanes wrote it)
+ *   seg_live  device uint32 [nruns] or NULL: for a split run of an image with path 1 the number of its segments the write pass
+ *             walked; 0 for every other run
+ * For every input, damaged ones included, with the status arrays starting from the same values: (a), (b) and (c) of the call above,
+ * and (d) for an image with path 1 the status IS the whole decode's: verify has seen every bit of its split runs and the others are
+ * walked to their end, so a 0 there does speak for the bytes behind the box.  (e) For path 0 or 2 the call above's caveat stands: a
+ * status of 0 says nothing about the bytes behind the last MCU a box needed.
+ * Every write lane and every lane of the last launch checks its image's box and offsets before any store: a failure lowers
+ * status[image] to RGBNM_JPEG_EBOX and nothing of that image is written.  The list's count and entries are device data: the count is
+ * clamped to the number of slots and every entry is checked against the slot's run record again, as in every segment launch; every
+ * record, trip count, stream read and store is bounded as in the two calls above.
+ * 6 + rounds launches whatever the data (the write launch's grid follows from the scratch's slot count; it reads the list's length on
+ * the device).  No allocation, no copy, no synchronisation: capturable, and a captured call reads the boxes and offsets at replay.
+ * RGBNM_EINVAL with nothing launched: whatever rgbnm_jpeg_decode_batch_crop or rgbnm_jpeg_decode_batch_split refuses, seg_live
+ * misaligned to 4 bytes, scratch smaller than the bound above.  nruns == 0: path is zeroed, nothing else.
+ * rgbnm_jpeg_split_crop_scratch_bytes is host only, at least rgbnm_jpeg_split_scratch_bytes, and 0 where that is 0. */
+size_t rgbnm_jpeg_split_crop_scratch_bytes(size_t stream_bytes, int nruns, int seg_bits);
+int rgbnm_jpeg_decode_batch_split_crop(const rgbnm_jpeg_device_plan* plan, int n, int Hb, int Wb, int Hbc, int Wbc, const int32_t* boxes,
+                                       const long long* y_off, const long long* c_off, int16_t* Ypacked, size_t y_elems, int16_t* Cpacked,
+                                       size_t c_elems, int32_t* status, int32_t* path, uint32_t* walked, uint32_t* seg_live, void* scratch,
+                                       size_t scratch_bytes, int seg_bits, int rounds, void* stream);
 
 /* Entropy ENCODING on the device (csrc/jpeg_emit.h, jpeg_encode.hip): from the int16 coefficient tensors back to whole files, SOI to
  * EOI.  The file is the one libjpeg's jpeg_write_coefficients writes with its defaults, byte for byte (the reference's

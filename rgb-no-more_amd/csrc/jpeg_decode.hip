@@ -13,7 +13,8 @@
 //     file.  Otherwise the lanes read the batch's table array in global memory.  The choice is wave-uniform.
 //   - an error lowers status[image] with atomicMin; no lane waits for another, no loop depends on the data for its bound.
 // decode_crop_kernel is the same launch for a crop box per image (rgbnm_jpeg_decode_batch_crop): runs outside the box are skipped,
-// the others stop after the last MCU the box needs, and only the box is stored, packed.
+// the others stop after the last MCU the box needs, and only the box is stored, packed.  rgbnm_jpeg_decode_batch_split_crop is the
+// split decode for such boxes: its verify, write and one-lane launches are kernels of their own behind the split kernels.
 #include "common.h"
 #include "jpeg_scan.h"
 #include "jpeg_walk.h"
@@ -368,8 +369,243 @@ __global__ __launch_bounds__(LANES) void split_verify_kernel(SArgs a) {
   }
 }
 
-// ---- the host side of the three entries -----------------------------------------------------------------------------------------------
-// What all three refuse: the plan, n, the grids, the outputs and the status and their alignment, and the plan's buffers where it has runs.
+// ---- the split decode for a crop box per image (rgbnm_jpeg_decode_batch_split_crop; jpeg_split.h, the crop form) ----------------------
+// Launches: init, map, scout, `rounds` x sync -- the split call's own kernels, which look at no box -- then verify, write and the
+// one-lane launch in the forms below.  Kernels of their own, not switches in the ones above: those stay the code they were.
+struct XArgs {
+  SArgs s;                                 // s.g: n and the grids; its Y / C are NULL
+  const int32_t* boxes;                    // [n][4]
+  const long long* y_off;                  // [n]
+  const long long* c_off;
+  int16_t* Y;                              // packed, y_elems
+  int16_t* C;                              // packed, c_elems
+  size_t y_elems, c_elems;
+  int32_t* status;
+  uint32_t* walked;                        // [nruns] or NULL
+  uint32_t* seg_live;                      // [nruns] or NULL
+  jpegsplit::Compact x;
+  int run_lanes;                           // runs per wave of the last launch
+  int fixed_lanes;                         // option "jpeg_lanes" is set: the write launch takes s.lanes entries per wave whatever the list's length
+};
+
+__device__ __forceinline__ int box_of(const XArgs& a, int image, jpegwalk::Crop* B) {
+  return jpegwalk::check_box(a.boxes + 4 * (size_t)image, a.y_off[image], a.c_off[image], a.s.g.Hb, a.s.g.Wb, a.s.g.Hbc, a.s.g.Wbc, a.Y,
+                             a.y_elems, a.C, a.c_elems, B);
+}
+
+// split_init_kernel, and the list is empty
+__global__ __launch_bounds__(256) void split_crop_init_kernel(XArgs a) {
+  const size_t m = a.s.s.nslots > (uint32_t)a.s.g.n ? a.s.s.nslots : (size_t)a.s.g.n;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (size_t)gridDim.x * blockDim.x) {
+    if (i < a.s.s.nslots) a.s.s.seg_run[i] = -1;
+    if (i < (size_t)a.s.g.n) a.s.path[i] = 0;
+    if (i == 0) *a.x.count = 0;
+  }
+}
+
+// split_verify_kernel's checks and scan, word for word; the wave also counts the run's live segments on the way and, if the run
+// passed, lists them: one atomic add reserves the range, a second trip over the segments fills it in segment order.  A bad box
+// leaves the run without live segments (the last launch reports it).
+__global__ __launch_bounds__(LANES) void split_verify_crop_kernel(XArgs a) {
+  using namespace jpegsplit;
+  const int lane = threadIdx.x;
+  const uint64_t* fin = a.s.s.exits[a.s.cur];
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (int ri = blockIdx.x; ri < a.s.p.nruns; ri += gridDim.x) {
+    const RunInfo info = a.s.s.info[ri];
+    const rgbnm_jpeg_run r = a.s.p.runs[ri];
+    Lane L;
+    if (info.nseg == 0 || jpegwalk::check_run(r, a.s.p.images, a.s.g.n, a.s.p.stream_bytes, a.s.p.ntables, &L) != 0) {
+      if (lane == 0) a.x.live[ri] = RunLive{0u, 0u};
+      continue;
+    }
+    jpegwalk::Crop B = {};
+    const bool boxed = box_of(a, r.image, &B) == 0;
+    const uint64_t N = (uint64_t)r.nmcu * (uint64_t)L.nblk;
+    const uint32_t total_bits = r.nbytes * 8u;
+    uint32_t carry[5] = {0, 0, 0, 0, 0};   // blocks completed, blocks started, DC sums
+    uint32_t nlive = 0;
+    bool bad = false, found = false;
+    for (uint32_t c0 = 0; c0 < info.nseg; c0 += LANES) {
+      const uint32_t j = c0 + (uint32_t)lane, slot = info.base + j;
+      const bool v = j < info.nseg;
+      SegRec c = {};
+      bool conv = true;
+      if (v) {
+        c = a.s.s.rec[slot];
+        conv = a.s.s.seg_run[slot] == ri && a.s.s.entry[slot] == (j ? fin[slot - 1] : pack_state(0, 0, 0));
+      }
+      const uint32_t own[5] = {c.ndone, c.nstart, c.dc[0], c.dc[1], c.dc[2]};
+      uint32_t incl[5];
+      for (int q = 0; q < 5; ++q) {
+        uint32_t x = own[q];
+        for (int d = 1; d < LANES; d <<= 1) {
+          const uint32_t y = __shfl_up(x, d, LANES);
+          if (lane >= d) x += y;
+        }
+        incl[q] = x;
+      }
+      int verdict = 0;
+      bool lv = false;
+      if (v) {
+        verdict = seg_verdict(c, (uint64_t)carry[0] + incl[0] - own[0], N, total_bits);
+        SegScan sc;
+        sc.b0 = carry[1] + incl[1] - own[1];
+        for (int q = 0; q < 3; ++q) sc.p[q] = carry[2 + q] + incl[2 + q] - own[2 + q];
+        a.s.s.scan[slot] = sc;
+        lv = boxed && seg_is_live(r, L, B, sc.b0, c.nstart);
+      }
+      bad = bad || __any(!conv || verdict == 1);
+      found = found || __any(verdict == 2);
+      nlive += (uint32_t)__popcll(__ballot(lv));
+      for (int q = 0; q < 5; ++q) carry[q] += __shfl(incl[q], LANES - 1, LANES);
+    }
+    bool passed = !(bad || !found);
+    uint32_t first = 0;
+    if (passed && nlive) {
+      if (lane == 0) first = atomicAdd(a.x.count, nlive);
+      first = __shfl(first, 0, LANES);
+      if (!list_fits(first, nlive, a.s.s.nslots)) passed = false;
+    }
+    if (!passed) nlive = 0;
+    if (lane == 0) {
+      if (!passed) atomicMax(&a.s.path[r.image], 2);
+      a.x.live[ri] = RunLive{first, nlive};
+    }
+    uint32_t at = first;
+    for (uint32_t c0 = 0; nlive && c0 < info.nseg; c0 += LANES) {
+      const uint32_t j = c0 + (uint32_t)lane, slot = info.base + j;
+      const bool lv = j < info.nseg && seg_is_live(r, L, B, a.s.s.scan[slot].b0, a.s.s.rec[slot].nstart);   // this lane's own words
+      const unsigned long long m = __ballot(lv);
+      const uint32_t k = at + (uint32_t)__popcll(m & below);
+      if (lv && k - first < nlive) a.x.list[k] = slot;
+      at += (uint32_t)__popcll(m);
+    }
+  }
+}
+
+// split_seg_kernel<2> over the list of live slots: lanes = consecutive entries, so normally live segments of one run.  The count and
+// every entry are re-checked as a slot's run is in every segment launch.
+__global__ __launch_bounds__(LANES) void split_write_crop_kernel(XArgs a) {
+  using namespace jpegsplit;
+  __shared__ alignas(16) uint8_t s_tile[LANES * PITCH];
+  __shared__ alignas(16) rgbnm_jpeg_hufftab s_tab[SLOTS];
+  __shared__ uint8_t s_zz[64];
+  const int lane = threadIdx.x;
+  int16_t* tile = wave_tile(s_tile, s_zz);
+  const uint32_t nslots = a.s.s.nslots, listed = *a.x.count, nlist = listed < nslots ? listed : nslots;
+  // lanes_per_wave's rule on the list's length, which only the device knows: about 2048 waves first, fuller waves beyond that
+  const uint32_t spread = (nlist + 2047u) / 2048u;
+  const int per = a.fixed_lanes ? a.s.lanes : (int)(spread < 1u ? 1u : spread > (uint32_t)LANES ? (uint32_t)LANES : spread);
+  const jpegwalk::Out none = {0, 0, 0, 0, 0, nullptr, nullptr};
+  for (long long base = (long long)blockIdx.x * per; base < (long long)nlist; base += (long long)gridDim.x * per) {
+    const uint32_t at = (uint32_t)base + (uint32_t)lane;
+    bool live = lane < per && at < nlist;
+    uint32_t slot = 0, j = 0;
+    int ri = -1;
+    rgbnm_jpeg_run r = {};
+    Lane L = {};
+    jpegwalk::Crop B = {};
+    if (live) {
+      slot = a.x.list[at];
+      live = slot < nslots;
+    }
+    if (live) {
+      ri = a.s.s.seg_run[slot];
+      live = ri >= 0 && ri < a.s.p.nruns;
+    }
+    if (live) {
+      const RunInfo info = a.s.s.info[ri];
+      j = slot - info.base;                // unsigned: a slot in front of the run's fails the next test too
+      live = j < info.nseg;
+    }
+    if (live) {
+      r = a.s.p.runs[ri];
+      live = r.nmcu != 0 && jpegwalk::check_run(r, a.s.p.images, a.s.g.n, a.s.p.stream_bytes, a.s.p.ntables, &L) == 0;
+    }
+    if (live) live = a.s.path[r.image] == 1;
+    if (live && box_of(a, r.image, &B) != 0) {
+      live = false;
+      atomicMin(&a.status[r.image], RGBNM_JPEG_EBOX);
+    }
+    const rgbnm_jpeg_hufftab* tabs = a.s.p.tables;
+    Lane S = L;
+    if (stage_tables(live, L, a.s.p.tables, s_tab)) {
+      tabs = s_tab;
+      S = staged(L);
+    }
+    if (!live) continue;
+    const SegScan sc = a.s.s.scan[slot];
+    if (write_walk<true>(a.s.p.stream, r, S, tabs, s_zz, none, tile, a.s.s.entry[slot], seg_end(r, j, a.s.seg_bits), (uint32_t)a.s.seg_bits + 64u,
+                         sc, B) != 0)
+      atomicMax(&a.s.path[r.image], 2);
+    if (L.ncomp == 1) {
+      const RunLive rl = a.x.live[ri];
+      if (at - rl.first < rl.count) zero_chroma_part_crop(B, (uint32_t)r.mcu0, (uint32_t)r.nmcu, L.total, at - rl.first, rl.count);
+    }
+  }
+}
+
+// decode_crop_kernel's walk for what is left: the runs that were not split and every run of an image whose split did not pass.  A split
+// run of a path 1 image is left alone as decode_kernel leaves it under the split call -- but its box is checked here too (a bad box
+// gave it no live segment, so no write lane has reported it), and a one-component run without a live segment zeroes its share of the
+// chroma crop here.  seg_live is written here, where the image's final path is known.
+__global__ __launch_bounds__(LANES) void decode_crop_rest_kernel(XArgs a) {
+  using namespace jpegwalk;
+  __shared__ alignas(16) uint8_t s_tile[LANES * PITCH];
+  __shared__ alignas(16) rgbnm_jpeg_hufftab s_tab[SLOTS];
+  __shared__ uint8_t s_zz[64];
+  const int lane = threadIdx.x;
+  int16_t* tile = wave_tile(s_tile, s_zz);
+  const int nruns = a.s.p.nruns, per = a.run_lanes, n = a.s.g.n;
+  for (long long base = (long long)blockIdx.x * per; base < nruns; base += (long long)gridDim.x * per) {
+    const int ri = (int)base + lane;
+    const bool mine = lane < per && ri < nruns;
+    bool ok = mine;                        // the records and the box passed: the run's image is written by this call
+    rgbnm_jpeg_run r = {};
+    Lane L = {};
+    Crop B = {};
+    uint32_t nwalk = 0, nlive = 0;
+    if (ok) {
+      r = a.s.p.runs[ri];
+      if (r.nmcu == 0) {                   // the record of a file the host refused
+        ok = false;
+      } else if (check_run(r, a.s.p.images, n, a.s.p.stream_bytes, a.s.p.ntables, &L) != 0) {
+        ok = false;
+        if (r.image >= 0 && r.image < n) atomicMin(&a.status[r.image], RGBNM_JPEG_ERECORD);
+      } else if (box_of(a, r.image, &B) != 0) {
+        ok = false;
+        atomicMin(&a.status[r.image], RGBNM_JPEG_EBOX);
+      } else if (a.s.s.info[ri].nseg && a.s.path[r.image] == 1) {      // the segment lanes have written it
+        const jpegsplit::RunLive rl = a.x.live[ri];
+        nlive = rl.count;
+        if (L.ncomp == 1 && nlive == 0) zero_chroma_share_crop(B, (uint32_t)r.mcu0, (uint32_t)r.nmcu, L.total);
+        ok = false;
+      } else {
+        // a run that was not split, in an image whose split runs passed: walked to its end, so that the image's status is the whole
+        // decode's (verify has vouched for the split runs; a walk that stops early vouches for nothing behind the box)
+        nwalk = a.s.path[r.image] == 1 ? (uint32_t)r.nmcu : crop_mcus(r, L, B);
+      }
+    }
+    const bool live = nwalk != 0;          // only these lanes walk
+    int err = 0;
+    const rgbnm_jpeg_hufftab* tabs = a.s.p.tables;
+    Lane S = L;
+    if (stage_tables(live, L, a.s.p.tables, s_tab)) {
+      tabs = s_tab;
+      S = staged(L);
+    }
+    if (live) err = decode_run_crop(a.s.p.stream, r, S, tabs, s_zz, B, nwalk, tile);
+    if (err) atomicMin(&a.status[r.image], err);
+    // a skipped run takes its share of a one-component file's zero chroma like a walked one
+    if (ok && L.ncomp == 1) zero_chroma_share_crop(B, (uint32_t)r.mcu0, (uint32_t)r.nmcu, L.total);
+    if (mine && a.walked) a.walked[ri] = nwalk;
+    if (mine && a.seg_live) a.seg_live[ri] = nlive;
+  }
+}
+
+// ---- the host side of the four entries ------------------------------------------------------------------------------------------------
+// What all four refuse: the plan, n, the grids, the outputs and the status and their alignment, and the plan's buffers where it has runs.
 static bool bad_call(const rgbnm_jpeg_device_plan* plan, int n, int Hb, int Wb, int Hbc, int Wbc, const void* Y, const void* C, const void* status) {
   if (!plan || !Y || !C || !status || n <= 0 || Hb < 1 || Wb < 1 || Hbc < 1 || Wbc < 1 || Hb > 4096 || Wb > 4096 || Hbc > 4096 ||
       Wbc > 4096 || plan->nruns < 0 || plan->ntables < 0)
@@ -497,6 +733,74 @@ int rgbnm_jpeg_decode_batch_split(const rgbnm_jpeg_device_plan* plan, int n, int
   a.path = path;
   a.lanes = lanes_per_wave(plan->nruns);
   decode_kernel<<<grid(cdiv(plan->nruns, a.lanes)), LANES, 0, st>>>(a);
+  LAUNCH_CHECK();
+  return RGBNM_OK;
+}
+
+size_t rgbnm_jpeg_split_crop_scratch_bytes(size_t stream_bytes, int nruns, int seg_bits) {
+  return jpegsplit::crop_scratch_bytes(stream_bytes, nruns, seg_bits);
+}
+
+int rgbnm_jpeg_decode_batch_split_crop(const rgbnm_jpeg_device_plan* plan, int n, int Hb, int Wb, int Hbc, int Wbc, const int32_t* boxes,
+                                       const long long* y_off, const long long* c_off, int16_t* Ypacked, size_t y_elems, int16_t* Cpacked,
+                                       size_t c_elems, int32_t* status, int32_t* path, uint32_t* walked, uint32_t* seg_live, void* scratch,
+                                       size_t scratch_bytes, int seg_bits, int rounds, void* stream) {
+  using namespace jpegdec;
+  if (bad_call(plan, n, Hb, Wb, Hbc, Wbc, Ypacked, Cpacked, status)) return RGBNM_EINVAL;
+  if (!boxes || !y_off || !c_off || y_elems == 0 || c_elems == 0) return RGBNM_EINVAL;
+  if (((uintptr_t)boxes & 3) || ((uintptr_t)y_off & 7) || ((uintptr_t)c_off & 7) || ((uintptr_t)walked & 3) || ((uintptr_t)seg_live & 3))
+    return RGBNM_EINVAL;
+  if (!path || ((uintptr_t)path & 3) || rounds < 0 || rounds > jpegsplit::ROUNDS_MAX) return RGBNM_EINVAL;
+  const size_t need = jpegsplit::crop_scratch_bytes(plan->stream_bytes, plan->nruns, seg_bits);   // 0: seg_bits out of range
+  if (need == 0 || !scratch || ((uintptr_t)scratch & 15) || scratch_bytes < need) return RGBNM_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  XArgs x;
+  SArgs& s = x.s;
+  s.p = *plan;
+  s.g = out_of(n, Hb, Wb, Hbc, Wbc, nullptr, nullptr);
+  s.path = path;
+  s.s = jpegsplit::carve(scratch, plan->stream_bytes, plan->nruns, seg_bits);
+  s.seg_bits = seg_bits;
+  const int ms = rgbnm_get_option("jpeg_min_seg");
+  s.min_seg = ms >= 2 ? ms : jpegsplit::MIN_SEG;
+  s.cur = 0;
+  s.lanes = 1;
+  x.boxes = boxes; x.y_off = y_off; x.c_off = c_off;
+  x.Y = Ypacked; x.C = Cpacked; x.y_elems = y_elems; x.c_elems = c_elems;
+  x.status = status;
+  x.walked = walked;
+  x.seg_live = seg_live;
+  x.x = jpegsplit::carve_crop(scratch, plan->stream_bytes, plan->nruns, seg_bits);
+  x.run_lanes = 1;
+  const int lanes_opt = rgbnm_get_option("jpeg_lanes");
+  x.fixed_lanes = lanes_opt >= 1 && lanes_opt <= LANES;
+  const int cap_opt = rgbnm_get_option("jpeg_split_wgs");          // as in the split call
+  const int cap = cap_opt >= 1 && cap_opt < MAX_WGS ? cap_opt : MAX_WGS;
+  auto grid = [cap](long long groups) { return (unsigned)(groups < 1 ? 1 : groups < cap ? groups : cap); };
+  const long long nslots = s.s.nslots;
+  split_crop_init_kernel<<<grid(cdivl(nslots > n ? nslots : n, 256)), 256, 0, st>>>(x);
+  LAUNCH_CHECK();
+  if (plan->nruns == 0) return RGBNM_OK;
+  s.lanes = lanes_per_wave(nslots);
+  x.run_lanes = lanes_per_wave(plan->nruns);
+  const unsigned seg_grid = grid(cdivl(nslots, s.lanes)), run_grid = grid(plan->nruns);
+  split_map_kernel<<<run_grid, LANES, 0, st>>>(s);
+  LAUNCH_CHECK();
+  split_seg_kernel<0><<<seg_grid, LANES, 0, st>>>(s);
+  LAUNCH_CHECK();
+  for (int j = 0; j < rounds; ++j) {
+    s.cur = j & 1;
+    split_seg_kernel<1><<<seg_grid, LANES, 0, st>>>(s);
+    LAUNCH_CHECK();
+  }
+  s.cur = rounds & 1;
+  split_verify_crop_kernel<<<run_grid, LANES, 0, st>>>(x);
+  LAUNCH_CHECK();
+  // over the list: its length is device data, so the grid is the whole-grid write pass's (enough for the list at any number of
+  // entries per wave that the kernel's rule can choose, the grid-stride loop aside) and the waves behind the list's end leave at once
+  split_write_crop_kernel<<<seg_grid, LANES, 0, st>>>(x);
+  LAUNCH_CHECK();
+  decode_crop_rest_kernel<<<grid(cdiv(plan->nruns, x.run_lanes)), LANES, 0, st>>>(x);
   LAUNCH_CHECK();
   return RGBNM_OK;
 }

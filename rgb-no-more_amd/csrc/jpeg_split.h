@@ -22,6 +22,8 @@
 //   write   per segment of a run that passed: skip the block under way at the entry, decode every block whose DC symbol starts
 //           before the segment's end -- on past the end until the last of them is complete -- and store through flush_block.
 // Every image with a run that did not pass is decoded by the one-lane walk afterwards, as are the runs that were not split.
+// The crop form (rgbnm_jpeg_decode_batch_split_crop; the last part of this file): the same passes up to verify, then the write pass
+// over a compacted list of the segments that hold a block of the image's crop box, into the packed crop.
 //
 // Safety (the bytes are untrusted): a walk that meets an impossible symbol carries on -- it skips one bit of an unassigned code,
 // clamps a coefficient index past 63, ignores the run nibble of a DC symbol -- and notes it, because a walk from a guessed state
@@ -179,9 +181,12 @@ __host__ __device__ inline int seg_verdict(const SegRec& c, uint64_t done_before
 
 // write: segment j's share of the blocks.  tile: as for decode_run, zero on entry and on return.  Returns 0, or -1 when the walk met
 // what verify should have excluded (the caller sends the image to the one-lane walk).
+// CROP (a compile-time choice, as in decode_run: the plain walk carries no trace of it): the blocks go through flush_block_crop into
+// the packed crop `box`, and g is not looked at.
+template <bool CROP = false>
 __host__ __device__ inline int write_walk(const uint8_t* stream, const rgbnm_jpeg_run& r, const Lane& L, const rgbnm_jpeg_hufftab* tabs,
                                           const uint8_t* zz, const Out& g, int16_t* tile, uint64_t state, uint32_t end, uint32_t maxtrips,
-                                          const SegScan& sc) {
+                                          const SegScan& sc, const jpegwalk::Crop box = jpegwalk::Crop()) {
   const uint32_t total_bits = r.nbytes * 8u, N = (uint32_t)r.nmcu * (uint32_t)L.nblk;
   uint32_t pos = state_pos(state), b = sc.b0;
   int k = state_k(state), blk = state_blk(state);
@@ -222,7 +227,8 @@ __host__ __device__ inline int write_walk(const uint8_t* stream, const rgbnm_jpe
     if (k >= 64) {
       k = 0;
       if (!skipping) {
-        jpegwalk::flush_block(tile, g, L, r.image, blk, mx, my);
+        if (CROP) jpegwalk::flush_block_crop(tile, box, L, blk, mx, my);
+        else jpegwalk::flush_block(tile, g, L, r.image, blk, mx, my);
         ++b;
         jpegwalk::next_block(L, bi, mx, my);
       }
@@ -243,6 +249,77 @@ __host__ __device__ inline void zero_chroma_part(const Out& g, int image, uint32
   const jpegwalk::Pieces run = jpegwalk::chroma_share(jpegwalk::chroma_pieces(g), mcu0, nmcu, total);
   const jpegwalk::Pieces seg = {run.lo + (run.hi - run.lo) * j / nseg, run.lo + (run.hi - run.lo) * ((uint64_t)j + 1) / nseg};
   jpegwalk::zero_pieces(jpegwalk::chroma_slot(g, image), seg);
+}
+
+// ---- the crop form (rgbnm_jpeg_decode_batch_split_crop): the write pass walks only the segments that hold a block of the box ----------
+// Scout, sync and verify see the whole run whatever the box.  Behind verify's scan every segment knows the blocks that start in it,
+// [b0, b0 + nstart): a raster range of MCUs.  A segment is LIVE iff one of those MCUs holds a block of the box of some component (the
+// box mapped through the sampling factors, as jpegwalk::crop_mcus maps it).  The wave that verifies a run counts its live segments,
+// reserves that many entries of one list with ONE atomic add and writes the live slots there in segment order; the write launch runs
+// over the list, so its waves are dense whatever the boxes.  The order of the runs in the list is the order of the atomics and may
+// differ from call to call; the outputs do not depend on it, because every block of a box starts in exactly one segment and that
+// segment alone stores it.  The list, its count and the per-run ranges are device data like every other record: a write lane clamps
+// the count, re-checks its slot as every segment lane does, and uses the range only to share out a one-component file's zero chroma.
+struct RunLive { uint32_t first, count; };                 // the run's entries of the list: [first, first + count)
+struct Compact {
+  uint32_t* list;       // [nslots]: the live slots, run after run
+  RunLive* live;        // [nruns]
+  uint32_t* count;      // entries reserved so far
+};
+// the crop form's scratch: the split call's, then the list, the ranges and the counter.  0 where scratch_bytes gives 0.
+inline size_t crop_scratch_bytes(size_t stream_bytes, int nruns, int seg_bits) {
+  const size_t base = scratch_bytes(stream_bytes, nruns, seg_bits);
+  if (!base) return 0;
+  return align16(base) + align16(slot_count(stream_bytes, nruns, seg_bits) * 4) + align16((size_t)nruns * sizeof(RunLive)) + 16;
+}
+inline Compact carve_crop(void* mem, size_t stream_bytes, int nruns, int seg_bits) {
+  uint8_t* p = static_cast<uint8_t*>(mem) + align16(scratch_bytes(stream_bytes, nruns, seg_bits));
+  Compact x;
+  x.list = reinterpret_cast<uint32_t*>(p); p += align16(slot_count(stream_bytes, nruns, seg_bits) * 4);
+  x.live = reinterpret_cast<RunLive*>(p); p += align16((size_t)nruns * sizeof(RunLive));
+  x.count = reinterpret_cast<uint32_t*>(p);
+  return x;
+}
+
+// The live test, closed form: the blocks [b0, b0 + nstart) of the run, cut to its nmcu * nblk, lie in the MCUs [lo, hi] (raster
+// order); per component the MCUs that hold a block of its box are a rectangle, and the first MCU of the rectangle at or behind lo is
+// found without a loop.
+__host__ __device__ inline bool seg_is_live(const rgbnm_jpeg_run& r, const Lane& L, const jpegwalk::Crop& B, uint32_t b0, uint32_t nstart) {
+  const uint32_t N = (uint32_t)r.nmcu * (uint32_t)L.nblk;   // below 2^25: check_run
+  if (b0 >= N || nstart == 0) return false;
+  const uint32_t end = nstart < N - b0 ? b0 + nstart : N, nblk = (uint32_t)L.nblk;
+  const int mcus_x = L.mcus_x;
+  const int lo = r.mcu0 + (int)(b0 / nblk), hi = r.mcu0 + (int)((end - 1) / nblk);
+  for (int c = 0; c < L.ncomp; ++c) {
+    const int hs = (int)(L.hv >> (8 * c)) & 15, vs = (int)(L.hv >> (8 * c + 4)) & 15;
+    const int t = c ? B.top / 2 : B.top, l = c ? B.left / 2 : B.left, h = c ? B.h / 2 : B.h, w = c ? B.w / 2 : B.w;
+    const int x0 = l / hs, xe = (l + w - 1) / hs, x1 = xe < mcus_x ? xe : mcus_x - 1, y0 = t / vs, y1 = (t + h - 1) / vs;
+    int y = lo / mcus_x, x = lo - y * mcus_x;
+    if (y < y0) {
+      y = y0;
+      x = x0;
+    } else if (x < x0) {
+      x = x0;
+    } else if (x > x1) {
+      ++y;
+      x = x0;
+    }
+    if (x0 <= x1 && y <= y1 && y * mcus_x + x <= hi) return true;
+  }
+  return false;
+}
+
+// Does a run's range of `total` entries from `first` fit the list?  (It always does: a slot is listed at most once.  A run whose
+// range does not fit is sent to the one-lane walk.)
+__host__ __device__ inline bool list_fits(uint32_t first, uint32_t total, uint32_t nslots) { return first <= nslots && total <= nslots - first; }
+
+// A one-component file's zero chroma in the packed crop: live segment `rank` of the run's `count` takes its part of the run's share
+// (jpegwalk::zero_chroma_share_crop).  A split run without a live segment leaves its share to the last launch.
+__host__ __device__ inline void zero_chroma_part_crop(const jpegwalk::Crop& B, uint32_t mcu0, uint32_t nmcu, uint32_t total, uint32_t rank,
+                                                      uint32_t count) {
+  const jpegwalk::Pieces run = jpegwalk::chroma_share((uint64_t)2 * (uint64_t)(B.h / 2) * (uint64_t)(B.w / 2) * 8u, mcu0, nmcu, total);
+  const jpegwalk::Pieces seg = {run.lo + (run.hi - run.lo) * rank / count, run.lo + (run.hi - run.lo) * ((uint64_t)rank + 1) / count};
+  jpegwalk::zero_pieces(B.C, seg);
 }
 
 }  // namespace jpegsplit

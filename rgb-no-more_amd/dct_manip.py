@@ -381,7 +381,8 @@ def launch_jpeg_decode(plan, dev, out, split=False, seg_bits=None, rounds=None, 
 
     if boxes is not None:
         if split:
-            raise ValueError("boxes need split=False: the split decode's scout and sync passes must see the whole run whatever the box")
+            raise ValueError("boxes need split=False: the split decode's scout and sync passes must see the whole run whatever the box "
+                             "(the split decode for boxes is decode_jpeg_batch_split_crop / launch_jpeg_split_crop)")
         if seg_bits is not None or rounds is not None or path is not None or scratch is not None:
             raise ValueError("seg_bits, rounds, path and scratch belong to split=True")
         L.require_cuda(Y, CbCr, status, *dev[:4])
@@ -460,7 +461,8 @@ def decode_jpeg_batch(plan, device="cuda", out=None, split=False, seg_bits=None,
     n = plan.n
     if boxes is not None:
         if split:
-            raise ValueError("boxes need split=False: the split decode's scout and sync passes must see the whole run whatever the box")
+            raise ValueError("boxes need split=False: the split decode's scout and sync passes must see the whole run whatever the box "
+                             "(the split decode for boxes is decode_jpeg_batch_split_crop / launch_jpeg_split_crop)")
         bx = _check_boxes(boxes, n, plan.grid)
         y_off, c_off, ny, ncc = packed_offsets(bx)
         if out is None:
@@ -487,6 +489,96 @@ def decode_jpeg_batch(plan, device="cuda", out=None, split=False, seg_bits=None,
     return out + (path,) if return_path else out
 
 
+# ---- the split decode for a crop box per file (rgbnm_jpeg_decode_batch_split_crop) ------------------------------------------------
+def jpeg_split_crop_scratch(plan, seg_bits=None, device="cuda"):
+    """uint8 device tensor for launch_jpeg_split_crop(scratch=...) on this plan (or any with no more stream bytes and runs)."""
+    from . import lib as L
+    nbytes = L.lib().rgbnm_jpeg_split_crop_scratch_bytes(plan.stream_bytes, plan.nruns,
+                                                         JPEG_SPLIT_SEG_BITS if seg_bits is None else int(seg_bits))
+    if nbytes == 0:
+        raise L.RgbnmError("seg_bits must be a multiple of 32 in 128..65536")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def launch_jpeg_split_crop(plan, dev, out, boxes, packed_out, path=None, scratch=None, seg_bits=None, rounds=None, walked=None,
+                           seg_live=None):
+    """The split decode for a crop box per file, the launches alone (no copy, no sync: capturable): launch_jpeg_decode(split=True)'s
+    scout, sync and verify passes over the whole runs, then only the segments that hold a block of a file's box are walked, in dense
+    waves, and only the boxes are stored, packed as launch_jpeg_decode(boxes=...) packs them.  For files without restart markers.
+    dev: upload_jpeg_plan's tensors; out: (Ypacked, Cpacked, quant, status) device tensors (alloc_jpeg_packed), quant and status
+    already holding the plan's; boxes: int32 (n, 4) DEVICE tensor; packed_out = (y_off, c_off, y_elems, c_elems) with int64 [n] device
+    offsets; path int32 [n], scratch (jpeg_split_crop_scratch): from the caching allocator when None; seg_bits, rounds: the split
+    decode's defaults; walked, seg_live: int32 [plan.nruns] device tensors or None -- the MCUs the one-lane walk took of each run, the
+    segments the write pass walked of each split run.  The device checks every box and offset again (RGBNM_JPEG_EBOX).  Returns path."""
+    from . import lib as L
+    Y, CbCr, _, status = out
+    hb, wb = plan.grid
+    hbc, wbc = (hb + 1) // 2, (wb + 1) // 2
+    n = plan.n
+    if not torch.is_tensor(boxes) or packed_out is None:
+        raise ValueError("boxes must be a device tensor and packed_out=(y_off, c_off, y_elems, c_elems) given: this is the capturable "
+                         "launch (decode_jpeg_batch_split_crop uploads them)")
+    y_off, c_off, ny, ncc = packed_out
+    L.require_cuda(Y, CbCr, status, *dev[:4])
+    L.require_cuda(boxes, y_off, c_off)
+    seg_bits = JPEG_SPLIT_SEG_BITS if seg_bits is None else int(seg_bits)
+    rounds = JPEG_SPLIT_ROUNDS if rounds is None else int(rounds)
+    with torch.cuda.device(Y.device):
+        if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, 4) or not boxes.is_contiguous():
+            raise L.RgbnmError("boxes must be int32 (n, 4)")
+        if any(t.dtype != torch.int64 or t.numel() != n or not t.is_contiguous() for t in (y_off, c_off)):
+            raise L.RgbnmError("y_off and c_off must be int64 [n]")
+        if Y.dim() != 1 or CbCr.dim() != 1 or Y.dtype != torch.int16 or CbCr.dtype != torch.int16 or not Y.is_contiguous() \
+                or not CbCr.is_contiguous() or int(ny) > Y.numel() or int(ncc) > CbCr.numel() or status.numel() != n \
+                or status.dtype != torch.int32:
+            raise L.RgbnmError("out tensors do not match the boxes (alloc_jpeg_packed)")
+        for name, t in (("walked", walked), ("seg_live", seg_live)):
+            if t is not None:
+                L.require_cuda(t)
+                if t.dtype != torch.int32 or t.numel() < plan.nruns or not t.is_contiguous():
+                    raise L.RgbnmError(f"{name} must be int32 [plan.nruns]")
+        if scratch is None:
+            scratch = jpeg_split_crop_scratch(plan, seg_bits, Y.device)
+        if path is None:
+            path = torch.empty(n, dtype=torch.int32, device=Y.device)
+        L.require_cuda(path, scratch)
+        if path.dtype != torch.int32 or path.numel() != n or not path.is_contiguous() or scratch.dtype != torch.uint8 \
+                or not scratch.is_contiguous():
+            raise L.RgbnmError("path must be int32 [n], scratch uint8 (jpeg_split_crop_scratch)")
+        dp = L.JpegDevicePlan(stream=dev[0].data_ptr(), stream_bytes=plan.stream_bytes, runs=dev[1].data_ptr(), images=dev[2].data_ptr(),
+                              tables=dev[3].data_ptr(), nruns=plan.nruns, ntables=plan.ntables)
+        L.check(L.lib().rgbnm_jpeg_decode_batch_split_crop(
+            C.byref(dp), n, hb, wb, hbc, wbc, boxes.data_ptr(), y_off.data_ptr(), c_off.data_ptr(), Y.data_ptr(), int(ny), CbCr.data_ptr(),
+            int(ncc), status.data_ptr(), path.data_ptr(), walked.data_ptr() if walked is not None else None,
+            seg_live.data_ptr() if seg_live is not None else None, scratch.data_ptr(), scratch.numel(), seg_bits, rounds, L.stream()),
+            "jpeg_decode_batch_split_crop")
+    return path
+
+
+def decode_jpeg_batch_split_crop(plan, device="cuda", boxes=None, out=None, seg_bits=None, rounds=None, return_path=False):
+    """decode_jpeg_batch(boxes=...) through the split decode (launch_jpeg_split_crop), for files without restart markers: (Ypacked,
+    Cpacked, quant, status, y_off, c_off), and the int32 path per file as a seventh with return_path=True.  The same packed bits.  For
+    a file with path 1 the status is the whole decode's; for the others decode_jpeg_batch(boxes=...)'s caveat stands."""
+    if boxes is None:
+        raise ValueError("boxes are required (decode_jpeg_batch(split=True) decodes whole grids)")
+    n = plan.n
+    bx = _check_boxes(boxes, n, plan.grid)
+    y_off, c_off, ny, ncc = packed_offsets(bx)
+    if out is None:
+        out = alloc_jpeg_packed(n, plan.grid, device)
+    dev = upload_jpeg_plan(plan, out[0].device)
+    out = (out[0], out[1], out[2][:n], out[3][:n])
+    out[2].copy_(dev[4], non_blocking=True)
+    out[3].copy_(dev[5], non_blocking=True)
+    d = out[0].device
+    packed = (y_off.to(d, non_blocking=True), c_off.to(d, non_blocking=True), ny, ncc)
+    path = launch_jpeg_split_crop(plan, dev, out, bx.to(d, non_blocking=True), packed, seg_bits=seg_bits, rounds=rounds)
+    for t in dev[:4]:
+        t.record_stream(torch.cuda.current_stream(d))
+    res = (out[0][:ny], out[1][:ncc], out[2], out[3], packed[0], packed[1])
+    return res + (path,) if return_path else res
+
+
 def jpeg_status_text(code):
     from . import lib as L
     return L.JPEG_STATUS.get(int(code), f"status {int(code)}")
@@ -510,13 +602,14 @@ def read_coefficients_batch_device(paths_or_bytes, grid=(64, 64), device="cuda",
     return Y, CbCr, quant
 
 
-def read_coefficients_batch_crop_device(paths_or_bytes, boxes, grid=(64, 64), device="cuda"):
+def read_coefficients_batch_crop_device(paths_or_bytes, boxes, grid=(64, 64), device="cuda", split=False):
     """read_coefficients_batch_crop with the entropy decode on the device: (Ypacked, Cpacked, quant, y_off, c_off), all DEVICE
     tensors.  A bad box raises the host crop reader's ValueError; a file the device cannot decode raises, naming it (synchronises to
-    read the device status)."""
+    read the device status).  split: the split decode for boxes (decode_jpeg_batch_split_crop), for files without restart markers."""
     bx = _check_boxes(boxes, len(paths_or_bytes), grid)
     plan = prepare_jpeg_batch(paths_or_bytes, grid)
-    Yp, Cp, quant, status, y_off, c_off = decode_jpeg_batch(plan, device, boxes=bx)
+    decode = decode_jpeg_batch_split_crop if split else decode_jpeg_batch
+    Yp, Cp, quant, status, y_off, c_off = decode(plan, device, boxes=bx)
     _raise_device_status(plan, status)
     return Yp, Cp, quant, y_off, c_off
 

@@ -181,6 +181,9 @@ PROTOTYPES = {
     "rgbnm_jpeg_split_scratch_bytes": (_sz, [_sz, _i, _i]),
     "rgbnm_jpeg_decode_batch_split": (_i, [_P(JpegDevicePlan), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
     "rgbnm_jpeg_decode_batch_crop": (_i, [_P(JpegDevicePlan), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "rgbnm_jpeg_split_crop_scratch_bytes": (_sz, [_sz, _i, _i]),
+    "rgbnm_jpeg_decode_batch_split_crop": (_i, [_P(JpegDevicePlan), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp,
+                                                _vp, _sz, _i, _i, _vp]),
     "rgbnm_jpeg_encode_bound": (_sz, [_i, _i, _i, _i, _i, _i]),
     "rgbnm_jpeg_encode_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _sz]),
     "rgbnm_jpeg_encode_header": (_i, [_i, _i, _i, _vp, _i, _vp, _sz]),

@@ -40,6 +40,9 @@ the box needs, and only the boxes are stored, packed as the host crop reader pac
 (apply_packed).  Same output bits as crop_on_host=True at the same seed and epoch.  A file's status then says nothing about stream
 bytes behind the last MCU its box needed.  Files without restart markers are walked by one lane each up to that MCU (jpeg_split takes
 no box: not combinable); the gain comes from restart markers.
+`crop_on_device="split"` (same conditions, jpeg_split stays False): the crop launch is the split decode for crop boxes
+(dm.launch_jpeg_split_crop) -- for files WITHOUT restart markers: their runs are cut into bit segments, and only the segments that hold
+a block of a file's box are walked for the stores.  Same output bits; `.crop_on_device` is True and `.crop_split` says which launch.
 `jpeg_split=True` (with decode="device" only): the launch is the split decode (dct_manip.launch_jpeg_decode(split=True)): runs of
 files without restart markers are cut into bit segments, one lane each; the same tensors, bit for bit.
 
@@ -78,7 +81,10 @@ class DCTBatchLoader:
                                  "boxes are drawn before the decode; the eval transform reads the whole grid")
         if decode not in ("host", "device"):
             raise ValueError(f'decode must be "host" or "device", got {decode!r}')
+        if crop_on_device not in (False, True, "split"):
+            raise ValueError(f'crop_on_device must be False, True or "split", got {crop_on_device!r}')
         self.crop_on_device = bool(crop_on_device)
+        self.crop_split = crop_on_device == "split"          # the crop launch is the split decode's (launch_jpeg_split_crop)
         if self.crop_on_device and self.crop_on_host:
             raise ValueError("crop_on_device and crop_on_host are the same crop on the two sides of PCIe: choose one")
         if decode == "device" and self.crop_on_host:
@@ -90,8 +96,9 @@ class DCTBatchLoader:
             if decode != "device":
                 raise ValueError('crop_on_device=True is the crop of the DEVICE decode: it needs decode="device"')
             if jpeg_split:
-                raise ValueError("crop_on_device=True cannot be combined with jpeg_split=True: the split decode takes no crop box (its "
-                                 "scout and sync passes must see the whole run)")
+                raise ValueError("crop_on_device=True cannot be combined with jpeg_split=True: the whole-grid split decode takes no crop "
+                                 'box (its scout and sync passes must see the whole run); crop_on_device="split" with jpeg_split=False '
+                                 "is the split decode for crop boxes")
             if not isinstance(transform, CT.TrainTransform_DCT) or transform.eval_mode or self.device.type != "cuda":
                 raise ValueError("crop_on_device needs the fused train transform (TrainTransform_DCT) and a HIP device: the crop "
                                  "boxes are drawn before the decode; the eval transform reads the whole grid")
@@ -200,7 +207,10 @@ class DCTBatchLoader:
             Yp = torch.empty(ny, dtype=torch.int16, device=self.device)
             Cp = torch.empty(ncc, dtype=torch.int16, device=self.device)
             Q, st = dev[4], dev[5]
-            dm.launch_jpeg_decode(plan, dev, (Yp, Cp, Q, st), boxes=boxes, packed_out=(yo, co, ny, ncc))
+            if self.crop_split:
+                dm.launch_jpeg_split_crop(plan, dev, (Yp, Cp, Q, st), boxes, (yo, co, ny, ncc))
+            else:
+                dm.launch_jpeg_decode(plan, dev, (Yp, Cp, Q, st), boxes=boxes, packed_out=(yo, co, ny, ncc))
             for t in dev[:4]:
                 t.record_stream(stream)
             for k, y0, yc, c0, csz, cc, q in cut:      # refused by prepare: the kernel leaves these slots alone

@@ -3,7 +3,10 @@
 tree to gfx950 device assembly with build.py's flags (RGBNM_HIPCC_FLAGS included) plus the file's own `// hipcc-flags:` line, and
 compare the two after dropping what depends on the text and not on the code (.file, .ident, comments, and every line naming
 __hip_cuid_, a hash of the translation unit's text).  Prints `identical` or the first differing lines per file; exits 1 on any
-difference.  usage: python tools/isa_diff.py [REV] [file.hip ...]   (REV defaults to HEAD~1; no file names = every file)"""
+difference.  usage: python tools/isa_diff.py [REV] [file.hip ...]   (REV defaults to HEAD~1; no file names = every file)
+With --kernels PATTERN (a regular expression over the mangled names) only the bodies of the matching functions are compared, each from
+its label to its end, with the function numbers in local labels dropped: for a change that ADDS kernels to a file and must leave
+the existing ones what they were."""
 import os
 import re
 import subprocess
@@ -36,8 +39,29 @@ def asm(tree, name):
     return out
 
 
+def bodies(lines, pattern):
+    """name -> instruction lines of every function whose mangled name matches; local labels lose their function number."""
+    out, name = {}, None
+    for t in lines or []:
+        m = re.match(r"(\w+):$", t)
+        if name is None and m and re.search(pattern, m.group(1)) and not m.group(1).startswith("."):
+            name = m.group(1)
+            out[name] = []
+        elif name is not None:
+            if re.match(r"\.Lfunc_end\d+:$", t):
+                name = None
+            else:
+                out[name].append(re.sub(r"\.L(BB|tmp|func_begin)\d+_?", r".L\1_", t))
+    return out
+
+
 def main():
     args = sys.argv[1:]
+    pattern = None
+    if "--kernels" in args:
+        k = args.index("--kernels")
+        pattern = args[k + 1]
+        del args[k:k + 2]
     rev = args.pop(0) if args and not args[0].endswith(".hip") else "HEAD~1"
     names = [os.path.basename(a) for a in args] or sorted(f for f in os.listdir(os.path.join(ROOT, CSRC)) if f.endswith(".hip"))
     bad = 0
@@ -47,6 +71,14 @@ def main():
         with ThreadPoolExecutor(max_workers=4) as ex:
             pairs = ex.map(lambda n: (n, asm(old, n), asm(ROOT, n)), names)
             for n, a, b in pairs:
+                if pattern is not None:
+                    ka, kb = bodies(a, pattern), bodies(b, pattern)
+                    for name in sorted(set(ka) | set(kb)):
+                        same, only = ka.get(name) == kb.get(name), name not in ka or name not in kb
+                        bad += not same and not only
+                        verdict = "identical" if same else f"only in {'the working tree' if name not in ka else rev}" if only else "DIFFERS"
+                        print(f"{n:24s} {name:72s} {verdict}  ({len(ka.get(name, []))} -> {len(kb.get(name, []))} lines)")
+                    continue
                 if a == b:
                     print(f"{n:24s} identical  ({len(b)} lines)")
                     continue

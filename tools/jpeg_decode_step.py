@@ -26,10 +26,19 @@ tests/test_loader_gpu.py makes them (16 x 16 random colours upsampled bicubic, p
       and on those with a marker per MCU row; each a process of its own per round.
   (x) and (y) go to profiles/jpeg_crop.json.
 
+  (z) the SPLIT decode launch FOR CROP BOXES (dct_manip.launch_jpeg_split_crop: scout, sync and verify over the whole runs, the write
+      pass only over the segments that hold a block of an image's box, compacted into dense waves, only the boxes stored) beside the
+      whole-grid split launch -- the yardstick, measured again here -- and the plain crop launch, on the marker-less q90 files, with
+      (x)'s boxes and the split decode's defaults: bytes written, the live share of the segments (from the launch's `seg_live`
+      array) and the share of images per `path` value.
+  (w) tools/pipeline_bench.py images/s with --decode device --crop-on-device split beside --decode device --jpeg-split (the
+      yardstick) and plain --decode device, on the marker-less files; each a process of its own per round.
+  (z) and (w) go to profiles/jpeg_split_crop.json.
+
 Protocol of the other step tools: warm-up, then ROUNDS interleaved rounds (order reversed every other round); median and min - max.
-Writes profiles/jpeg_decode.json, or profiles/jpeg_split.json for parts s / p, or profiles/jpeg_crop.json for parts x / y (parts
-given with --parts are replaced, the others kept), and prints it.
-usage: python tools/jpeg_decode_step.py [--parts a,b,c | s,p | x,y] [--rounds 6] [--batch 256]"""
+Writes profiles/jpeg_decode.json, or profiles/jpeg_split.json for parts s / p, or profiles/jpeg_crop.json for parts x / y, or
+profiles/jpeg_split_crop.json for parts z / w (parts given with --parts are replaced, the others kept), and prints it.
+usage: python tools/jpeg_decode_step.py [--parts a,b,c | s,p | x,y | z,w] [--rounds 6] [--batch 256]"""
 import argparse
 import io
 import json
@@ -232,6 +241,63 @@ def part_x(B, rounds, iters, warmup):
     return out
 
 
+def part_z(B, rounds, iters, warmup):
+    from rgb_no_more_amd import custom_transforms as CT
+    dev = torch.device("cuda", 0)
+    packed, _ = CT.FastParamSampler(CT.TrainTransform_DCT(out_dtype=torch.bfloat16), seed=1234).sample(B, 64, 64)
+    boxes = torch.from_numpy(packed["crop"].astype("int32"))
+    y_off, c_off, ny, ncc = DM.packed_offsets(boxes)
+    bdev, yo, co = boxes.to(dev), y_off.to(dev), c_off.to(dev)
+    sb, nr = DM.JPEG_SPLIT_SEG_BITS, DM.JPEG_SPLIT_ROUNDS
+    files = synth(64, **SETS["q90"])
+    batch = [files[i % 64] for i in range(B)]
+    plan = DM.prepare_jpeg_batch(batch, grid=(64, 64))
+    assert plan.nbad == 0
+    up = DM.upload_jpeg_plan(plan, dev)
+    out = DM.alloc_jpeg_out(B, (64, 64), dev)
+    out[2].copy_(up[4])
+    out[3].copy_(up[5])
+    path = torch.empty(B, dtype=torch.int32, device=dev)
+    scratch = DM.jpeg_split_scratch(plan, sb, dev)
+    DM.launch_jpeg_decode(plan, up, out, split=True, path=path, scratch=scratch)
+    pk = (torch.full((ny,), 0x5555, dtype=torch.int16, device=dev), torch.full((ncc,), 0x5555, dtype=torch.int16, device=dev),
+          out[2].clone(), up[5].clone())
+    pk2 = tuple(t.clone() for t in pk)
+    xpath = torch.empty(B, dtype=torch.int32, device=dev)
+    xscratch = DM.jpeg_split_crop_scratch(plan, sb, dev)
+    seg_live = torch.full((plan.nruns,), -1, dtype=torch.int32, device=dev)
+    DM.launch_jpeg_split_crop(plan, up, pk, bdev, (yo, co, ny, ncc), path=xpath, scratch=xscratch, seg_live=seg_live)
+    DM.launch_jpeg_decode(plan, up, pk2, boxes=bdev, packed_out=(yo, co, ny, ncc))
+    torch.cuda.synchronize()
+    # the bits that are timed: the boxes cut out of the whole-grid split launch's output, and the plain crop launch's
+    for i in range(B):
+        t, l, h, w = boxes[i].tolist()
+        assert torch.equal(pk[0][int(y_off[i]):int(y_off[i]) + h * w * 64], out[0][i, 0, t:t + h, l:l + w].reshape(-1)), i
+        assert torch.equal(pk[1][int(c_off[i]):int(c_off[i]) + h * w * 32], out[1][i, :, t // 2:(t + h) // 2, l // 2:(l + w) // 2].reshape(-1)), i
+    assert torch.equal(pk[0], pk2[0]) and torch.equal(pk[1], pk2[1]) and torch.equal(path, xpath)
+    assert int(pk[3].min()) == 0 and int(out[3].min()) == 0
+    nbytes = plan.runs[:plan.nruns, 1].to(torch.int64) & 0xFFFFFFFF
+    nseg = (nbytes * 8 + sb - 1) // sb
+    written = (xpath.cpu() == 1)[plan.runs[:plan.nruns, 2].to(torch.int64)] & (nseg >= 16)
+    share = [float((path == v).sum()) / B for v in (0, 1, 2)]
+    base = {"runs": plan.nruns, "seg_bits": sb, "sync_rounds": nr, "path_share": share, "stream_bytes": plan.stream_bytes}
+    meta = {"q90_split": dict(base, bytes_written=2 * (out[0].numel() + out[1].numel()), scratch_bytes=scratch.numel()),
+            "q90_split_crop": dict(base, bytes_written=2 * (ny + ncc), scratch_bytes=xscratch.numel(), box_share_of_grid=ny / (B * 64 * 64 * 64),
+                                   segments=int(nseg[written].sum()), segments_live=int(seg_live.cpu()[written].sum()),
+                                   live_share_of_segments=float(seg_live.cpu()[written].sum()) / max(1, int(nseg[written].sum()))),
+            "q90_crop": {"runs": plan.nruns, "bytes_written": 2 * (ny + ncc)}}
+    fns = {"q90_split": lambda: DM.launch_jpeg_decode(plan, up, out, split=True, path=path, scratch=scratch),
+           "q90_split_crop": lambda: DM.launch_jpeg_split_crop(plan, up, pk, bdev, (yo, co, ny, ncc), path=xpath, scratch=xscratch),
+           "q90_crop": lambda: DM.launch_jpeg_decode(plan, up, pk2, boxes=bdev, packed_out=(yo, co, ny, ncc))}
+    res = summary(timed(list(fns), fns, warmup, rounds, iters))
+    for k, v in res.items():
+        v.update(meta[k])
+        v["images_per_s"] = B / v["ms_median"] * 1e3
+        print(f"(z) {k}: {v['ms_median']:.3f} ms ({v['ms_min']:.3f} - {v['ms_max']:.3f}) per batch, {v['bytes_written'] / 1e6:.1f} MB written, "
+              f"live share {v.get('live_share_of_segments')}", file=sys.stderr)
+    return res
+
+
 PIPELINE = {"host_16_threads": ["--decode", "host", "--threads", "16"],
             "device": ["--decode", "device", "--threads", "16", "--prefetch", "4"],
             "device_rst_row": ["--decode", "device", "--threads", "16", "--prefetch", "4", "--restart-rows", "1"]}
@@ -242,6 +308,10 @@ PIPELINE_SPLIT = {"host_16_threads": PIPELINE["host_16_threads"], "device": PIPE
 
 PIPELINE_CROP = {"device": PIPELINE["device"], "device_crop": PIPELINE["device"] + ["--crop-on-device"],
                  "device_rst_row": PIPELINE["device_rst_row"], "device_rst_row_crop": PIPELINE["device_rst_row"] + ["--crop-on-device"]}
+
+
+PIPELINE_SPLIT_CROP = {"device": PIPELINE["device"], "device_split": PIPELINE["device"] + ["--jpeg-split"],
+                       "device_crop_split": PIPELINE["device"] + ["--crop-on-device", "split"]}
 
 
 def part_c(B, rounds, steps, warmup, cfgs=PIPELINE):
@@ -275,11 +345,12 @@ def main():
     ap.add_argument("--out", default=None, help="default: profiles/jpeg_split.json for parts s / p, else profiles/jpeg_decode.json")
     a = ap.parse_args()
     parts = a.parts.split(",")
-    groups = [g for g in ({"a", "b", "c"}, {"s", "p"}, {"x", "y"}) if set(parts) & g]
+    groups = [g for g in ({"a", "b", "c"}, {"s", "p"}, {"x", "y"}, {"z", "w"}) if set(parts) & g]
     if len(groups) != 1:
-        raise SystemExit("parts a / b / c, s / p and x / y write different files: run them separately")
+        raise SystemExit("parts a / b / c, s / p, x / y and z / w write different files: run them separately")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", {"a": "jpeg_decode.json", "s": "jpeg_split.json", "x": "jpeg_crop.json"}[min(groups[0])])
+        a.out = os.path.join(ROOT, "profiles", {"a": "jpeg_decode.json", "p": "jpeg_split.json", "x": "jpeg_crop.json",
+                                                "w": "jpeg_split_crop.json"}[min(groups[0])])
     assert torch.cuda.is_available(), "needs the GPU"
     torch.cuda.set_device(0)
     res = {}
@@ -304,6 +375,10 @@ def main():
         res["x_crop_launch"] = part_x(a.batch, a.rounds, a.iters, a.warmup)
     if "y" in parts:
         res["y_pipeline"] = part_c(a.batch, a.rounds, a.steps, 8, PIPELINE_CROP)
+    if "z" in parts:
+        res["z_split_crop_launch"] = part_z(a.batch, a.rounds, a.iters, a.warmup)
+    if "w" in parts:
+        res["w_pipeline"] = part_c(a.batch, a.rounds, a.steps, 8, PIPELINE_SPLIT_CROP)
     line = json.dumps(res)
     with open(a.out, "w") as fh:
         fh.write(line + "\n")

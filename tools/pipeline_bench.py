@@ -50,8 +50,9 @@ def main():
     ap.add_argument("--prefetch", type=int, default=2, help="batches the loader keeps ahead of the step")
     ap.add_argument("--jpeg-split", action="store_true",
                     help="with --decode device: long runs are cut into bit segments, one lane each (loader jpeg_split)")
-    ap.add_argument("--crop-on-device", action="store_true",
-                    help="with --decode device: the decode walks and stores only each image's crop box (loader crop_on_device)")
+    ap.add_argument("--crop-on-device", nargs="?", const=True, default=False, choices=("split",),
+                    help="with --decode device: the decode walks and stores only each image's crop box (loader crop_on_device); "
+                         "`--crop-on-device split`: through the split decode, for files without restart markers")
     a = ap.parse_args()
     if a.decode == "device":
         a.crop_on_host = 0
@@ -129,7 +130,7 @@ def main():
            "ms_per_step": round(1e3 * dt / a.steps, 3), "per_gpu_batch": B, "host_threads": a.threads,
            "host_decode_only_images_per_sec": round(dec, 1), "avg_jpeg_bytes": round(fsize),
            "h2d_bytes_per_image": round(h2d),
-           "crop_on_host": bool(a.crop_on_host), "crop_on_device": bool(a.crop_on_device),
+           "crop_on_host": bool(a.crop_on_host), "crop_on_device": bool(a.crop_on_device), "crop_split": a.crop_on_device == "split",
            "loss": round(float(loss.item()), 4),
            "note": "one process; decoder thread (pthread pool inside librgbnm_reader.so, GIL released) runs two batches "
                    "ahead; bounded by the host Huffman decode when value ~ host_decode_only"}
